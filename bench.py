@@ -6,6 +6,11 @@ Workload (BASELINE.json configs[1]): KITTI seq-00-shaped sequence, 4541 HDL-64 s
 over the whole resident sequence: lmono_scanreg_batch + lmono_odom_batch_d (+ the RCCL pose exchange when N > 1).
 Inputs are resident in HBM before the timed region.  Weak scaling: every rank processes its own 4541-scan range of
 one long trajectory; value = scans of all ranks * steps / max-over-ranks time.
+
+A plain run sets up, warms up, times --steps steps and prints the result line.  --full adds what the headline does not need:
+parity against the committed CPU trajectory, the untimed extras (sequential schedule, latency, streaming, BA, stress world) and
+the CPU baselines.  --dump-outputs DIR writes the last timed step's outputs as .npy files (the inputs are seeded: two builds
+compare output for output).
 """
 import argparse
 import json
@@ -824,7 +829,10 @@ def main():
     ap.add_argument("--seq", type=int, default=0, choices=[0, 1, 2], help="0: the S1 figure-8 sequence (headline); 1: the held-out sequence (other world, clover trajectory); "
                     "2: the stress sequence (cluttered world: small boxes, 20 %% stray returns, moving cylinders, dropped ring sectors)")
     ap.add_argument("--az", type=int, default=2000, help="azimuth steps per ring (2000 = HDL-64 at 10 Hz)")
-    ap.add_argument("--cpu-sample", type=int, default=128, help="scans of the CPU baseline sample (0 = skip)")
+    ap.add_argument("--full", action="store_true", help="also the parity figures, the untimed extras and the CPU baselines (off: the headline only)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="write the last timed step's outputs (poses, increments, scan counts, "
+                    "boundary residuals) as DIR/<name>.npy, float64")
+    ap.add_argument("--cpu-sample", type=int, default=128, help="scans of the CPU baseline sample (with --full; 0 = skip)")
     ap.add_argument("--cpu-frames", type=int, default=-1, help="ba-seq: frames of the CPU oracle's replay (-1 = the whole stream)")
     ap.add_argument("--stream-chunks", type=int, default=8, help="streamed extra: scan ranges the sequence streams through two working sets in")
     ap.add_argument("--stream-chains", type=int, default=64, help="streamed extra: chains per range (0 = --chains / --stream-chunks)")
@@ -843,6 +851,10 @@ def main():
     ap.add_argument("--frames", type=int, default=20, help="colour: frames per stream and step")
     ap.add_argument("--keyframes", type=int, default=4541, help="posegraph: keyframes of the graph")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.workload != "lidar":
+        ap.error("--dump-outputs: the lidar workload only")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args))
     if args.probe_ranks:
@@ -940,7 +952,7 @@ def main():
     torch.cuda.synchronize()
     h2d_s = time.time() - t0
     sample = None
-    if rank == 0 and world == 1 and args.cpu_sample > 0:
+    if args.full and rank == 0 and world == 1 and args.cpu_sample > 0:
         m = min(args.cpu_sample, n_local)
         sample = (np.ascontiguousarray(xyzi[:off[m]]), off[:m + 1].copy())
     del xyzi, xyzi_t
@@ -1002,11 +1014,16 @@ def main():
     n_cloud_mean = float(cnt[:, 0].mean())
     gpu_incr = incr_d.cpu().numpy()
     gpu_poses = poses_d.cpu().numpy()
+    if args.dump_outputs and rank == 0:
+        # what a caller of the timed path receives from its last step (rank 0's share): 160 B per scan, 0.7 MB for the 4541-scan default
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, a in (("poses", gpu_poses), ("incr", gpu_incr), ("scan_counts", cnt), ("boundary_residual", boundary[-1]["resid"])):
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), np.asarray(a, np.float64))
 
     # ---- tolerance of the timed run: its poses against the committed trajectory of the strictly sequential CPU path over
     # the WHOLE sequence (tests/golden/s1_seq00_oracle.npz: data, not the oracle), every owned scan the fixture covers
     parity = None
-    if not args.kitti_dir and args.az == 2000 and os.path.exists(GOLDEN % args.seq):
+    if args.full and not args.kitti_dir and args.az == 2000 and os.path.exists(GOLDEN % args.seq):
         gold = np.load(GOLDEN % args.seq)
         gp, gi, gc = gold["poses"], gold["incr"], gold["feat_counts"]
         hi = min(own_end, len(gp))
@@ -1139,13 +1156,13 @@ def main():
             out["ate_vs_cpu_m"] = parity["ate_vs_cpu_m"]
             out["rpe_vs_cpu"] = parity["rpe_vs_cpu"]
             out["parity"] = parity
-        if traj is not None:
-            m_gt = min(n_own, len(traj))
-            out["ate_vs_truth_m"] = round(trajectory.ate(gpu_poses[:m_gt], _gt_relative(traj[:m_gt])), 4) if rank == 0 and own_begin == 0 else None
-        else:
+        if traj is None:
             out["data"] = "KITTI-layout sequence " + args.kitti_dir
             out["config"]["workload"] = "KITTI-layout sequence on disk, laserOdometry-only (configs[1])"
-        if world == 1 and not args.no_extras:
+        elif args.full:
+            m_gt = min(n_own, len(traj))
+            out["ate_vs_truth_m"] = round(trajectory.ate(gpu_poses[:m_gt], _gt_relative(traj[:m_gt])), 4) if rank == 0 and own_begin == 0 else None
+        if args.full and world == 1 and not args.no_extras:
             # ---- untimed extras.  (1) A-LOAM's own schedule: ONE chain, no lead-in (every scan pair warm-started from the
             # previous increment) -- the run whose poses must EQUAL the CPU path's, and the throughput of that schedule
             seq_incr = torch.zeros((n_local, 7), dtype=torch.float64, device=dev)

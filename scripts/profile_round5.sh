@@ -29,9 +29,9 @@ for grp in FETCH_SIZE WRITE_SIZE "TCC_HIT_sum TCC_MISS_sum" "SQ_INSTS_VALU SQ_IN
   rm -rf $OUT/pmc_$tag $OUT/pmc_$tag.out
 done
 echo "[1/3] headline traces and counters done"
-timeout -k 10 300 python3 bench.py > $OUT/final_bench_4541scans.json 2> $OUT/bench.err
-timeout -k 10 300 python3 bench.py --seq 1 --no-extras --cpu-sample 0 > $OUT/final_bench_seq1_held_out.json 2> $OUT/bench1.err
-timeout -k 10 300 python3 bench.py --seq 2 --no-extras --cpu-sample 0 > $OUT/final_bench_seq2_stress.json 2> $OUT/bench2.err
+timeout -k 10 300 python3 bench.py --full > $OUT/final_bench_4541scans.json 2> $OUT/bench.err
+timeout -k 10 300 python3 bench.py --full --seq 1 --no-extras --cpu-sample 0 > $OUT/final_bench_seq1_held_out.json 2> $OUT/bench1.err
+timeout -k 10 300 python3 bench.py --full --seq 2 --no-extras --cpu-sample 0 > $OUT/final_bench_seq2_stress.json 2> $OUT/bench2.err
 fi
 # ---- 2. BA half
 if [ "$PART" = all ] || [ "$PART" = ba ]; then

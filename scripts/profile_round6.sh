@@ -51,9 +51,9 @@ json.dump(out, open("$OUT/pmc_k_correspond.json", "w"), indent=1)
 print("k_corr_flat per launch:", {k: v for k, v in out.items() if k.endswith("per_launch") or k == "l2_hit_rate"})
 PY
 echo "[headline] traces and counters done"
-timeout -k 10 400 python3 bench.py > $OUT/final_bench_4541scans.json 2> $OUT/bench.err
-timeout -k 10 300 python3 bench.py --seq 1 --no-extras --cpu-sample 0 > $OUT/final_bench_seq1_held_out.json 2> $OUT/bench1.err
-timeout -k 10 300 python3 bench.py --seq 2 --no-extras --cpu-sample 0 > $OUT/final_bench_seq2_stress.json 2> $OUT/bench2.err
+timeout -k 10 400 python3 bench.py --full > $OUT/final_bench_4541scans.json 2> $OUT/bench.err
+timeout -k 10 300 python3 bench.py --full --seq 1 --no-extras --cpu-sample 0 > $OUT/final_bench_seq1_held_out.json 2> $OUT/bench1.err
+timeout -k 10 300 python3 bench.py --full --seq 2 --no-extras --cpu-sample 0 > $OUT/final_bench_seq2_stress.json 2> $OUT/bench2.err
 head -6 $OUT/final_kernel_stats_4541scans_main_pass_only.csv | cut -c1-200
 tail -1 $OUT/final_bench_4541scans.json | cut -c1-400
 fi

@@ -7,7 +7,7 @@ CFGS=${3:-"6,0 6,1 4,1 8,0 8,1 10,0 12,0"}
 for S in $SEQS; do
   for cfg in $CFGS; do
     L=${cfg%,*}; X=${cfg#*,}
-    timeout -k 10 300 python3 bench.py --seq $S --no-extras --cpu-sample 0 --steps 5 --lead $L --lead-seed $X > $O/seq${S}_l${L}_s${X}.json 2> $O/seq${S}_l${L}_s${X}.err || { echo "seq $S lead $L seed $X failed"; tail -3 $O/seq${S}_l${L}_s${X}.err; continue; }
+    timeout -k 10 300 python3 bench.py --full --seq $S --no-extras --cpu-sample 0 --steps 5 --lead $L --lead-seed $X > $O/seq${S}_l${L}_s${X}.json 2> $O/seq${S}_l${L}_s${X}.err || { echo "seq $S lead $L seed $X failed"; tail -3 $O/seq${S}_l${L}_s${X}.err; continue; }
     python3 - <<PY
 import json
 d=json.loads(open("$O/seq${S}_l${L}_s${X}.json").read().strip().splitlines()[-1])

@@ -15,7 +15,7 @@ while read -r flags; do
   if [ "${TESTS:-1}" != "0" ]; then
     LMONO_HIP_LIB=$lib timeout -k 10 300 python -m pytest tests/test_lidar_gpu.py -m gpu -x -q -k "correspondences or odometry_sequential or odometry_full or dense_rings or other_sensors_and_near or chain_sharded" > $OUT/t$i.log 2>&1; rc=$?
   fi
-  LMONO_HIP_LIB=$lib timeout -k 10 250 python bench.py --no-extras --cpu-sample 0 "$@" > $OUT/b$i.json 2> $OUT/b$i.err
+  LMONO_HIP_LIB=$lib timeout -k 10 250 python bench.py --full --no-extras --cpu-sample 0 "$@" > $OUT/b$i.json 2> $OUT/b$i.err
   python - <<PY
 import json
 try:

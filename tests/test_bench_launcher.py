@@ -43,6 +43,13 @@ def test_launcher_environment_is_respected():
     assert len(lines) == 1 and json.loads(lines[0])["ranks_seen"] == 2
 
 
+def test_bad_arguments_are_refused():
+    """--steps below 1 and --dump-outputs with a workload it does not cover end in a usage error before anything is set up."""
+    for argv in (["--steps", "0"], ["--workload", "ba", "--dump-outputs", "unused"]):
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + argv, capture_output=True, text=True, timeout=120)
+        assert p.returncode == 2 and "error:" in p.stderr, (argv, p.stderr[-500:])
+
+
 def test_strong_and_weak_shard_sizes():
     from lmono_amd import sharding
     # strong: 4541 scans in total over 8 ranks (configs[3]); weak: 4541 per rank

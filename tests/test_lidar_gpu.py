@@ -331,7 +331,7 @@ def test_bench_multi_rank_step_rehearsed_on_one_gpu():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, LMONO_BENCH_REHEARSE="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", "29537",
-           os.path.join(root, "bench.py"), "--gpus", "2", "--scans", "96", "--chains", "8", "--steps", "2", "--warmup", "1", "--no-extras", "--cpu-sample", "0"]
+           os.path.join(root, "bench.py"), "--gpus", "2", "--scans", "96", "--chains", "8", "--steps", "2", "--warmup", "1", "--full", "--no-extras", "--cpu-sample", "0"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=root)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-3000:]
     line = [ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1]
@@ -356,7 +356,7 @@ def test_bench_strong_scaling_step_rehearsed_with_four_ranks():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, LMONO_BENCH_REHEARSE="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "4", "--master-addr", "127.0.0.1", "--master-port", "29541",
-           os.path.join(root, "bench.py"), "--gpus", "4", "--scaling", "strong", "--steps", "2", "--warmup", "1", "--no-extras", "--cpu-sample", "0"]
+           os.path.join(root, "bench.py"), "--gpus", "4", "--scaling", "strong", "--steps", "2", "--warmup", "1", "--full", "--no-extras", "--cpu-sample", "0"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=root)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-3000:]
     d = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1])
@@ -366,6 +366,34 @@ def test_bench_strong_scaling_step_rehearsed_with_four_ranks():
     assert d["boundary_validation"]["unresolved"] == 0 and d["boundary_validation"]["rank_boundary_rounds"] >= 1
     print("4-rank strong-scaling rehearsal on one GPU: ATE vs CPU %.2e m over %d scans, chains per rank %s, rank-boundary rounds %s"
           % (d["ate_vs_cpu_m"], d["parity"]["scans_compared"], d["config"].get("odometry_chains_per_gpu"), d["boundary_validation"]["rank_boundary_rounds"]))
+
+
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """A plain bench run prints the headline line without the --full figures, and --dump-outputs writes the last timed step's outputs as
+    float64 .npy files: the same bytes in a second run, the poses and increments of --dump-poses."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    runs = []
+    for k in range(2):
+        d = tmp_path / ("out%d" % k)
+        cmd = [sys.executable, os.path.join(root, "bench.py"), "--scans", "96", "--chains", "8", "--steps", "3", "--warmup", "1",
+               "--dump-outputs", str(d), "--dump-poses", str(tmp_path / ("poses%d.npz" % k))]
+        out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=root)
+        assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-3000:]
+        line = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1])
+        runs.append((line, {f[:-4]: np.load(d / f) for f in os.listdir(d)}, np.load(tmp_path / ("poses%d.npz" % k))))
+    (a, da, pa), (_, db, _) = runs
+    assert a["steps"] == 3 and a["ms_per_step"] > 0 and a["unit"] == "scans/s" and a["higher_is_better"] is True
+    for key in ("parity", "ate_vs_cpu_m", "ate_vs_truth_m", "sequential", "latency", "streamed", "secondary", "cpu_baseline"):
+        assert key not in a, key
+    assert sorted(da) == ["boundary_residual", "incr", "poses", "scan_counts"]
+    assert da["poses"].shape == (96, 7) and da["incr"].shape == (96, 7) and da["scan_counts"].shape == (96, 6)
+    for name in da:
+        assert da[name].dtype == np.float64 and da[name].tobytes() == db[name].tobytes(), name
+    assert da["poses"].tobytes() == pa["poses"].tobytes() and da["incr"].tobytes() == pa["incr"].tobytes()
 
 
 def test_api_errors_and_limits(oracle, gpu_ctx, small_seq):

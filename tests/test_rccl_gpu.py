@@ -30,7 +30,7 @@ def _bench(extra, tmp_path, name, force, port):
 
 @pytest.mark.gpu
 def test_lidar_step_through_a_world_1_rccl_group_is_the_same_bytes(tmp_path):
-    extra = ["--scans", "192", "--chains", "16", "--no-extras", "--cpu-sample", "0"]
+    extra = ["--scans", "192", "--chains", "16", "--full", "--no-extras", "--cpu-sample", "0"]
     a, pa = _bench(extra, tmp_path, "plain", False, 29581)
     b, pb = _bench(extra, tmp_path, "rccl", True, 29583)
     assert a["config"]["parallelism"] == "no collective (1 rank)" and a["config"]["collective_ranks"] == 0

@@ -403,6 +403,42 @@ int lmono_map_builder_cloud(lmono_ctx *, lmono_map_builder *, int which, lmono_p
 int64_t lmono_map_builder_map(lmono_ctx *, lmono_map_builder *, lmono_point_rgb *out_h, int64_t cap);   /* rgb_map; returns its size */
 int lmono_map_builder_clear(lmono_ctx *, lmono_map_builder *);                         /* rgb_map->clear()                    */
 
+/* ---- image feature tracker ---------------------------------------------------------------------------------
+ * Replaces FeatureTracker::trackImage of the mono path with use_rejectF = 0 (mono_lidar_mapping/src/image_process/
+ * FeatureTracker.cc:189-433): BGR2GRAY (:193), forward / backward pyramidal LK with the 0.5 px round-trip and inBorder tests
+ * (:213-249), track_cnt++ (:251), setMask (:55-84, ties in track count kept in current order), goodFeaturesToTrack under the
+ * mask (:281-297), undistortedPts through the PINHOLE liftProjective (:172-187) and ptsVelocity (:94-133).  The pyramid of a
+ * frame and its Scharr planes stay on the device and become the previous pyramid of the next frame.  The camera is the
+ * lmono_camera of the map builder (its kernel_* / blur_type fields are not read).  Not provided: rejectWithF (:435-503; a
+ * non-zero flags argument is refused), the right-image branch (:305-347), drawTrack.                                        */
+#define LMONO_TRACK_MAX_POINTS 512   /* largest max_cnt                                       */
+#define LMONO_TRACK_GREY8      0     /* image: [height][width] uint8                          */
+#define LMONO_TRACK_BGR8       1     /* image: [height][width][3] uint8 (cv::Mat BGR8)        */
+#define LMONO_TRACK_REJECT_F   1     /* flags bit: use_rejectF -- refused                     */
+/* one feature of the frame (:372-397): id, normalised x y (z = 1), pixel u v, velocity of the normalised point, track count;
+ * id / x_n / y_n / u / v / vx / vy are FeatureManager::Image's (feature_id, xyz_uv_velocity) with camera_id 0 */
+typedef struct { int32_t id; float x_n, y_n, u, v, vx, vy; int32_t track_cnt; } lmono_track_record;
+typedef struct lmono_tracker lmono_tracker;
+/* max_cnt: MAX_CNT (1..512); min_dist: MIN_DIST in pixels (1..128); flags: 0.  NULL (see lmono_last_error) for an image side
+ * of 21 pixels or less (the LK window), limits exceeded or LMONO_TRACK_REJECT_F. */
+lmono_tracker *lmono_tracker_create(lmono_ctx *, const lmono_camera *, int max_cnt, int min_dist, int flags);
+void           lmono_tracker_destroy(lmono_tracker *);
+int            lmono_tracker_reset(lmono_ctx *, lmono_tracker *);                       /* forget points, ids and the last frame */
+/* One trackImage on a host image.  records_out: [cap >= max_cnt] (may be NULL); *n_out: features of the frame. */
+int lmono_tracker_track(lmono_ctx *, lmono_tracker *, double time, const uint8_t *image_h, int format, lmono_track_record *records_out, int cap, int *n_out);
+/* n_streams independent trackers (distinct) advanced by one frame each, images already resident in HBM (image_d[s] device
+ * pointers; times, caps, n_out host arrays [n]; records_out [n] host pointers); every phase is one launch for all streams. */
+int lmono_tracker_track_batch(lmono_ctx *, int n_streams, lmono_tracker *const *trackers, const double *times, const uint8_t *const *image_d, int format,
+                              lmono_track_record *const *records_out, const int *caps, int *n_out);
+/* diagnostics: level `level` of the last frame's pyramid and its Scharr planes (any output may be NULL); returns the number of
+ * levels (cv::buildOpticalFlowPyramid keeps a level while both sides exceed 21) */
+int lmono_tracker_pyramid(lmono_ctx *, lmono_tracker *, int level, uint8_t *image_h, int16_t *dx_h, int16_t *dy_h, int *width, int *height);
+/* min-eigenvalue corner response [height][width] fp32 of the last frame that had room for new corners */
+int lmono_tracker_response(lmono_ctx *, lmono_tracker *, float *response_h);
+/* the two cv::calcOpticalFlowPyrLK calls of :218 / :223 between the last two frames on n <= 512 given points: pts_h [n][2] ->
+ * fwd_h [n][2], rev_h [n][2], status_h [n][2] (forward, backward; backward is 0 where forward failed).  Leaves the tracks alone. */
+int lmono_tracker_lk(lmono_ctx *, lmono_tracker *, int n, const float *pts_h, float *fwd_h, float *rev_h, uint8_t *status_h);
+
 /* ---- loop-closure pose graph -- NEW FEATURE, no counterpart in the reference --------------------------
  * The reference detects loops and publishes loop_info = relative_t, relative_q (w x y z), relative_yaw
  * (mono_lidar_mapping/src/loop_detection/KeyFrame.cc:570-633) and re-anchors the window rigidly (Estimator.cc:309-365); it never

@@ -16,6 +16,8 @@ SYMBOLS = [
     "lmono_pose_prefix_d", "lmono_pose_rebase_d", "lmono_map_refine", "lmono_voxel_filter", "lmono_mapper_create", "lmono_mapper_destroy", "lmono_mapper_reset", "lmono_mapper_process", "lmono_mapper_process_batch", "lmono_mapper_cube",
     "lmono_map_builder_create", "lmono_map_builder_destroy", "lmono_associate_to_map", "lmono_associate_to_map_batch", "lmono_map_builder_depth",
     "lmono_map_builder_cloud", "lmono_map_builder_map", "lmono_map_builder_clear",
+    "lmono_tracker_create", "lmono_tracker_destroy", "lmono_tracker_reset", "lmono_tracker_track", "lmono_tracker_track_batch", "lmono_tracker_pyramid",
+    "lmono_tracker_response", "lmono_tracker_lk",
     "lmono_pose_graph_create", "lmono_pose_graph_destroy", "lmono_pose_graph_reset", "lmono_pose_graph_info", "lmono_pose_graph_reduce_buffer", "lmono_pose_graph_set_reduce_buffer", "lmono_pose_graph_linearise",
     "lmono_pose_graph_step", "lmono_pose_graph_optimize", "lmono_pose_graph_result", "lmono_factor_eval", "lmono_factor_eval_d", "lmono_factor_eval_blocks", "lmono_factor_eval_blocks_d",
     "lmono_triangulate", "lmono_outlier_scores", "lmono_shift_depth", "lmono_shift_depth_batch", "lmono_marginalize", "lmono_marg_evaluate", "lmono_marg_second_new", "lmono_ba_batch_create", "lmono_ba_batch_update", "lmono_ba_batch_destroy", "lmono_ba_solve", "lmono_ba_batch_reset", "lmono_ba_batch_read", "lmono_debug_bounds",
@@ -778,6 +780,135 @@ class MapBuilder:
             self.close()
         except Exception:
             pass
+
+
+TRACK_RECORD = np.dtype([("id", np.int32), ("x_n", np.float32), ("y_n", np.float32), ("u", np.float32), ("v", np.float32),
+                         ("vx", np.float32), ("vy", np.float32), ("track_cnt", np.int32)])
+TRACK_MAX_POINTS = 512
+
+
+def _tracker_prototypes(L):
+    L.lmono_tracker_create.restype = C.c_void_p
+    L.lmono_tracker_create.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int]
+    L.lmono_tracker_destroy.argtypes = [C.c_void_p]
+    L.lmono_tracker_reset.argtypes = [C.c_void_p, C.c_void_p]
+    L.lmono_tracker_track.argtypes = [C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+    L.lmono_tracker_track_batch.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.lmono_tracker_pyramid.argtypes = [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 5
+    L.lmono_tracker_response.argtypes = [C.c_void_p] * 3
+    L.lmono_tracker_lk.argtypes = [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 4
+
+
+def feature_frame(records):
+    """records -> FeatureManager::Image: {feature_id: [(camera_id 0, [x, y, u, v, vx, vy] float64)]} (FeatureTracker.cc:372-397)."""
+    return {int(r["id"]): [(0, np.array([r["x_n"], r["y_n"], r["u"], r["v"], r["vx"], r["vy"]], np.float64))] for r in records}
+
+
+class FeatureTracker:
+    """FeatureTracker::trackImage of the mono path on the device (lmono_tracker_*): pyramidal KLT with forward-backward check,
+    setMask, goodFeaturesToTrack, liftProjective and velocities.  track() returns the frame's TRACK_RECORD array."""
+
+    def __init__(self, ctx, camera, max_cnt=150, min_dist=30, flags=0):
+        self.ctx = ctx
+        ctx._children.add(self)
+        self.cam = camera
+        self.max_cnt = int(max_cnt)
+        _tracker_prototypes(ctx.L)
+        self.h = ctx.L.lmono_tracker_create(ctx.h, C.byref(camera), int(max_cnt), int(min_dist), int(flags))
+        if not self.h:
+            raise LmonoError("lmono_tracker_create failed: " + ctx.last_error())
+
+    def _format(self, image):
+        if image.shape == (self.cam.height, self.cam.width):
+            return 0
+        if image.shape == (self.cam.height, self.cam.width, 3):
+            return 1
+        raise LmonoError("image must be [height][width] or [height][width][3] uint8")
+
+    def track(self, time, image):
+        image = np.ascontiguousarray(image, np.uint8)
+        rec = np.zeros(TRACK_MAX_POINTS, TRACK_RECORD)
+        n = C.c_int(0)
+        self.ctx.check(self.ctx.L.lmono_tracker_track(self.ctx.h, self.h, float(time), image.ctypes.data, self._format(image), rec.ctypes.data, len(rec), C.addressof(n)))
+        return rec[:n.value].copy()
+
+    def track_image(self, time, image):
+        """trackImage(time, image) -> FeatureManager::Image."""
+        return feature_frame(self.track(time, image))
+
+    def reset(self):
+        self.ctx.check(self.ctx.L.lmono_tracker_reset(self.ctx.h, self.h))
+
+    def n_levels(self):
+        return self.ctx.L.lmono_tracker_pyramid(self.ctx.h, self.h, 0, None, None, None, None, None)
+
+    def pyramid(self, level):
+        """-> (image u8, dx i16, dy i16) of one level of the last frame's pyramid."""
+        w, h = C.c_int(0), C.c_int(0)
+        n = self.ctx.L.lmono_tracker_pyramid(self.ctx.h, self.h, int(level), None, None, None, C.addressof(w), C.addressof(h))
+        self.ctx.check(min(n, 0))
+        if level >= n:
+            raise LmonoError("the pyramid has %d levels" % n)
+        img = np.zeros((h.value, w.value), np.uint8); dx = np.zeros((h.value, w.value), np.int16); dy = np.zeros_like(dx)
+        self.ctx.check(min(self.ctx.L.lmono_tracker_pyramid(self.ctx.h, self.h, int(level), img.ctypes.data, dx.ctypes.data, dy.ctypes.data, None, None), 0))
+        return img, dx, dy
+
+    def response(self):
+        r = np.zeros((self.cam.height, self.cam.width), np.float32)
+        self.ctx.check(self.ctx.L.lmono_tracker_response(self.ctx.h, self.h, r.ctypes.data))
+        return r
+
+    def lk(self, pts):
+        """Forward and backward LK between the last two frames on given points -> (fwd [n, 2], rev [n, 2], status [n, 2])."""
+        pts = np.ascontiguousarray(pts, np.float32).reshape(-1, 2)
+        n = len(pts)
+        fwd = np.zeros((n, 2), np.float32); rev = np.zeros((n, 2), np.float32); st = np.zeros((n, 2), np.uint8)
+        self.ctx.check(self.ctx.L.lmono_tracker_lk(self.ctx.h, self.h, n, pts.ctypes.data, fwd.ctypes.data, rev.ctypes.data, st.ctypes.data))
+        return fwd, rev, st
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.ctx.L.lmono_tracker_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class FeatureTrackerBatch:
+    """N independent FeatureTrackers advanced by one frame per call, every phase one launch (lmono_tracker_track_batch).
+    Images are device pointers (e.g. torch tensors' data_ptr()) of [height][width] or [height][width][3] uint8.
+    max_cnt: one value, or one per stream."""
+
+    def __init__(self, ctx, cameras, max_cnt=150, min_dist=30):
+        self.ctx = ctx
+        cnts = [int(max_cnt)] * len(cameras) if np.isscalar(max_cnt) else [int(v) for v in max_cnt]
+        self.trackers = [FeatureTracker(ctx, cam, cnts[s], min_dist) for s, cam in enumerate(cameras)]
+        n = len(self.trackers)
+        self._handles = (C.c_void_p * n)(*[t.h for t in self.trackers])
+        self._rec = np.zeros((n, TRACK_MAX_POINTS), TRACK_RECORD)
+        self._recp = (C.c_void_p * n)(*[self._rec[s].ctypes.data for s in range(n)])
+        self._caps = np.full(n, TRACK_MAX_POINTS, np.int32)
+
+    def track(self, times, image_ptrs, bgr=False):
+        n = len(self.trackers)
+        t = np.ascontiguousarray(times, np.float64).reshape(n)
+        ip = (C.c_void_p * n)(*[int(p) for p in image_ptrs])
+        cnt = np.zeros(n, np.int32)
+        self.ctx.check(self.ctx.L.lmono_tracker_track_batch(self.ctx.h, n, self._handles, t.ctypes.data, ip, 1 if bgr else 0, self._recp,
+                                                            self._caps.ctypes.data, cnt.ctypes.data))
+        return [self._rec[s, :cnt[s]].copy() for s in range(n)]
+
+    def reset(self):
+        for t in self.trackers:
+            t.reset()
+
+    def close(self):
+        for t in self.trackers:
+            t.close()
 
 
 class PoseGraph:

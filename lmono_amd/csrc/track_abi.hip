@@ -1,0 +1,246 @@
+// track_abi.hip -- C ABI of the image feature tracker (included by lmono_hip.hip after lmono_ctx is defined)
+#pragma once
+#include "track.hip"
+
+struct lmono_tracker {
+    lmono_ctx *ctx = nullptr;
+    TrkJob job{};                        // the stream's device pointers and constants; per-frame fields are filled per call
+    TrkPyr pyr[2]{};
+    int cur = 0;                         // pyr[cur] holds the last frame
+    int frames = 0;
+    double prev_time = 0.0;
+    bool stale = false;                  // a frame failed half way: the device counters are not trustworthy until lmono_tracker_reset
+    float2 *lk_pts = nullptr;            // staging of the diagnostic LK call
+    unsigned char *image = nullptr;      // staging of the host-buffer entry ([h][w][3])
+    std::vector<void *> allocs;
+    // job table + counts of a batch led by this tracker
+    TrkJob *jobs = nullptr;
+    int *counts = nullptr;
+    int jobs_cap = 0;
+};
+
+template <typename T> static bool trk_alloc(lmono_tracker *t, T *&p, size_t n)
+{
+    void *q = nullptr;
+    if (hipMalloc(&q, (n ? n : 1) * sizeof(T)) != hipSuccess) return false;
+    t->allocs.push_back(q);
+    p = (T *)q;
+    return true;
+}
+
+extern "C" void lmono_tracker_destroy(lmono_tracker *t)
+{
+    if (!t) return;
+    for (void *p : t->allocs) (void)hipFree(p);
+    delete t;
+}
+
+extern "C" int lmono_tracker_reset(lmono_ctx *c, lmono_tracker *t)
+{
+    if (!c || !t || t->ctx != c) return LMONO_EINVAL;
+    HIP_TRY(c, hipMemsetAsync(t->job.st, 0, sizeof(TrkState), c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    t->frames = 0; t->prev_time = 0.0; t->stale = false;
+    return LMONO_OK;
+}
+
+extern "C" lmono_tracker *lmono_tracker_create(lmono_ctx *c, const lmono_camera *cam, int max_cnt, int min_dist, int flags)
+{
+    if (!c) return nullptr;
+    if (!cam || cam->width <= kTrkWin || cam->height <= kTrkWin || cam->width > 8192 || cam->height > 8192 || max_cnt < 1 || max_cnt > kTrkMaxPts ||
+        min_dist < 1 || min_dist > kTrkMaxRadius || flags != 0 || !(cam->fx != 0.0) || !(cam->fy != 0.0)) {
+        c->err = (flags & LMONO_TRACK_REJECT_F) ? "lmono_tracker_create: rejectWithF is not implemented (use_rejectF must be 0)"
+                                                : "lmono_tracker_create: bad camera / limits (image sides 22..8192, 1 <= max_cnt <= 512, 1 <= min_dist <= 128, flags 0)";
+        return nullptr;
+    }
+    if (hipSetDevice(c->device) != hipSuccess) { c->err = "hipSetDevice failed"; return nullptr; }
+    lmono_tracker *t = new lmono_tracker();
+    t->ctx = c;
+    TrkJob &j = t->job;
+    j.w = cam->width; j.h = cam->height; j.max_cnt = max_cnt; j.min_dist = min_dist; j.lk_n = -1;
+    ColourCam &k = j.cam;
+    k.w = cam->width; k.h = cam->height;
+    k.fx = cam->fx; k.fy = cam->fy; k.cx = cam->cx; k.cy = cam->cy; k.k1 = cam->k1; k.k2 = cam->k2; k.p1 = cam->p1; k.p2 = cam->p2;
+    k.ik11 = 1.0 / k.fx; k.ik13 = -k.cx / k.fx; k.ik22 = 1.0 / k.fy; k.ik23 = -k.cy / k.fy;
+    k.distort = !(k.k1 == 0.0 && k.k2 == 0.0 && k.p1 == 0.0 && k.p2 == 0.0);
+    {   // rows of cv::circle(mask, pt, MIN_DIST, 0, -1): the filled midpoint circle of OpenCV's drawing.cpp
+        int err = 0, dx = min_dist, dy = 0, plus = 1, minus = 2 * min_dist - 1;
+        for (int i = 0; i <= kTrkMaxRadius; i++) j.hw[i] = 0;
+        while (dx >= dy) {
+            j.hw[dy] = std::max(j.hw[dy], dx);
+            j.hw[dx] = std::max(j.hw[dx], dy);
+            dy++; err += plus; plus += 2;
+            if (err > 0) { err -= minus; dx--; minus -= 2; }
+        }
+    }
+    // cv::buildOpticalFlowPyramid: a level exists while both of its sides exceed the window
+    int lw[kTrkLevels], lh[kTrkLevels];
+    lw[0] = j.w; lh[0] = j.h; j.n_levels = 1;
+    while (j.n_levels < kTrkLevels) {
+        const int w2 = (lw[j.n_levels - 1] + 1) / 2, h2 = (lh[j.n_levels - 1] + 1) / 2;
+        if (w2 <= kTrkWin || h2 <= kTrkWin) break;
+        lw[j.n_levels] = w2; lh[j.n_levels] = h2; j.n_levels++;
+    }
+    const size_t np = (size_t)j.w * j.h;
+    bool ok = true;
+    for (int b = 0; b < 2 && ok; b++)
+        for (int l = 0; l < j.n_levels && ok; l++) {
+            TrkLevel &L = t->pyr[b].lv[l];
+            L.w = lw[l]; L.h = lh[l];
+            ok = trk_alloc(t, L.img, (size_t)L.w * L.h) && trk_alloc(t, L.dx, (size_t)L.w * L.h) && trk_alloc(t, L.dy, (size_t)L.w * L.h);
+        }
+    ok = ok && trk_alloc(t, j.st, 1) && trk_alloc(t, j.pts, kTrkMaxPts) && trk_alloc(t, j.un, kTrkMaxPts) && trk_alloc(t, j.ids, kTrkMaxPts) && trk_alloc(t, j.cnt, kTrkMaxPts) &&
+         trk_alloc(t, j.cur_pts, kTrkMaxPts) && trk_alloc(t, j.rev_pts, kTrkMaxPts) && trk_alloc(t, j.st_f, kTrkMaxPts) && trk_alloc(t, j.st_b, kTrkMaxPts) &&
+         trk_alloc(t, j.kept_pix, kTrkMaxPts) && trk_alloc(t, j.resp, np) && trk_alloc(t, j.cand, np) && trk_alloc(t, j.new_pts, kTrkMaxPts) &&
+         trk_alloc(t, j.rec, kTrkMaxPts) && trk_alloc(t, t->lk_pts, kTrkMaxPts) && trk_alloc(t, t->image, np * 3);
+    ok = ok && hipMemset(j.st, 0, sizeof(TrkState)) == hipSuccess && hipMemset(j.resp, 0, np * sizeof(float)) == hipSuccess;
+    if (!ok) { c->err = "lmono_tracker_create: device allocation failed"; lmono_tracker_destroy(t); return nullptr; }
+    return t;
+}
+
+static int trk_job_table(lmono_ctx *c, lmono_tracker *lead, int n_streams, const char *who)
+{
+    if (lead->jobs_cap >= n_streams) return LMONO_OK;
+    int cap = std::max(lead->jobs_cap, 1);
+    while (cap < n_streams) cap <<= 1;
+    TrkJob *jb = nullptr; int *cn = nullptr;
+    if (!trk_alloc(lead, jb, (size_t)cap) || !trk_alloc(lead, cn, (size_t)cap)) { c->err = std::string(who) + ": job table allocation failed"; return LMONO_ENOMEM; }
+    for (void *old : { (void *)lead->jobs, (void *)lead->counts }) {      // the outgrown table (no launch that reads it is in flight: every call ends synchronised)
+        if (!old) continue;
+        (void)hipFree(old);
+        lead->allocs.erase(std::find(lead->allocs.begin(), lead->allocs.end(), old));
+    }
+    lead->jobs = jb; lead->counts = cn; lead->jobs_cap = cap;
+    return LMONO_OK;
+}
+
+static inline unsigned trk_blocks(size_t n) { return (unsigned)std::min<size_t>((n + kTrkT - 1) / kTrkT, 4096); }
+
+extern "C" int lmono_tracker_track_batch(lmono_ctx *c, int n_streams, lmono_tracker *const *trks, const double *times, const uint8_t *const *image_d, int format,
+                                         lmono_track_record *const *records_out, const int *caps, int *n_out)
+{
+    if (!c || n_streams <= 0 || !trks || !times || !image_d || !n_out || (format != LMONO_TRACK_GREY8 && format != LMONO_TRACK_BGR8)) return LMONO_EINVAL;
+    for (int s = 0; s < n_streams; s++) {
+        if (!trks[s] || trks[s]->ctx != c || !image_d[s]) { c->err = "lmono_tracker_track_batch: bad stream arguments"; return LMONO_EINVAL; }
+        if (trks[s]->stale) { c->err = "lmono_tracker_track_batch: an earlier frame of this tracker failed half way; call lmono_tracker_reset"; return LMONO_EINVAL; }
+        for (int u = 0; u < s; u++) if (trks[u] == trks[s]) { c->err = "lmono_tracker_track_batch: trackers must be distinct"; return LMONO_EINVAL; }
+        if (records_out && records_out[s] && (!caps || caps[s] < trks[s]->job.max_cnt)) { c->err = "lmono_tracker_track_batch: record capacity below max_cnt"; return LMONO_ECAPACITY; }
+    }
+    lmono_tracker *lead = trks[0];
+    if (int rc = trk_job_table(c, lead, n_streams, "lmono_tracker_track_batch")) return rc;
+    std::vector<TrkJob> jobs((size_t)n_streams);
+    size_t max_np = 0; int max_levels = 1, max_cnt = 1, max_tiles = 1;
+    for (int s = 0; s < n_streams; s++) {
+        lmono_tracker *t = trks[s];
+        TrkJob &j = jobs[(size_t)s];
+        j = t->job;
+        j.cur = t->pyr[t->cur ^ 1]; j.prev = t->pyr[t->cur];   // prev_img = cur_img (:359) by pointer swap, committed when the frame has succeeded
+        j.src = image_d[s]; j.format = format; j.lk_n = -1;
+        j.dt = times[s] - t->prev_time;
+        j.n_out = lead->counts + s;
+        max_np = std::max(max_np, (size_t)j.w * j.h);
+        max_levels = std::max(max_levels, j.n_levels); max_cnt = std::max(max_cnt, j.max_cnt);
+        max_tiles = std::max(max_tiles, ((j.w + kTrkTW - 1) / kTrkTW) * ((j.h + kTrkTH - 1) / kTrkTH));
+    }
+    const unsigned ns = (unsigned)n_streams;
+    for (int s = 0; s < n_streams; s++) trks[s]->stale = true;     // until the last step below has succeeded
+    HIP_TRY(c, hipMemcpyAsync(lead->jobs, jobs.data(), sizeof(TrkJob) * (size_t)n_streams, hipMemcpyHostToDevice, c->stream));
+    k_trk_grey<<<dim3(trk_blocks(max_np), ns), kTrkT, 0, c->stream>>>(lead->jobs);
+    if (int rc = check_launch(c, "k_trk_grey")) return rc;
+    for (int l = 1; l < max_levels; l++) {
+        k_trk_pyrdown<<<dim3(trk_blocks(max_np >> (2 * l - 1)), ns), kTrkT, 0, c->stream>>>(lead->jobs, l);
+        if (int rc = check_launch(c, "k_trk_pyrdown")) return rc;
+    }
+    for (int l = 0; l < max_levels; l++) {
+        k_trk_scharr<<<dim3(trk_blocks(l ? max_np >> (2 * l - 1) : max_np), ns), kTrkT, 0, c->stream>>>(lead->jobs, l);
+        if (int rc = check_launch(c, "k_trk_scharr")) return rc;
+    }
+    const unsigned lk_blocks = (unsigned)((max_cnt + kTrkT / kWave - 1) / (kTrkT / kWave));
+    k_trk_lk<<<dim3(lk_blocks, ns), kTrkT, 0, c->stream>>>(lead->jobs, 0);
+    if (int rc = check_launch(c, "k_trk_lk")) return rc;
+    k_trk_lk<<<dim3(lk_blocks, ns), kTrkT, 0, c->stream>>>(lead->jobs, 1);
+    if (int rc = check_launch(c, "k_trk_lk")) return rc;
+    k_trk_update<<<ns, kTrkMaxPts, 0, c->stream>>>(lead->jobs);
+    if (int rc = check_launch(c, "k_trk_update")) return rc;
+    k_trk_response<<<dim3((unsigned)max_tiles, ns), kTrkT, 0, c->stream>>>(lead->jobs);
+    if (int rc = check_launch(c, "k_trk_response")) return rc;
+    k_trk_nms<<<dim3(trk_blocks(max_np), ns), kTrkT, 0, c->stream>>>(lead->jobs);
+    if (int rc = check_launch(c, "k_trk_nms")) return rc;
+    k_trk_select<<<ns, kTrkT, 0, c->stream>>>(lead->jobs);
+    if (int rc = check_launch(c, "k_trk_select")) return rc;
+    k_trk_finish<<<ns, kTrkMaxPts, 0, c->stream>>>(lead->jobs);
+    if (int rc = check_launch(c, "k_trk_finish")) return rc;
+    HIP_TRY(c, hipMemcpyAsync(n_out, lead->counts, sizeof(int) * (size_t)n_streams, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    for (int s = 0; s < n_streams; s++) {
+        lmono_tracker *t = trks[s];
+        t->frames++; t->prev_time = times[s];
+        if (records_out && records_out[s] && n_out[s] > 0)
+            HIP_TRY(c, hipMemcpyAsync(records_out[s], t->job.rec, sizeof(lmono_track_record) * (size_t)n_out[s], hipMemcpyDeviceToHost, c->stream));
+    }
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    for (int s = 0; s < n_streams; s++) { trks[s]->cur ^= 1; trks[s]->stale = false; }
+    return LMONO_OK;
+}
+
+extern "C" int lmono_tracker_track(lmono_ctx *c, lmono_tracker *t, double time, const uint8_t *image_h, int format, lmono_track_record *records_out, int cap, int *n_out)
+{
+    if (!c || !t || t->ctx != c || !image_h || !n_out || (format != LMONO_TRACK_GREY8 && format != LMONO_TRACK_BGR8)) return LMONO_EINVAL;
+    HIP_TRY(c, hipMemcpyAsync(t->image, image_h, (size_t)t->job.w * t->job.h * (format == LMONO_TRACK_BGR8 ? 3 : 1), hipMemcpyHostToDevice, c->stream));
+    const uint8_t *img = t->image;
+    return lmono_tracker_track_batch(c, 1, &t, &time, &img, format, &records_out, &cap, n_out);
+}
+
+extern "C" int lmono_tracker_pyramid(lmono_ctx *c, lmono_tracker *t, int level, uint8_t *image_h, int16_t *dx_h, int16_t *dy_h, int *width, int *height)
+{
+    if (!c || !t || t->ctx != c || level < 0) return LMONO_EINVAL;
+    if (level >= t->job.n_levels) {
+        if (width) *width = 0;
+        if (height) *height = 0;
+        return t->job.n_levels;
+    }
+    if (t->frames == 0 && (image_h || dx_h || dy_h)) { c->err = "lmono_tracker_pyramid: no frame tracked yet"; return LMONO_EINVAL; }
+    const TrkLevel &L = t->pyr[t->cur].lv[level];
+    const size_t np = (size_t)L.w * L.h;
+    if (width) *width = L.w;
+    if (height) *height = L.h;
+    if (image_h) HIP_TRY(c, hipMemcpyAsync(image_h, L.img, np, hipMemcpyDeviceToHost, c->stream));
+    if (dx_h) HIP_TRY(c, hipMemcpyAsync(dx_h, L.dx, np * sizeof(short), hipMemcpyDeviceToHost, c->stream));
+    if (dy_h) HIP_TRY(c, hipMemcpyAsync(dy_h, L.dy, np * sizeof(short), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return t->job.n_levels;
+}
+
+extern "C" int lmono_tracker_response(lmono_ctx *c, lmono_tracker *t, float *response_h)
+{
+    if (!c || !t || t->ctx != c || !response_h) return LMONO_EINVAL;
+    HIP_TRY(c, hipMemcpyAsync(response_h, t->job.resp, sizeof(float) * (size_t)t->job.w * t->job.h, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return LMONO_OK;
+}
+
+extern "C" int lmono_tracker_lk(lmono_ctx *c, lmono_tracker *t, int n, const float *pts_h, float *fwd_h, float *rev_h, uint8_t *status_h)
+{
+    if (!c || !t || t->ctx != c || n < 0 || n > kTrkMaxPts || !pts_h || !fwd_h || !rev_h || !status_h) return LMONO_EINVAL;
+    if (t->frames < 2) { c->err = "lmono_tracker_lk: needs two tracked frames"; return LMONO_EINVAL; }
+    if (n == 0) return LMONO_OK;
+    if (int rc = trk_job_table(c, t, 1, "lmono_tracker_lk")) return rc;
+    TrkJob j = t->job;
+    j.cur = t->pyr[t->cur]; j.prev = t->pyr[t->cur ^ 1];
+    j.lk_n = n; j.lk_pts = t->lk_pts;
+    HIP_TRY(c, hipMemcpyAsync(t->lk_pts, pts_h, sizeof(float2) * (size_t)n, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(t->jobs, &j, sizeof(TrkJob), hipMemcpyHostToDevice, c->stream));
+    const unsigned lk_blocks = (unsigned)((n + kTrkT / kWave - 1) / (kTrkT / kWave));
+    k_trk_lk<<<dim3(lk_blocks, 1), kTrkT, 0, c->stream>>>(t->jobs, 0);
+    if (int rc = check_launch(c, "k_trk_lk")) return rc;
+    k_trk_lk<<<dim3(lk_blocks, 1), kTrkT, 0, c->stream>>>(t->jobs, 1);
+    if (int rc = check_launch(c, "k_trk_lk")) return rc;
+    std::vector<unsigned char> sf((size_t)n), sb((size_t)n);
+    HIP_TRY(c, hipMemcpyAsync(fwd_h, j.cur_pts, sizeof(float2) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(rev_h, j.rev_pts, sizeof(float2) * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(sf.data(), j.st_f, (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(sb.data(), j.st_b, (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    for (int i = 0; i < n; i++) { status_h[2 * i] = sf[(size_t)i]; status_h[2 * i + 1] = sb[(size_t)i]; }
+    return LMONO_OK;
+}

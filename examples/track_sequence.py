@@ -2,6 +2,7 @@
 
   python examples/track_sequence.py --synthetic 20 --out tracks/                 # workloads/s5 frames with known flow
   python examples/track_sequence.py --sequence /data/kitti/05 --out tracks/      # <sequence>/image_0/%06d.png (+ times.txt)
+  ... --reject-f 1.0 0.5                                                         # use_rejectF: 1 with F_THRESHOLD, F_DIS of the config
   ... --estimator                                                                # every frame's tracks go into Estimator::processImage
 
 Per frame one text file <out>/%06d.txt: "id x_n y_n u v vx vy track_cnt" per feature (FeatureTracker.cc:372-397).  With
@@ -72,6 +73,7 @@ def main():
     ap.add_argument("--camera", help="fx,fy,cx,cy[,k1,k2,p1,p2] of the PINHOLE cam yaml")
     ap.add_argument("--max-cnt", type=int, default=150)
     ap.add_argument("--min-dist", type=int, default=30)
+    ap.add_argument("--reject-f", type=float, nargs=2, metavar=("THR", "DIS"), help="rejectWithF with F_THRESHOLD, F_DIS (use_rejectF: 1)")
     ap.add_argument("--estimator", action="store_true", help="feed every frame into Estimator::processImage (lmono_amd/host/estimator_seq)")
     a = ap.parse_args()
     if not a.synthetic and not a.sequence:
@@ -84,9 +86,15 @@ def main():
     os.makedirs(a.out, exist_ok=True)
     ctx = lmono_amd.Context(0)
     tracker = lmono_amd.FeatureTracker(ctx, lmono_amd.Camera(*cam, 5, 0, 0), a.max_cnt, min(a.min_dist, 15) if a.synthetic else a.min_dist)
+    if a.reject_f:
+        tracker.set_reject_f(a.reject_f[0], a.reject_f[1])
     records = []
     for k, (t, img) in enumerate(zip(times, frames)):
         rec = tracker.track(t, img)
+        if a.reject_f:
+            st, _ = tracker.reject_stats()
+            if st[0] >= 0:
+                print("frame %d: rejectWithF: %d valid hypotheses, best %d, %d gate-1 inliers, %d kept after gate 2" % (k, st[0], st[1], st[2], st[3]))
         records.append(rec)
         with open(os.path.join(a.out, "%06d.txt" % k), "w") as f:
             for r in rec:

@@ -404,7 +404,7 @@ int64_t lmono_map_builder_map(lmono_ctx *, lmono_map_builder *, lmono_point_rgb 
 int lmono_map_builder_clear(lmono_ctx *, lmono_map_builder *);                         /* rgb_map->clear()                    */
 
 /* ---- image feature tracker ---------------------------------------------------------------------------------
- * Replaces FeatureTracker::trackImage of the mono path with use_rejectF = 0 (mono_lidar_mapping/src/image_process/
+ * Replaces FeatureTracker::trackImage of the mono path, use_rejectF = 0 or 1 (lmono_tracker_set_reject_f) (mono_lidar_mapping/src/image_process/
  * FeatureTracker.cc:189-433): BGR2GRAY (:193), forward / backward pyramidal LK with the 0.5 px round-trip and inBorder tests
  * (:213-249), track_cnt++ (:251), setMask (:55-84, ties in track count kept in current order), goodFeaturesToTrack under the
  * mask (:281-297), undistortedPts through the PINHOLE liftProjective (:172-187) and ptsVelocity (:94-133).  The pyramid of a
@@ -414,7 +414,7 @@ int lmono_map_builder_clear(lmono_ctx *, lmono_map_builder *);                  
 #define LMONO_TRACK_MAX_POINTS 512   /* largest max_cnt                                       */
 #define LMONO_TRACK_GREY8      0     /* image: [height][width] uint8                          */
 #define LMONO_TRACK_BGR8       1     /* image: [height][width][3] uint8 (cv::Mat BGR8)        */
-#define LMONO_TRACK_REJECT_F   1     /* flags bit: use_rejectF -- refused                     */
+#define LMONO_TRACK_REJECT_F   1     /* flags bit: refused -- use lmono_tracker_set_reject_f  */
 /* one feature of the frame (:372-397): id, normalised x y (z = 1), pixel u v, velocity of the normalised point, track count;
  * id / x_n / y_n / u / v / vx / vy are FeatureManager::Image's (feature_id, xyz_uv_velocity) with camera_id 0 */
 typedef struct { int32_t id; float x_n, y_n, u, v, vx, vy; int32_t track_cnt; } lmono_track_record;
@@ -438,6 +438,18 @@ int lmono_tracker_response(lmono_ctx *, lmono_tracker *, float *response_h);
 /* the two cv::calcOpticalFlowPyrLK calls of :218 / :223 between the last two frames on n <= 512 given points: pts_h [n][2] ->
  * fwd_h [n][2], rev_h [n][2], status_h [n][2] (forward, backward; backward is 0 where forward failed).  Leaves the tracks alone. */
 int lmono_tracker_lk(lmono_ctx *, lmono_tracker *, int n, const float *pts_h, float *fwd_h, float *rev_h, uint8_t *status_h);
+/* rejectWithF (:259-262, :435-503): after the forward-backward test, n_hyp 8-point hypotheses from a
+ * counter-based sample stream keyed by (seed, frames since the last reset, hypothesis, draw) are scored in fp64 against
+ * f_threshold (F_THRESHOLD, gate 1); F is refitted over the winner's inliers, and an inlier whose symmetric distance
+ * r^2 / (|l|^2 + |l'|^2) exceeds f_dis (F_DIS, :467-499) is dropped too (gate 2).  Our own definition: parity with OpenCV's
+ * RANSAC is unpinned.  Fewer than 8 survivors: the step does not run; no valid hypothesis or fewer than 8 inliers: all dropped. */
+typedef struct { double f_threshold, f_dis, focal_length; int32_t n_hyp; uint32_t seed; } lmono_reject_f;   /* focal_length 0 -> 460, n_hyp 0 -> 256 */
+int lmono_tracker_set_reject_f(lmono_ctx *, lmono_tracker *, const lmono_reject_f *);   /* NULL: off; takes effect with the next frame */
+/* last frame: stats[4] = valid hypotheses, best hypothesis, gate-1 inliers, kept after gate 2 (all -1: step did not run); F [9] row-major */
+int lmono_tracker_reject_stats(lmono_ctx *, lmono_tracker *, int32_t *stats, double *F);
+/* diagnostic, like lmono_tracker_lk: the step on n (8..512) given pixel pairs with the tracker's camera and parameters; leaves the tracks alone */
+int lmono_tracker_reject_f(lmono_ctx *, lmono_tracker *, int n, const float *prev_px_h, const float *cur_px_h, uint32_t frame_key,
+                           uint8_t *status_h, int32_t *stats, double *F);
 
 /* ---- loop-closure pose graph -- NEW FEATURE, no counterpart in the reference --------------------------
  * The reference detects loops and publishes loop_info = relative_t, relative_q (w x y z), relative_yaw

@@ -17,7 +17,7 @@ SYMBOLS = [
     "lmono_map_builder_create", "lmono_map_builder_destroy", "lmono_associate_to_map", "lmono_associate_to_map_batch", "lmono_map_builder_depth",
     "lmono_map_builder_cloud", "lmono_map_builder_map", "lmono_map_builder_clear",
     "lmono_tracker_create", "lmono_tracker_destroy", "lmono_tracker_reset", "lmono_tracker_track", "lmono_tracker_track_batch", "lmono_tracker_pyramid",
-    "lmono_tracker_response", "lmono_tracker_lk",
+    "lmono_tracker_response", "lmono_tracker_lk", "lmono_tracker_set_reject_f", "lmono_tracker_reject_stats", "lmono_tracker_reject_f",
     "lmono_pose_graph_create", "lmono_pose_graph_destroy", "lmono_pose_graph_reset", "lmono_pose_graph_info", "lmono_pose_graph_reduce_buffer", "lmono_pose_graph_set_reduce_buffer", "lmono_pose_graph_linearise",
     "lmono_pose_graph_step", "lmono_pose_graph_optimize", "lmono_pose_graph_result", "lmono_factor_eval", "lmono_factor_eval_d", "lmono_factor_eval_blocks", "lmono_factor_eval_blocks_d",
     "lmono_triangulate", "lmono_outlier_scores", "lmono_shift_depth", "lmono_shift_depth_batch", "lmono_marginalize", "lmono_marg_evaluate", "lmono_marg_second_new", "lmono_ba_batch_create", "lmono_ba_batch_update", "lmono_ba_batch_destroy", "lmono_ba_solve", "lmono_ba_batch_reset", "lmono_ba_batch_read", "lmono_debug_bounds",
@@ -797,6 +797,14 @@ def _tracker_prototypes(L):
     L.lmono_tracker_pyramid.argtypes = [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 5
     L.lmono_tracker_response.argtypes = [C.c_void_p] * 3
     L.lmono_tracker_lk.argtypes = [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 4
+    L.lmono_tracker_set_reject_f.argtypes = [C.c_void_p] * 3
+    L.lmono_tracker_reject_stats.argtypes = [C.c_void_p] * 4
+    L.lmono_tracker_reject_f.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+
+
+class RejectF(C.Structure):
+    """lmono_reject_f: the parameters of rejectWithF (F_THRESHOLD, F_DIS, FOCAL_LENGTH; hypothesis count and sample seed)."""
+    _fields_ = [("f_threshold", C.c_double), ("f_dis", C.c_double), ("focal_length", C.c_double), ("n_hyp", C.c_int32), ("seed", C.c_uint32)]
 
 
 def feature_frame(records):
@@ -866,6 +874,33 @@ class FeatureTracker:
         self.ctx.check(self.ctx.L.lmono_tracker_lk(self.ctx.h, self.h, n, pts.ctypes.data, fwd.ctypes.data, rev.ctypes.data, st.ctypes.data))
         return fwd, rev, st
 
+    def set_reject_f(self, f_threshold, f_dis=None, focal_length=460.0, n_hyp=256, seed=0):
+        """Switch rejectWithF on from the next frame (use_rejectF: 1, F_THRESHOLD, F_DIS); set_reject_f(None) switches it off."""
+        if f_threshold is None:
+            self.ctx.check(self.ctx.L.lmono_tracker_set_reject_f(self.ctx.h, self.h, None))
+            return
+        if f_dis is None:
+            raise LmonoError("set_reject_f needs f_threshold and f_dis")
+        prm = RejectF(float(f_threshold), float(f_dis), float(focal_length), int(n_hyp), int(seed) & 0xFFFFFFFF)
+        self.ctx.check(self.ctx.L.lmono_tracker_set_reject_f(self.ctx.h, self.h, C.byref(prm)))
+
+    def reject_stats(self):
+        """-> (stats [4] int32: valid hypotheses, best hypothesis, gate-1 inliers, kept after gate 2; all -1 when the step did
+        not run, F [9] fp64 row-major) of the last frame."""
+        stats = np.zeros(4, np.int32); F = np.zeros(9, np.float64)
+        self.ctx.check(self.ctx.L.lmono_tracker_reject_stats(self.ctx.h, self.h, stats.ctypes.data, F.ctypes.data))
+        return stats, F
+
+    def reject_f(self, prev_px, cur_px, frame_key=0):
+        """The rejection step alone on 8..512 given pixel pairs -> (status [n] uint8, stats [4], F [9]); leaves the tracks alone."""
+        a = np.ascontiguousarray(prev_px, np.float32).reshape(-1, 2); b = np.ascontiguousarray(cur_px, np.float32).reshape(-1, 2)
+        if len(a) != len(b):
+            raise LmonoError("prev_px and cur_px differ in length")
+        st = np.zeros(max(len(a), 1), np.uint8); stats = np.zeros(4, np.int32); F = np.zeros(9, np.float64)
+        self.ctx.check(self.ctx.L.lmono_tracker_reject_f(self.ctx.h, self.h, len(a), a.ctypes.data, b.ctypes.data, int(frame_key) & 0xFFFFFFFF,
+                                                         st.ctypes.data, stats.ctypes.data, F.ctypes.data))
+        return st[:len(a)], stats, F
+
     def close(self):
         if getattr(self, "h", None):
             self.ctx.L.lmono_tracker_destroy(self.h)
@@ -881,12 +916,15 @@ class FeatureTracker:
 class FeatureTrackerBatch:
     """N independent FeatureTrackers advanced by one frame per call, every phase one launch (lmono_tracker_track_batch).
     Images are device pointers (e.g. torch tensors' data_ptr()) of [height][width] or [height][width][3] uint8.
-    max_cnt: one value, or one per stream."""
+    max_cnt: one value, or one per stream.  reject_f: None, one dict of set_reject_f arguments for every stream, or a list
+    with one dict or None per stream (streams with and without rejection share a batch)."""
 
-    def __init__(self, ctx, cameras, max_cnt=150, min_dist=30):
+    def __init__(self, ctx, cameras, max_cnt=150, min_dist=30, reject_f=None):
         self.ctx = ctx
         cnts = [int(max_cnt)] * len(cameras) if np.isscalar(max_cnt) else [int(v) for v in max_cnt]
         self.trackers = [FeatureTracker(ctx, cam, cnts[s], min_dist) for s, cam in enumerate(cameras)]
+        if reject_f is not None:
+            self.set_reject_f(reject_f)
         n = len(self.trackers)
         self._handles = (C.c_void_p * n)(*[t.h for t in self.trackers])
         self._rec = np.zeros((n, TRACK_MAX_POINTS), TRACK_RECORD)
@@ -901,6 +939,19 @@ class FeatureTrackerBatch:
         self.ctx.check(self.ctx.L.lmono_tracker_track_batch(self.ctx.h, n, self._handles, t.ctypes.data, ip, 1 if bgr else 0, self._recp,
                                                             self._caps.ctypes.data, cnt.ctypes.data))
         return [self._rec[s, :cnt[s]].copy() for s in range(n)]
+
+    def set_reject_f(self, reject_f):
+        per = [reject_f] * len(self.trackers) if reject_f is None or isinstance(reject_f, dict) else list(reject_f)
+        if len(per) != len(self.trackers):
+            raise LmonoError("reject_f needs one entry per stream")
+        for t, prm in zip(self.trackers, per):
+            if prm is None:
+                t.set_reject_f(None)
+            else:
+                t.set_reject_f(**prm)
+
+    def reject_stats(self):
+        return [t.reject_stats() for t in self.trackers]
 
     def reset(self):
         for t in self.trackers:

@@ -9,6 +9,7 @@
 //   k_trk_lk        cv::calcOpticalFlowPyrLK (:218, :223), one wave per (stream, point): the 441 patch pixels live 7 per
 //                   lane in registers for all iterations, integer products, integer wave sums, the 2 x 2 solve in fp64 in
 //                   every lane; levels and iterations loop inside the kernel
+//   k_trk_reject    rejectWithF (:259-262, :435-503; track_reject.hip), only when a stream of the batch has it switched on
 //   k_trk_update    forward-backward / inBorder test (:226-243), compaction (:245-248), track_cnt++ (:251), setMask
 //                   (:55-84, stable order), one workgroup per stream
 //   k_trk_response  cv::cornerMinEigenVal (block 3, Sobel 3) on an LDS tile with halo + the maximum over unmasked pixels
@@ -61,6 +62,14 @@ struct TrkJob {
     lmono_track_record *rec;
     int *n_out;
     int hw[kTrkMaxRadius + 1];         // cv::circle(.., MIN_DIST, .., -1): half width of row |dy|
+    // rejectWithF (track_reject.hip); rej_st == nullptr: off
+    unsigned char *rej_st;             // one status byte per point slot
+    int *rej_stats;                    // valid hypotheses, best hypothesis, gate-1 inliers, kept after gate 2
+    double *rej_F;                     // [9] row-major
+    double rej_thr2, rej_dis, rej_focal;
+    int rej_nhyp, rej_n;               // rej_n >= 0: diagnostic call on rej_n given pairs
+    unsigned int rej_seed, rej_key;    // rej_key: frames tracked since the last reset
+    const float2 *rej_prev, *rej_cur;
 };
 
 __device__ __forceinline__ int trk_reflect(int i, int n)
@@ -246,6 +255,15 @@ __device__ __forceinline__ bool trk_in_circle(const int *hw, int r, int dx, int 
     return dy <= r && dx <= hw[dy];
 }
 
+// status of the forward-backward test and inBorder (:226-243) of point slot i
+__device__ __forceinline__ int trk_keep(const TrkJob &j, int i)
+{
+    const float2 c = j.cur_pts[i], p = j.pts[i], q = j.rev_pts[i];
+    const double dx = (double)(p.x - q.x), dy = (double)(p.y - q.y);
+    const float rx = rintf(c.x), ry = rintf(c.y);
+    return j.st_f[i] && j.st_b[i] && sqrt(dx * dx + dy * dy) <= 0.5 && 1.f <= rx && rx < (float)(j.w - 1) && 1.f <= ry && ry < (float)(j.h - 1);
+}
+
 // one workgroup of kTrkMaxPts threads per stream, thread i owns point slot i
 __global__ __launch_bounds__(kTrkMaxPts) void k_trk_update(const TrkJob *jobs)
 {
@@ -255,16 +273,13 @@ __global__ __launch_bounds__(kTrkMaxPts) void k_trk_update(const TrkJob *jobs)
     const TrkJob &j = jobs[blockIdx.x];
     const int i = threadIdx.x, n = j.st->n, r = j.min_dist;
     for (int k = i; k <= r; k += kTrkMaxPts) s_hw[k] = j.hw[k];
-    // status of the forward-backward test and inBorder (:226-243)
     int keep = 0;
     float2 c = make_float2(0.f, 0.f), un = c;
     int id = 0, cnt = 0;
     if (i < n) {
         c = j.cur_pts[i];
-        const float2 p = j.pts[i], q = j.rev_pts[i];
-        const double dx = (double)(p.x - q.x), dy = (double)(p.y - q.y);
-        const float rx = rintf(c.x), ry = rintf(c.y);
-        keep = j.st_f[i] && j.st_b[i] && sqrt(dx * dx + dy * dy) <= 0.5 && 1.f <= rx && rx < (float)(j.w - 1) && 1.f <= ry && ry < (float)(j.h - 1);
+        keep = trk_keep(j, i);
+        if (j.rej_st) keep = keep && j.rej_st[i];
         id = j.ids[i]; cnt = j.cnt[i] + 1; un = j.un[i];
     }
     s_flag[i] = keep;
@@ -480,3 +495,5 @@ __global__ __launch_bounds__(kTrkMaxPts) void k_trk_finish(const TrkJob *jobs)
 }
 
 } // namespace lmono
+
+#include "track_reject.hip"

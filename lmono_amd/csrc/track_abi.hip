@@ -12,6 +12,15 @@ struct lmono_tracker {
     bool stale = false;                  // a frame failed half way: the device counters are not trustworthy until lmono_tracker_reset
     float2 *lk_pts = nullptr;            // staging of the diagnostic LK call
     unsigned char *image = nullptr;      // staging of the host-buffer entry ([h][w][3])
+    // rejectWithF (lmono_tracker_set_reject_f): parameters, device outputs, the last frame's stats / F on the host
+    bool rej_on = false, rej_ran = false;
+    lmono_reject_f rej{};
+    unsigned char *rej_st = nullptr;
+    int *rej_stats = nullptr;
+    double *rej_F = nullptr;
+    float2 *rej_prev = nullptr, *rej_cur = nullptr;      // staging of the diagnostic call
+    int32_t last_stats[4] = { -1, -1, -1, -1 };
+    double last_F[9] = {};
     std::vector<void *> allocs;
     // job table + counts of a batch led by this tracker
     TrkJob *jobs = nullptr;
@@ -40,7 +49,7 @@ extern "C" int lmono_tracker_reset(lmono_ctx *c, lmono_tracker *t)
     if (!c || !t || t->ctx != c) return LMONO_EINVAL;
     HIP_TRY(c, hipMemsetAsync(t->job.st, 0, sizeof(TrkState), c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    t->frames = 0; t->prev_time = 0.0; t->stale = false;
+    t->frames = 0; t->prev_time = 0.0; t->stale = false; t->rej_ran = false;
     return LMONO_OK;
 }
 
@@ -49,7 +58,7 @@ extern "C" lmono_tracker *lmono_tracker_create(lmono_ctx *c, const lmono_camera 
     if (!c) return nullptr;
     if (!cam || cam->width <= kTrkWin || cam->height <= kTrkWin || cam->width > 8192 || cam->height > 8192 || max_cnt < 1 || max_cnt > kTrkMaxPts ||
         min_dist < 1 || min_dist > kTrkMaxRadius || flags != 0 || !(cam->fx != 0.0) || !(cam->fy != 0.0)) {
-        c->err = (flags & LMONO_TRACK_REJECT_F) ? "lmono_tracker_create: rejectWithF is not implemented (use_rejectF must be 0)"
+        c->err = (flags & LMONO_TRACK_REJECT_F) ? "lmono_tracker_create: rejectWithF is not switched on by flags (flags must be 0): use lmono_tracker_set_reject_f"
                                                 : "lmono_tracker_create: bad camera / limits (image sides 22..8192, 1 <= max_cnt <= 512, 1 <= min_dist <= 128, flags 0)";
         return nullptr;
     }
@@ -92,10 +101,44 @@ extern "C" lmono_tracker *lmono_tracker_create(lmono_ctx *c, const lmono_camera 
     ok = ok && trk_alloc(t, j.st, 1) && trk_alloc(t, j.pts, kTrkMaxPts) && trk_alloc(t, j.un, kTrkMaxPts) && trk_alloc(t, j.ids, kTrkMaxPts) && trk_alloc(t, j.cnt, kTrkMaxPts) &&
          trk_alloc(t, j.cur_pts, kTrkMaxPts) && trk_alloc(t, j.rev_pts, kTrkMaxPts) && trk_alloc(t, j.st_f, kTrkMaxPts) && trk_alloc(t, j.st_b, kTrkMaxPts) &&
          trk_alloc(t, j.kept_pix, kTrkMaxPts) && trk_alloc(t, j.resp, np) && trk_alloc(t, j.cand, np) && trk_alloc(t, j.new_pts, kTrkMaxPts) &&
-         trk_alloc(t, j.rec, kTrkMaxPts) && trk_alloc(t, t->lk_pts, kTrkMaxPts) && trk_alloc(t, t->image, np * 3);
+         trk_alloc(t, j.rec, kTrkMaxPts) && trk_alloc(t, t->lk_pts, kTrkMaxPts) && trk_alloc(t, t->image, np * 3) &&
+         trk_alloc(t, t->rej_st, kTrkMaxPts) && trk_alloc(t, t->rej_stats, 4) && trk_alloc(t, t->rej_F, 9) && trk_alloc(t, t->rej_prev, kTrkMaxPts) && trk_alloc(t, t->rej_cur, kTrkMaxPts);
     ok = ok && hipMemset(j.st, 0, sizeof(TrkState)) == hipSuccess && hipMemset(j.resp, 0, np * sizeof(float)) == hipSuccess;
     if (!ok) { c->err = "lmono_tracker_create: device allocation failed"; lmono_tracker_destroy(t); return nullptr; }
     return t;
+}
+
+// the job's rejectWithF fields from the tracker's parameters; n >= 0: the diagnostic call on n staged pairs
+static void trk_reject_job(const lmono_tracker *t, TrkJob &j, int n, uint32_t frame_key)
+{
+    j.rej_st = t->rej_st; j.rej_stats = t->rej_stats; j.rej_F = t->rej_F;
+    j.rej_thr2 = t->rej.f_threshold * t->rej.f_threshold; j.rej_dis = t->rej.f_dis; j.rej_focal = t->rej.focal_length;
+    j.rej_nhyp = t->rej.n_hyp; j.rej_seed = t->rej.seed; j.rej_key = frame_key; j.rej_n = n;
+    j.rej_prev = t->rej_prev; j.rej_cur = t->rej_cur;
+}
+
+extern "C" int lmono_tracker_set_reject_f(lmono_ctx *c, lmono_tracker *t, const lmono_reject_f *p)
+{
+    if (!c || !t || t->ctx != c) return LMONO_EINVAL;
+    if (!p) { t->rej_on = false; return LMONO_OK; }
+    if (!(p->f_threshold > 0.0) || !std::isfinite(p->f_threshold) || !(p->f_dis > 0.0) || !std::isfinite(p->f_dis) || !(p->focal_length >= 0.0) ||
+        !std::isfinite(p->focal_length) || p->n_hyp < 0 || p->n_hyp > kRejMaxHyp) {
+        c->err = "lmono_tracker_set_reject_f: f_threshold and f_dis must be finite and > 0, focal_length finite and >= 0, 0 <= n_hyp <= 1024";
+        return LMONO_EINVAL;
+    }
+    t->rej = *p;
+    if (t->rej.focal_length == 0.0) t->rej.focal_length = 460.0;      // FOCAL_LENGTH, parameter.h:50
+    if (t->rej.n_hyp == 0) t->rej.n_hyp = 256;
+    t->rej_on = true;
+    return LMONO_OK;
+}
+
+extern "C" int lmono_tracker_reject_stats(lmono_ctx *c, lmono_tracker *t, int32_t *stats, double *F)
+{
+    if (!c || !t || t->ctx != c) return LMONO_EINVAL;
+    for (int k = 0; k < 4 && stats; k++) stats[k] = t->rej_ran ? t->last_stats[k] : -1;
+    for (int k = 0; k < 9 && F; k++) F[k] = t->rej_ran ? t->last_F[k] : 0.0;
+    return LMONO_OK;
 }
 
 static int trk_job_table(lmono_ctx *c, lmono_tracker *lead, int n_streams, const char *who)
@@ -130,6 +173,7 @@ extern "C" int lmono_tracker_track_batch(lmono_ctx *c, int n_streams, lmono_trac
     if (int rc = trk_job_table(c, lead, n_streams, "lmono_tracker_track_batch")) return rc;
     std::vector<TrkJob> jobs((size_t)n_streams);
     size_t max_np = 0; int max_levels = 1, max_cnt = 1, max_tiles = 1;
+    bool any_reject = false;
     for (int s = 0; s < n_streams; s++) {
         lmono_tracker *t = trks[s];
         TrkJob &j = jobs[(size_t)s];
@@ -138,6 +182,7 @@ extern "C" int lmono_tracker_track_batch(lmono_ctx *c, int n_streams, lmono_trac
         j.src = image_d[s]; j.format = format; j.lk_n = -1;
         j.dt = times[s] - t->prev_time;
         j.n_out = lead->counts + s;
+        if (t->rej_on) { trk_reject_job(t, j, -1, (uint32_t)t->frames); any_reject = true; }
         max_np = std::max(max_np, (size_t)j.w * j.h);
         max_levels = std::max(max_levels, j.n_levels); max_cnt = std::max(max_cnt, j.max_cnt);
         max_tiles = std::max(max_tiles, ((j.w + kTrkTW - 1) / kTrkTW) * ((j.h + kTrkTH - 1) / kTrkTH));
@@ -160,6 +205,10 @@ extern "C" int lmono_tracker_track_batch(lmono_ctx *c, int n_streams, lmono_trac
     if (int rc = check_launch(c, "k_trk_lk")) return rc;
     k_trk_lk<<<dim3(lk_blocks, ns), kTrkT, 0, c->stream>>>(lead->jobs, 1);
     if (int rc = check_launch(c, "k_trk_lk")) return rc;
+    if (any_reject) {
+        k_trk_reject<<<ns, kRejT, 0, c->stream>>>(lead->jobs);
+        if (int rc = check_launch(c, "k_trk_reject")) return rc;
+    }
     k_trk_update<<<ns, kTrkMaxPts, 0, c->stream>>>(lead->jobs);
     if (int rc = check_launch(c, "k_trk_update")) return rc;
     k_trk_response<<<dim3((unsigned)max_tiles, ns), kTrkT, 0, c->stream>>>(lead->jobs);
@@ -177,6 +226,11 @@ extern "C" int lmono_tracker_track_batch(lmono_ctx *c, int n_streams, lmono_trac
         t->frames++; t->prev_time = times[s];
         if (records_out && records_out[s] && n_out[s] > 0)
             HIP_TRY(c, hipMemcpyAsync(records_out[s], t->job.rec, sizeof(lmono_track_record) * (size_t)n_out[s], hipMemcpyDeviceToHost, c->stream));
+        t->rej_ran = t->rej_on;
+        if (t->rej_on) {
+            HIP_TRY(c, hipMemcpyAsync(t->last_stats, t->rej_stats, sizeof(t->last_stats), hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(c, hipMemcpyAsync(t->last_F, t->rej_F, sizeof(t->last_F), hipMemcpyDeviceToHost, c->stream));
+        }
     }
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     for (int s = 0; s < n_streams; s++) { trks[s]->cur ^= 1; trks[s]->stale = false; }
@@ -242,5 +296,29 @@ extern "C" int lmono_tracker_lk(lmono_ctx *c, lmono_tracker *t, int n, const flo
     HIP_TRY(c, hipMemcpyAsync(sb.data(), j.st_b, (size_t)n, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     for (int i = 0; i < n; i++) { status_h[2 * i] = sf[(size_t)i]; status_h[2 * i + 1] = sb[(size_t)i]; }
+    return LMONO_OK;
+}
+
+extern "C" int lmono_tracker_reject_f(lmono_ctx *c, lmono_tracker *t, int n, const float *prev_px_h, const float *cur_px_h, uint32_t frame_key,
+                                      uint8_t *status_h, int32_t *stats, double *F)
+{
+    if (!c || !t || t->ctx != c || !prev_px_h || !cur_px_h || !status_h) return LMONO_EINVAL;
+    if (!t->rej_on) { c->err = "lmono_tracker_reject_f: rejection is off; call lmono_tracker_set_reject_f first"; return LMONO_EINVAL; }
+    if (n < 8 || n > kTrkMaxPts) { c->err = "lmono_tracker_reject_f: n must be in 8..512"; return LMONO_EINVAL; }
+    if (int rc = trk_job_table(c, t, 1, "lmono_tracker_reject_f")) return rc;
+    TrkJob j = t->job;
+    trk_reject_job(t, j, n, frame_key);
+    HIP_TRY(c, hipMemcpyAsync(t->rej_prev, prev_px_h, sizeof(float2) * (size_t)n, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(t->rej_cur, cur_px_h, sizeof(float2) * (size_t)n, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(t->jobs, &j, sizeof(TrkJob), hipMemcpyHostToDevice, c->stream));
+    k_trk_reject<<<1, kRejT, 0, c->stream>>>(t->jobs);
+    if (int rc = check_launch(c, "k_trk_reject")) return rc;
+    int32_t st[4]; double Fd[9];
+    HIP_TRY(c, hipMemcpyAsync(status_h, t->rej_st, (size_t)n, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(st, t->rej_stats, sizeof(st), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(Fd, t->rej_F, sizeof(Fd), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    for (int k = 0; k < 4 && stats; k++) stats[k] = st[k];
+    for (int k = 0; k < 9 && F; k++) F[k] = Fd[k];
     return LMONO_OK;
 }

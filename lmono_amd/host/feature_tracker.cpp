@@ -12,6 +12,20 @@ FeatureTracker::~FeatureTracker() { lmono_tracker_destroy(trk_); }
 
 void FeatureTracker::reset() { hip_.check(lmono_tracker_reset(hip_.get(), trk_), "lmono_tracker_reset"); }
 
+void FeatureTracker::setRejectF(double f_threshold, double f_dis)
+{
+    const lmono_reject_f prm = { f_threshold, f_dis, 0.0, 0, 0u };
+    hip_.check(lmono_tracker_set_reject_f(hip_.get(), trk_, &prm), "lmono_tracker_set_reject_f");
+}
+void FeatureTracker::clearRejectF() { hip_.check(lmono_tracker_set_reject_f(hip_.get(), trk_, nullptr), "lmono_tracker_set_reject_f"); }
+
+std::array<int32_t, 4> FeatureTracker::rejectStats(std::array<double, 9> *F)
+{
+    std::array<int32_t, 4> stats;
+    hip_.check(lmono_tracker_reject_stats(hip_.get(), trk_, stats.data(), F ? F->data() : nullptr), "lmono_tracker_reject_stats");
+    return stats;
+}
+
 FeatureTracker::FeatureFrame FeatureTracker::trackImage(double cur_time, const uint8_t *image, int format)
 {
     records.resize(LMONO_TRACK_MAX_POINTS);

@@ -1,9 +1,11 @@
 // lmono_amd/host/track_test.cpp -- synthetic frames -> FeatureTracker::trackImage (device tracker) -> FeatureManager::featureCheck.
 // A textured plane (sinusoids + random rectangles) is cut out under a slow drift; every frame's feature frame has to be taken in by
 // featureCheck in full: survivors extend their tracks, new ids open tracks, nothing else.  Prints one line per frame and "track_test ok".
+//   track_test [frames [seed [reject]]]   seed 0: the default canvas; "reject": setRejectF(1.0, 0.5), plus one REJ line per frame
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 #include <vector>
 #include "feature_tracker.hpp"
 
@@ -15,6 +17,8 @@ static double rnd() { g_seed = g_seed * 1664525u + 1013904223u; return (g_seed >
 int main(int argc, char **argv)
 {
     const int n_frames = argc > 1 ? std::atoi(argv[1]) : 24;
+    if (argc > 2 && std::atoi(argv[2]) != 0) g_seed = (unsigned int)std::atoi(argv[2]);
+    const bool reject = argc > 3 && std::strcmp(argv[3], "reject") == 0;
     const int W = 320, H = 240, CW = 480, CH = 360;
     std::vector<double> canvas((size_t)CW * CH);
     for (int y = 0; y < CH; y++)
@@ -30,6 +34,7 @@ int main(int argc, char **argv)
         Params params;
         lmono_camera cam = { W, H, 300.0, 300.0, 160.0, 120.0, -0.1, 0.02, 0.0005, -0.0005, 5, 0, 0 };
         FeatureTracker tracker(hip, cam, 150, 15);
+        if (reject) { tracker.setRejectF(1.0, 0.5); std::printf("rejectWithF on: F_THRESHOLD 1.0 F_DIS 0.5\n"); }
         FeatureManager fm;
         fm.params = &params; fm.hip = &hip;
         std::vector<uint8_t> bgr((size_t)W * H * 3);
@@ -65,6 +70,11 @@ int main(int argc, char **argv)
             }
             if (f > 0 && survivors < 50) { std::fprintf(stderr, "frame %d: only %d survivors\n", f, survivors); return 1; }
             keyframes += keyframe ? 1 : 0;
+            if (reject) {
+                const std::array<int32_t, 4> rs = tracker.rejectStats();
+                std::printf("REJ %d valid %d best %d inliers %d kept %d\n", f, rs[0], rs[1], rs[2], rs[3]);
+                if (f > 0 && (rs[0] <= 0 || rs[3] < 50)) { std::fprintf(stderr, "frame %d: rejectWithF kept %d\n", f, rs[3]); return 1; }
+            }
             std::printf("TRK %d features %zu survivors %d new %d keyframe %d tracks %zu\n", f, image.size(), survivors, fresh, keyframe ? 1 : 0, fm.feature.size());
             if (frame_count == WINDOW_SIZE) fm.removeBack();       // slideWindow, MARGIN_OLD (Estimator.cc:700-771)
             else frame_count++;

@@ -2,7 +2,9 @@
 streams at 1241 x 376 with 150 points, images resident on the device, plus per-kernel times of one 64-stream frame from the
 torch profiler's device events.  Prints one JSON line.  One process; run it under `timeout`; exits non-zero on any HIP error.
 
-  timeout 300 python scripts/track_bench.py [--streams 1,8,64,256] [--frames 12] [--warmup 3] [--no-kernels]"""
+  timeout 300 python scripts/track_bench.py [--streams 1,8,64,256] [--frames 12] [--warmup 3] [--no-kernels] [--reject-f THR DIS]
+
+--reject-f switches rejectWithF on in every stream (lmono_tracker_set_reject_f; k_trk_reject then shows among the kernels)."""
 import argparse
 import json
 import os
@@ -25,6 +27,7 @@ def main():
     ap.add_argument("--max-cnt", type=int, default=150)
     ap.add_argument("--min-dist", type=int, default=30)
     ap.add_argument("--no-kernels", action="store_true")
+    ap.add_argument("--reject-f", type=float, nargs=2, metavar=("THR", "DIS"))
     a = ap.parse_args()
     import torch
     import lmono_amd
@@ -36,9 +39,11 @@ def main():
     torch.cuda.synchronize()
     ctx = lmono_amd.Context(0)
     cam = lmono_amd.Camera(w, h, 718.856, 718.856, 607.1928, 185.2157, 0.0, 0.0, 0.0, 0.0, 5, 0, 0)
-    out = {"bench": "track", "width": w, "height": h, "max_cnt": a.max_cnt, "min_dist": a.min_dist, "frames": a.frames, "warmup": a.warmup, "runs": []}
+    out = {"bench": "track", "width": w, "height": h, "max_cnt": a.max_cnt, "min_dist": a.min_dist, "frames": a.frames, "warmup": a.warmup,
+           "reject_f": a.reject_f, "runs": []}
     for n in [int(x) for x in a.streams.split(",")]:
-        batch = lmono_amd.FeatureTrackerBatch(ctx, [cam] * n, a.max_cnt, a.min_dist)
+        batch = lmono_amd.FeatureTrackerBatch(ctx, [cam] * n, a.max_cnt, a.min_dist,
+                                              reject_f=dict(f_threshold=a.reject_f[0], f_dis=a.reject_f[1]) if a.reject_f else None)
         ms = []
         feats = 0
         for f in range(n_img):

@@ -166,7 +166,7 @@ class Context:
         return int(v.value)
 
     def odom_chain_groups(self, n_chains):
-        """Chain groups (HIP streams) an odometry call with n_chains chains runs on: the rule of odom_run in lmono_hip.hip."""
+        """Chain groups (HIP streams) an odometry call with n_chains chains runs on: the rule of odom_run in lidar_abi.hip."""
         g = max(1, min(8, self.get_option(self.OPT_ODOM_STREAMS)))
         if self.get_option(self.OPT_CORR_TILE) != 3:
             return 1

@@ -113,7 +113,7 @@ def test_chain_groups_and_lead_in_options_at_bench_scale(seq00):
 
 
 def test_context_on_a_caller_stream_gives_the_same_increments(seq00):
-    """A context moved onto a caller-created stream runs at most 3 chain groups, all on the library's own streams (lmono_hip.hip:
+    """A context moved onto a caller-created stream runs at most 3 chain groups, all on the library's own streams (lidar_abi.hip:
     odom_run); the increments are the null-stream context's bit for bit."""
     import torch
     import lmono_amd

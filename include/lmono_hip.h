@@ -468,6 +468,9 @@ lmono_pose_graph *lmono_pose_graph_create(lmono_ctx *, int n, const double *pose
 void              lmono_pose_graph_destroy(lmono_pose_graph *);
 int   lmono_pose_graph_reset(lmono_ctx *, lmono_pose_graph *);                    /* back to the odometry poses, same graph */
 int   lmono_pose_graph_info(lmono_pose_graph *, int64_t *reduce_count, int *bandwidth_blocks, int *n_edges);
+/* pos_out [n]: the elimination position of every keyframe (reverse Cuthill-McKee); H, g and cost of the reduce buffer are
+ * stored in that order: H [n][bandwidth + 1][16] (block (p, p - d), row-major, lower band) | g [4 n] | cost [n] */
+int   lmono_pose_graph_order(lmono_pose_graph *, int32_t *pos_out);
 void *lmono_pose_graph_reduce_buffer(lmono_pose_graph *);                         /* device pointer, reduce_count doubles */
 /* use a caller-owned device buffer of reduce_count doubles instead (e.g. the storage of the tensor handed to the all-reduce) */
 int   lmono_pose_graph_set_reduce_buffer(lmono_pose_graph *, void *buffer_d);

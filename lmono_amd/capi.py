@@ -18,7 +18,7 @@ SYMBOLS = [
     "lmono_map_builder_cloud", "lmono_map_builder_map", "lmono_map_builder_clear",
     "lmono_tracker_create", "lmono_tracker_destroy", "lmono_tracker_reset", "lmono_tracker_track", "lmono_tracker_track_batch", "lmono_tracker_pyramid",
     "lmono_tracker_response", "lmono_tracker_lk", "lmono_tracker_set_reject_f", "lmono_tracker_reject_stats", "lmono_tracker_reject_f",
-    "lmono_pose_graph_create", "lmono_pose_graph_destroy", "lmono_pose_graph_reset", "lmono_pose_graph_info", "lmono_pose_graph_reduce_buffer", "lmono_pose_graph_set_reduce_buffer", "lmono_pose_graph_linearise",
+    "lmono_pose_graph_create", "lmono_pose_graph_destroy", "lmono_pose_graph_reset", "lmono_pose_graph_info", "lmono_pose_graph_order", "lmono_pose_graph_reduce_buffer", "lmono_pose_graph_set_reduce_buffer", "lmono_pose_graph_linearise",
     "lmono_pose_graph_step", "lmono_pose_graph_optimize", "lmono_pose_graph_result", "lmono_factor_eval", "lmono_factor_eval_d", "lmono_factor_eval_blocks", "lmono_factor_eval_blocks_d",
     "lmono_triangulate", "lmono_outlier_scores", "lmono_shift_depth", "lmono_shift_depth_batch", "lmono_marginalize", "lmono_marg_evaluate", "lmono_marg_second_new", "lmono_ba_batch_create", "lmono_ba_batch_update", "lmono_ba_batch_destroy", "lmono_ba_solve", "lmono_ba_batch_reset", "lmono_ba_batch_read", "lmono_debug_bounds",
 ]
@@ -996,6 +996,13 @@ class PoseGraph:
     def reset(self):
         self.ctx.L.lmono_pose_graph_reset.argtypes = [C.c_void_p, C.c_void_p]
         self.ctx.check(self.ctx.L.lmono_pose_graph_reset(self.ctx.h, self.h))
+
+    def order(self):
+        """Elimination position of every keyframe: the order H, g and cost are stored in inside the reduce buffer."""
+        pos = np.zeros(self.n, np.int32)
+        self.ctx.L.lmono_pose_graph_order.argtypes = [C.c_void_p, C.c_void_p]
+        self.ctx.check(self.ctx.L.lmono_pose_graph_order(self.h, pos.ctypes.data))
+        return pos
 
     def use_reduce_tensor(self, tensor):
         """Make a caller-owned contiguous fp64 device tensor of reduce_count elements the buffer linearise() fills and step()

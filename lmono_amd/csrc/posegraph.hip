@@ -137,7 +137,7 @@ __global__ __launch_bounds__(256) void k_pg_linearise(PgView v, int lo, int hi)
     }
     *cost = cs;
     if (node == 0) {
-        if (lo == 0) { Hrow[0] = 1.0; Hrow[5] = 1.0; Hrow[10] = 1.0; Hrow[15] = 1.0; }     // once over all ranks
+        if (lo == 0 && hi > 0) { Hrow[0] = 1.0; Hrow[5] = 1.0; Hrow[10] = 1.0; Hrow[15] = 1.0; }     // once over all ranks: by the owner of keyframe 0 (with world > n several ranks start at 0)
         return;
     }
     if (!any) return;

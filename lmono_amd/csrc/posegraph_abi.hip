@@ -14,6 +14,7 @@ struct lmono_pose_graph {
     int64_t reduce_count = 0;
     std::vector<void *> allocs;
     std::vector<double> pitch_h, roll_h, x0_h;
+    std::vector<int> pos_h;
 };
 
 template <typename T> static bool pg_upload(lmono_pose_graph *g, const T *&dst, const std::vector<T> &src)
@@ -164,7 +165,7 @@ extern "C" lmono_pose_graph *lmono_pose_graph_create(lmono_ctx *c, int n, const 
               pg_alloc(g, v.cur, (size_t)g->reduce_count) && pg_alloc(g, v.Aw, hsz) && pg_alloc(g, v.scale, (size_t)n * 4) && pg_alloc(g, v.diag, (size_t)n * 4) &&
               pg_alloc(g, v.gs, (size_t)n * 4) && pg_alloc(g, v.sol, (size_t)n * 4) && pg_alloc(g, v.st, 1);
     ok = ok && hipMemcpy(v.x, x.data(), x.size() * sizeof(double), hipMemcpyHostToDevice) == hipSuccess;
-    g->x0_h = x;
+    g->x0_h = x; g->pos_h = pos;
     if (!ok) { c->err = "lmono_pose_graph_create: device allocation failed"; lmono_pose_graph_destroy(g); return nullptr; }
     return g;
 }
@@ -183,6 +184,13 @@ extern "C" int lmono_pose_graph_info(lmono_pose_graph *g, int64_t *reduce_count,
     if (reduce_count) *reduce_count = g->reduce_count;
     if (bandwidth) *bandwidth = g->w;
     if (n_edges) *n_edges = g->n_edges;
+    return LMONO_OK;
+}
+
+extern "C" int lmono_pose_graph_order(lmono_pose_graph *g, int32_t *pos_out)
+{
+    if (!g || !pos_out) return LMONO_EINVAL;
+    for (int i = 0; i < g->n; i++) pos_out[i] = g->pos_h[(size_t)i];
     return LMONO_OK;
 }
 

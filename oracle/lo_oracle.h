@@ -150,6 +150,7 @@ lo_pg *lo_pg_create(int n, const double *poses_tq, int n_loops, const int32_t *l
 void lo_pg_free(lo_pg *);
 int64_t lo_pg_reduce_count(const lo_pg *);
 int lo_pg_bandwidth(const lo_pg *);
+void lo_pg_order(const lo_pg *, int32_t *pos_out);                      /* elimination position of every keyframe */
 void lo_pg_linearise(lo_pg *, int rank, int world, double *buf);       /* this rank's [H band | g | cost] */
 int lo_pg_step(lo_pg *, const double *summed_buf, int max_iter);        /* 1 when finished */
 void lo_pg_result(const lo_pg *, double *out_tq, double *stats);

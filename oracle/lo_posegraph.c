@@ -116,7 +116,7 @@ static double edge_eval(const pg_graph *g, const pg_edge *e, const double *x /* 
 
 /* band storage: scalar row i = 4 pos + c holds columns 4 (pos - w) .. 4 pos + 3 in band[i * bw + (col - 4 (pos - w))], bw = 4 (w + 1).
  * Only the edges whose newer keyframe b lies in [lo, hi) are added (the share of one rank); the identity rows of the constant
- * first keyframe are written by the rank that owns keyframe 0. */
+ * first keyframe are written by the rank that owns keyframe 0 (lo <= 0 < hi: with more ranks than keyframes several start at 0). */
 static double linearise(const pg_graph *g, const double *x, double *band, double *grad, int lo, int hi)
 {
     const int n = g->n, w = g->w, bw = 4 * (w + 1);
@@ -150,7 +150,7 @@ static double linearise(const pg_graph *g, const double *x, double *band, double
             }
         }
     }
-    if (lo == 0) for (int c = 0; c < 4; c++) band[(size_t)(4 * p0 + c) * bw + (4 * w + c)] = 1.0;
+    if (lo == 0 && hi > 0) for (int c = 0; c < 4; c++) band[(size_t)(4 * p0 + c) * bw + (4 * w + c)] = 1.0;
     return cost;
 }
 
@@ -290,6 +290,7 @@ lo_pg *lo_pg_create(int n, const double *poses_tq, int n_loops, const int32_t *l
 
 int64_t lo_pg_reduce_count(const lo_pg *s) { return (int64_t)s->n4 * s->bw + s->n4 + 1; }
 int lo_pg_bandwidth(const lo_pg *s) { return s->g.w; }
+void lo_pg_order(const lo_pg *s, int32_t *pos_out) { for (int i = 0; i < s->g.n; i++) pos_out[i] = s->g.pos[i]; }
 
 /* buf: [H band | g | cost] of the edges owned by `rank` at the current linearisation point */
 void lo_pg_linearise(lo_pg *s, int rank, int world, double *buf)

@@ -597,6 +597,11 @@ class PoseGraph:
         t = self.reduce_tensor
         return t if isinstance(t, np.ndarray) else t.numpy()       # a CPU torch tensor shares its memory with the array
 
+    def order(self):
+        pos = np.zeros(self.n, np.int32)
+        lib().lo_pg_order(self.h, _fp(pos, C.c_int32))
+        return pos
+
     def linearise(self, rank=0, world=1):
         lib().lo_pg_linearise(self.h, C.c_int(rank), C.c_int(world), _fp(self._buf(), C.c_double))
 

@@ -451,6 +451,55 @@ int lmono_tracker_reject_stats(lmono_ctx *, lmono_tracker *, int32_t *stats, dou
 int lmono_tracker_reject_f(lmono_ctx *, lmono_tracker *, int n, const float *prev_px_h, const float *cur_px_h, uint32_t frame_key,
                            uint8_t *status_h, int32_t *stats, double *F);
 
+/* ---- keyframe descriptors ------------------------------------------------------------------------------------
+ * Replaces the per-keyframe image work of the loop detector, KeyFrame (mono_lidar_mapping/src/loop_detection/KeyFrame.cc):
+ * computeBRIEFPoint (:184-210: cv::FAST(image, kp, 20, true), a BRIEF descriptor per corner, liftProjective), computeWindowBRIEFPoint
+ * (:172-182: a descriptor per window point point_2d_uv), DVision's BRIEF::compute (src/loop_detection/DVision/BRIEF.cpp:39-106:
+ * 9 x 9 Gaussian blur with sigma 2, 256 pixel-pair tests), searchByBRIEFDes / searchInAera (:217-267: exhaustive Hamming search from
+ * 128 with a strict <, matched below 80) and the count that findConnection compares with MIN_BRIEF_LOOP_NUM (:455-462, :557).
+ * FAST-9/16 with 3 x 3 strict non-maximum suppression and the integer blur ([7 17 32 46 52 46 32 17 7] / 256 per axis, REFLECT_101,
+ * one rounding) are definitions of this project, written out in DESIGN.md 6f: parity with cv::FAST and cv::GaussianBlur is unpinned.
+ * BRIEF and the search follow the reference's source statement by statement.  The test pattern is an argument (the reference reads
+ * brief_pattern.yml from BRIEF_PATTERN_FILE at run time).  Keypoints are in row-major order (y, then x).
+ * Not provided: db.query / db.add (DBoW2; the vocabulary is absent), PnPRANSAC and everything behind it (:551-688), the USE_ORB
+ * branch, the thumbnail, distributionValidation (dead code), every DEBUG_IMAGE product.                                              */
+typedef struct { int8_t x1[256], y1[256], x2[256], y2[256]; } lmono_brief_pattern;   /* every offset in -63..63 */
+typedef struct lmono_keyframes lmono_keyframes;
+/* A device-resident store of up to max_keyframes (<= 65535) keyframes of up to max_keypoints (<= 65535) FAST corners each: per keyframe
+ * its keypoints, normalised keypoints, descriptors (8 uint32: bit i is bit i & 31 of word i >> 5), window points and window descriptors.
+ * fast_threshold: 0 means 20 (:187).  The camera is the lmono_camera of the map builder (PINHOLE; kernel_* / blur_type are not read).
+ * NULL (see lmono_last_error) for an image side outside 16..8192, limits exceeded or a pattern offset outside -63..63. */
+lmono_keyframes *lmono_keyframes_create(lmono_ctx *, const lmono_camera *, const lmono_brief_pattern *, int max_keyframes, int max_keypoints, int fast_threshold);
+void             lmono_keyframes_destroy(lmono_keyframes *);
+int              lmono_keyframes_clear(lmono_ctx *, lmono_keyframes *);                    /* forget every keyframe */
+int              lmono_keyframes_size(lmono_ctx *, lmono_keyframes *);                     /* stored keyframes (or an error < 0) */
+/* The first KeyFrame constructor (:14-93) on a host image (format: LMONO_TRACK_GREY8 / LMONO_TRACK_BGR8): window_uv_h [n_window <= 512][2]
+ * are point_2d_uv.  *index_out: the new keyframe's index; *n_keypoints_out: FAST corners found (also when refused).  LMONO_ECAPACITY,
+ * with the store unchanged and nothing truncated, when the image has more corners than max_keypoints or the store is full. */
+int lmono_keyframes_add(lmono_ctx *, lmono_keyframes *, const uint8_t *image_h, int format, int n_window, const float *window_uv_h, int *index_out, int *n_keypoints_out);
+/* n independent stores (distinct) advanced by one keyframe each, images already resident in HBM (image_d[s] device pointers; n_window,
+ * index_out, n_keypoints_out host arrays [n]; window_uv_h [n] host pointers); every phase is one launch for all streams and the call has
+ * one read-back.  When any stream is refused (LMONO_ECAPACITY) no store is changed. */
+int lmono_keyframes_add_batch(lmono_ctx *, int n, lmono_keyframes *const *stores, const uint8_t *const *image_d, int format, const int *n_window,
+                              const float *const *window_uv_h, int *index_out, int *n_keypoints_out);
+/* The second KeyFrame constructor (:96-133): a keyframe from saved keypoints [n][2], normalised keypoints [n][2] and descriptors [n][8],
+ * without an image; optionally with window points and their descriptors (n_window may be 0). */
+int lmono_keyframes_load(lmono_ctx *, lmono_keyframes *, int n_keypoints, const float *keypoints_h, const float *norm_h, const uint32_t *descriptors_h,
+                         int n_window, const float *window_uv_h, const uint32_t *window_descriptors_h, int *index_out);
+/* searchByBRIEFDes (:248-267) of keyframe `cur`'s window descriptors against n_old stored keyframes in one launch.  Outputs (any may be
+ * NULL) are [n_old][n_window of cur]: status (1: matched), index of the nearest old keypoint (-1: no distance below 128), its distance
+ * (128 then), the matched old pixel and old normalised point ((0, 0) when unmatched, as the reference pushes); counts_h [n_old]: matched
+ * points per old keyframe, the number findConnection compares with MIN_BRIEF_LOOP_NUM (:557).  Equal distances: the lowest index wins. */
+int lmono_keyframes_match(lmono_ctx *, lmono_keyframes *, int cur, int n_old, const int32_t *old_indices, uint8_t *status_h, int32_t *index_h, int32_t *dist_h,
+                          float *old_uv_h, float *old_norm_h, int32_t *counts_h);
+/* diagnostics: the blurred image and the FAST score image (A - 1 at a corner, else 0), [height][width] uint8, of the last image added
+ * (refused ones included); either may be NULL */
+int lmono_keyframes_images(lmono_ctx *, lmono_keyframes *, uint8_t *blur_h, uint8_t *score_h);
+/* a stored keyframe: counts and (any may be NULL) keypoints [n][2], normalised keypoints [n][2], descriptors [n][8], window points
+ * [m][2], window descriptors [m][8]; call once with NULL arrays for the counts */
+int lmono_keyframes_get(lmono_ctx *, lmono_keyframes *, int index, int *n_keypoints, float *keypoints_h, float *norm_h, uint32_t *descriptors_h,
+                        int *n_window, float *window_uv_h, uint32_t *window_descriptors_h);
+
 /* ---- loop-closure pose graph -- NEW FEATURE, no counterpart in the reference --------------------------
  * The reference detects loops and publishes loop_info = relative_t, relative_q (w x y z), relative_yaw
  * (mono_lidar_mapping/src/loop_detection/KeyFrame.cc:570-633) and re-anchors the window rigidly (Estimator.cc:309-365); it never

@@ -18,6 +18,8 @@ SYMBOLS = [
     "lmono_map_builder_cloud", "lmono_map_builder_map", "lmono_map_builder_clear",
     "lmono_tracker_create", "lmono_tracker_destroy", "lmono_tracker_reset", "lmono_tracker_track", "lmono_tracker_track_batch", "lmono_tracker_pyramid",
     "lmono_tracker_response", "lmono_tracker_lk", "lmono_tracker_set_reject_f", "lmono_tracker_reject_stats", "lmono_tracker_reject_f",
+    "lmono_keyframes_create", "lmono_keyframes_destroy", "lmono_keyframes_clear", "lmono_keyframes_size", "lmono_keyframes_add", "lmono_keyframes_add_batch",
+    "lmono_keyframes_load", "lmono_keyframes_match", "lmono_keyframes_images", "lmono_keyframes_get",
     "lmono_pose_graph_create", "lmono_pose_graph_destroy", "lmono_pose_graph_reset", "lmono_pose_graph_info", "lmono_pose_graph_order", "lmono_pose_graph_reduce_buffer", "lmono_pose_graph_set_reduce_buffer", "lmono_pose_graph_linearise",
     "lmono_pose_graph_step", "lmono_pose_graph_optimize", "lmono_pose_graph_result", "lmono_factor_eval", "lmono_factor_eval_d", "lmono_factor_eval_blocks", "lmono_factor_eval_blocks_d",
     "lmono_triangulate", "lmono_outlier_scores", "lmono_shift_depth", "lmono_shift_depth_batch", "lmono_marginalize", "lmono_marg_evaluate", "lmono_marg_second_new", "lmono_ba_batch_create", "lmono_ba_batch_update", "lmono_ba_batch_destroy", "lmono_ba_solve", "lmono_ba_batch_reset", "lmono_ba_batch_read", "lmono_debug_bounds",
@@ -960,6 +962,180 @@ class FeatureTrackerBatch:
     def close(self):
         for t in self.trackers:
             t.close()
+
+
+class BriefPattern(C.Structure):
+    """lmono_brief_pattern: the 256 pixel-pair tests of DVision's BRIEF (x1, y1, x2, y2 of brief_pattern.yml)."""
+    _fields_ = [("x1", C.c_int8 * 256), ("y1", C.c_int8 * 256), ("x2", C.c_int8 * 256), ("y2", C.c_int8 * 256)]
+
+
+def load_brief_pattern(path):
+    """Read an OpenCV-YAML pattern file in the list layout of the reference's brief_pattern.yml (a line `x1:` followed by one
+    `- <integer>` line per entry, likewise y1, x2, y2) -> int32 [4, 256] in the order x1, y1, x2, y2.  No YAML library."""
+    keys = ("x1", "y1", "x2", "y2")
+    got = {}
+    cur = None
+    with open(path) as f:
+        for no, raw in enumerate(f, 1):
+            line = raw.split("#")[0].strip() if not raw.startswith("%") else ""
+            if not line or line == "---":
+                continue
+            if line.endswith(":") and line[:-1].strip() in keys:
+                cur = line[:-1].strip()
+                if cur in got:
+                    raise LmonoError("%s:%d: key %s appears twice" % (path, no, cur))
+                got[cur] = []
+            elif line.startswith("-") and cur is not None:
+                try:
+                    got[cur].append(int(line[1:].strip()))
+                except ValueError:
+                    raise LmonoError("%s:%d: not an integer entry: %r" % (path, no, raw.rstrip())) from None
+            else:
+                raise LmonoError("%s:%d: not a line of a BRIEF pattern list: %r" % (path, no, raw.rstrip()))
+    for k in keys:
+        if len(got.get(k, ())) != 256:
+            raise LmonoError("%s: key %s has %d entries, a BRIEF pattern needs exactly 256" % (path, k, len(got.get(k, ()))))
+    return np.array([got[k] for k in keys], np.int32)
+
+
+def _brief_pattern_struct(pattern):
+    p = np.asarray(pattern)
+    if p.shape != (4, 256):
+        raise LmonoError("a BRIEF pattern is [4][256] integers (x1, y1, x2, y2)")
+    if (np.abs(p.astype(np.int64)) > 127).any():
+        raise LmonoError("a BRIEF pattern offset does not fit 8 bits (the library takes -63..63)")
+    s = BriefPattern()
+    for name, row in zip(("x1", "y1", "x2", "y2"), p):
+        getattr(s, name)[:] = [int(v) for v in row]
+    return s
+
+
+def _keyframes_prototypes(L):
+    L.lmono_keyframes_create.restype = C.c_void_p
+    L.lmono_keyframes_create.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int]
+    L.lmono_keyframes_destroy.argtypes = [C.c_void_p]
+    L.lmono_keyframes_clear.argtypes = [C.c_void_p, C.c_void_p]
+    L.lmono_keyframes_size.argtypes = [C.c_void_p, C.c_void_p]
+    L.lmono_keyframes_add.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.lmono_keyframes_add_batch.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 4
+    L.lmono_keyframes_load.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.lmono_keyframes_match.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 7
+    L.lmono_keyframes_images.argtypes = [C.c_void_p] * 4
+    L.lmono_keyframes_get.argtypes = [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 7
+
+
+class KeyFrames:
+    """A device-resident store of keyframes (lmono_keyframes_*): FAST corners, BRIEF descriptors of the corners and of
+    the window points, and the exhaustive Hamming search of KeyFrame::searchByBRIEFDes.  pattern: [4][256] (load_brief_pattern)."""
+
+    def __init__(self, ctx, camera, pattern, max_keyframes=64, max_keypoints=4096, fast_threshold=0):
+        self.ctx = ctx
+        ctx._children.add(self)
+        self.cam = camera
+        _keyframes_prototypes(ctx.L)
+        pat = _brief_pattern_struct(pattern)
+        self.h = ctx.L.lmono_keyframes_create(ctx.h, C.byref(camera), C.byref(pat), int(max_keyframes), int(max_keypoints), int(fast_threshold))
+        if not self.h:
+            raise LmonoError("lmono_keyframes_create failed: " + ctx.last_error())
+        self.last_n_keypoints = 0
+
+    def _format(self, image):
+        if image.shape == (self.cam.height, self.cam.width):
+            return 0
+        if image.shape == (self.cam.height, self.cam.width, 3):
+            return 1
+        raise LmonoError("image must be [height][width] or [height][width][3] uint8")
+
+    def __len__(self):
+        n = self.ctx.L.lmono_keyframes_size(self.ctx.h, self.h)
+        self.ctx.check(min(n, 0))
+        return n
+
+    def add(self, image, window_uv):
+        """One keyframe from a host image and its window points [n <= 512][2] -> (index, FAST corners found)."""
+        image = np.ascontiguousarray(image, np.uint8)
+        uv = np.ascontiguousarray(window_uv, np.float32).reshape(-1, 2)
+        idx, nkp = C.c_int(-1), C.c_int(0)
+        rc = self.ctx.L.lmono_keyframes_add(self.ctx.h, self.h, image.ctypes.data, self._format(image), len(uv), uv.ctypes.data if len(uv) else None,
+                                            C.addressof(idx), C.addressof(nkp))
+        self.last_n_keypoints = nkp.value
+        self.ctx.check(rc)
+        return idx.value, nkp.value
+
+    @classmethod
+    def add_batch(cls, stores, image_ptrs, window_uvs, bgr=False):
+        """One keyframe for each of several distinct stores, every phase one launch (lmono_keyframes_add_batch).  image_ptrs: device
+        pointers (e.g. torch tensors' data_ptr()) -> (indices [n], FAST corners found [n])."""
+        n = len(stores)
+        ctx = stores[0].ctx
+        uvs = [np.ascontiguousarray(u, np.float32).reshape(-1, 2) for u in window_uvs]
+        if len(uvs) != n or len(image_ptrs) != n:
+            raise LmonoError("add_batch needs one image and one window point array per store")
+        hs = (C.c_void_p * n)(*[s.h for s in stores])
+        ip = (C.c_void_p * n)(*[int(p) for p in image_ptrs])
+        up = (C.c_void_p * n)(*[u.ctypes.data if len(u) else None for u in uvs])
+        nw = np.array([len(u) for u in uvs], np.int32)
+        idx = np.full(n, -1, np.int32); nkp = np.zeros(n, np.int32)
+        rc = ctx.L.lmono_keyframes_add_batch(ctx.h, n, hs, ip, 1 if bgr else 0, nw.ctypes.data, up, idx.ctypes.data, nkp.ctypes.data)
+        for s, k in zip(stores, nkp):
+            s.last_n_keypoints = int(k)
+        ctx.check(rc)
+        return idx, nkp
+
+    def load(self, keypoints, norm, descriptors, window_uv=None, window_descriptors=None):
+        """A keyframe from saved data (the reference's second constructor) -> index."""
+        kp = np.ascontiguousarray(keypoints, np.float32).reshape(-1, 2); nm = np.ascontiguousarray(norm, np.float32).reshape(-1, 2)
+        de = np.ascontiguousarray(descriptors, np.uint32).reshape(-1, 8)
+        uv = np.zeros((0, 2), np.float32) if window_uv is None else np.ascontiguousarray(window_uv, np.float32).reshape(-1, 2)
+        wd = np.zeros((0, 8), np.uint32) if window_descriptors is None else np.ascontiguousarray(window_descriptors, np.uint32).reshape(-1, 8)
+        if not (len(kp) == len(nm) == len(de)) or len(uv) != len(wd):
+            raise LmonoError("load: keypoints / norm / descriptors (and window points / descriptors) differ in length")
+        idx = C.c_int(-1)
+        self.ctx.check(self.ctx.L.lmono_keyframes_load(self.ctx.h, self.h, len(kp), kp.ctypes.data, nm.ctypes.data, de.ctypes.data, len(uv), uv.ctypes.data, wd.ctypes.data,
+                                                       C.addressof(idx)))
+        return idx.value
+
+    def get(self, index):
+        """-> dict: keypoints [n, 2], norm [n, 2], descriptors [n, 8], window_uv [m, 2], window_descriptors [m, 8] of a stored keyframe."""
+        nk, nw = C.c_int(0), C.c_int(0)
+        self.ctx.check(self.ctx.L.lmono_keyframes_get(self.ctx.h, self.h, int(index), C.addressof(nk), None, None, None, C.addressof(nw), None, None))
+        kp = np.zeros((nk.value, 2), np.float32); nm = np.zeros_like(kp); de = np.zeros((nk.value, 8), np.uint32)
+        uv = np.zeros((nw.value, 2), np.float32); wd = np.zeros((nw.value, 8), np.uint32)
+        self.ctx.check(self.ctx.L.lmono_keyframes_get(self.ctx.h, self.h, int(index), None, kp.ctypes.data, nm.ctypes.data, de.ctypes.data, None, uv.ctypes.data, wd.ctypes.data))
+        return {"keypoints": kp, "norm": nm, "descriptors": de, "window_uv": uv, "window_descriptors": wd}
+
+    def images(self):
+        """-> (blurred image, FAST score image), uint8 [height, width], of the last image added."""
+        b = np.zeros((self.cam.height, self.cam.width), np.uint8); s = np.zeros_like(b)
+        self.ctx.check(self.ctx.L.lmono_keyframes_images(self.ctx.h, self.h, b.ctypes.data, s.ctypes.data))
+        return b, s
+
+    def match(self, cur, old_indices):
+        """searchByBRIEFDes of keyframe cur's window descriptors against each of old_indices -> dict of [n_old, n_window] arrays
+        status, index, dist, old_uv [.., 2], old_norm [.., 2] and counts [n_old]."""
+        old = np.ascontiguousarray(old_indices, np.int32).reshape(-1)
+        nw = C.c_int(0)
+        self.ctx.check(self.ctx.L.lmono_keyframes_get(self.ctx.h, self.h, int(cur), None, None, None, None, C.addressof(nw), None, None))
+        n, m = len(old), nw.value
+        st = np.zeros((n, m), np.uint8); ix = np.full((n, m), -1, np.int32); di = np.full((n, m), 128, np.int32)
+        uv = np.zeros((n, m, 2), np.float32); nm = np.zeros((n, m, 2), np.float32); cnt = np.zeros(n, np.int32)
+        self.ctx.check(self.ctx.L.lmono_keyframes_match(self.ctx.h, self.h, int(cur), n, old.ctypes.data, st.ctypes.data, ix.ctypes.data, di.ctypes.data,
+                                                        uv.ctypes.data, nm.ctypes.data, cnt.ctypes.data))
+        return {"status": st, "index": ix, "dist": di, "old_uv": uv, "old_norm": nm, "counts": cnt}
+
+    def clear(self):
+        self.ctx.check(self.ctx.L.lmono_keyframes_clear(self.ctx.h, self.h))
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.ctx.L.lmono_keyframes_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class PoseGraph:

@@ -337,4 +337,5 @@ extern "C" void lmono_host_free(lmono_ctx *c, void *p) { if (c && p) (void)hipHo
 #include "mapping_abi.hip"
 #include "colour_abi.hip"
 #include "track_abi.hip"
+#include "keyframe_abi.hip"
 #include "posegraph_abi.hip"

@@ -79,6 +79,9 @@ __device__ __forceinline__ int trk_reflect(int i, int n)
     return min(max(i, 0), n - 1);
 }
 
+// cv::cvtColor BGR2GRAY on 8-bit data (shared with keyframe.hip)
+__device__ __forceinline__ int trk_bgr_to_grey(int b, int g, int r) { return (b * 1868 + g * 9617 + r * 4899 + 8192) >> 14; }
+
 __global__ __launch_bounds__(kTrkT) void k_trk_grey(const TrkJob *jobs)
 {
     const TrkJob &j = jobs[blockIdx.y];
@@ -88,7 +91,7 @@ __global__ __launch_bounds__(kTrkT) void k_trk_grey(const TrkJob *jobs)
         if (j.format == 0) dst[i] = j.src[i];
         else {
             const int b = j.src[3 * (size_t)i], g = j.src[3 * (size_t)i + 1], r = j.src[3 * (size_t)i + 2];
-            dst[i] = (unsigned char)((b * 1868 + g * 9617 + r * 4899 + 8192) >> 14);
+            dst[i] = (unsigned char)trk_bgr_to_grey(b, g, r);
         }
     }
 }

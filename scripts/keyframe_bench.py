@@ -1,0 +1,126 @@
+"""scripts/keyframe_bench.py -- throughput of the device keyframe descriptors (lmono_keyframes_*): keyframes/s of
+lmono_keyframes_add_batch for 1, 8, 64 streams at 1241 x 376 with 150 window points, images resident on the device; matches/s of
+lmono_keyframes_match for one current keyframe against 4 and against 1024 stored keyframes; per-kernel times of one 64-stream add and
+of one 1024-keyframe match from the torch profiler's device events.  Prints one JSON line.  One process; run it under `timeout`;
+exits non-zero on any HIP error.
+
+  timeout 300 python scripts/keyframe_bench.py [--pattern tests/golden/brief_pattern.yml] [--streams 1,8,64] [--old 4,1024]
+                                               [--calls 12] [--warmup 3] [--no-kernels]"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def _kernel_times(prof):
+    kern = {}
+    for e in prof.key_averages():
+        if "k_kf_" in e.key:
+            name = e.key[e.key.index("k_kf_"):].split("(")[0]
+            name = name.split("E")[0] if e.key.startswith("_Z") else name
+            us = getattr(e, "device_time_total", None)
+            if us is None:
+                us = getattr(e, "cuda_time_total", 0.0)
+            kern[name] = kern.get(name, 0.0) + float(us)
+    return kern
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--pattern", default=os.path.join(ROOT, "tests", "golden", "brief_pattern.yml"))
+    ap.add_argument("--streams", default="1,8,64")
+    ap.add_argument("--old", default="4,1024")
+    ap.add_argument("--calls", type=int, default=12)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--width", type=int, default=1241)
+    ap.add_argument("--height", type=int, default=376)
+    ap.add_argument("--window", type=int, default=150)
+    ap.add_argument("--max-keypoints", type=int, default=8192)
+    ap.add_argument("--no-kernels", action="store_true")
+    a = ap.parse_args()
+    import torch
+    import lmono_amd
+    from workloads import s5
+    w, h = a.width, a.height
+    pat = lmono_amd.load_brief_pattern(a.pattern)
+    n_img = a.calls + a.warmup
+    variants = [s5.Sequence(w, h, 2, seed=20 + v, step=(2.0 + 0.5 * v, 0.5 * v - 0.5), margin=64).frames for v in range(4)]
+    dev = [[torch.from_numpy(f).to("cuda:0") for f in seq] for seq in variants]       # 4 x 2 images shared by all streams (device resident)
+    torch.cuda.synchronize()
+    rng = np.random.default_rng(1)
+    uv = np.stack([rng.uniform(20, w - 20, a.window), rng.uniform(20, h - 20, a.window)], 1).astype(np.float32)
+    ctx = lmono_amd.Context(0)
+    cam = lmono_amd.Camera(w, h, 718.856, 718.856, 607.1928, 185.2157, 0.0, 0.0, 0.0, 0.0, 5, 0, 0)
+    out = {"bench": "keyframe", "width": w, "height": h, "window": a.window, "max_keypoints": a.max_keypoints, "calls": a.calls, "warmup": a.warmup,
+           "add": [], "match": []}
+    for n in [int(x) for x in a.streams.split(",")]:
+        stores = [lmono_amd.KeyFrames(ctx, cam, pat, 2, a.max_keypoints) for _ in range(n)]
+        ms, nkp = [], None
+        for f in range(n_img):
+            for s in stores:
+                s.clear()
+            ptrs = [dev[s % 4][f % 2].data_ptr() for s in range(n)]
+            t0 = time.perf_counter()
+            _, nkp = lmono_amd.KeyFrames.add_batch(stores, ptrs, [uv] * n)               # synchronises before it returns
+            dt = (time.perf_counter() - t0) * 1e3
+            if f >= a.warmup:
+                ms.append(dt)
+        ms = np.array(ms)
+        run = {"streams": n, "ms_per_call_median": float(np.median(ms)), "ms_per_call_min": float(ms.min()), "ms_per_call_max": float(ms.max()),
+               "keyframes_per_s": float(n * 1e3 / np.median(ms)), "keypoints_mean": float(np.mean(nkp))}
+        if n == 64 and not a.no_kernels:
+            from torch.profiler import ProfilerActivity, profile
+            for s in stores:
+                s.clear()
+            with profile(activities=[ProfilerActivity.CUDA, ProfilerActivity.CPU]) as prof:
+                lmono_amd.KeyFrames.add_batch(stores, [dev[s % 4][0].data_ptr() for s in range(n)], [uv] * n)
+                torch.cuda.synchronize()
+            run["kernels_us"] = _kernel_times(prof)
+        out["add"].append(run)
+        for s in stores:
+            s.close()
+    # one current keyframe against stored keyframes: the store is filled by lmono_keyframes_load with copies of four real keyframes
+    olds = [int(x) for x in a.old.split(",")]
+    store = lmono_amd.KeyFrames(ctx, cam, pat, max(olds) + 1, a.max_keypoints)
+    seeds = []
+    for v in range(4):
+        store.add(variants[v][0], uv)
+        seeds.append(store.get(v))
+    store.clear()
+    for o in range(max(olds)):
+        g = seeds[o % 4]
+        store.load(g["keypoints"], g["norm"], g["descriptors"])
+    cur, _ = store.add(variants[0][1], uv)
+    for n_old in olds:
+        idx = list(range(n_old))
+        ms, counts = [], None
+        for f in range(n_img):
+            t0 = time.perf_counter()
+            counts = store.match(cur, idx)["counts"]
+            dt = (time.perf_counter() - t0) * 1e3
+            if f >= a.warmup:
+                ms.append(dt)
+        ms = np.array(ms)
+        pairs = float(a.window) * float(sum(len(seeds[o % 4]["keypoints"]) for o in range(n_old)))
+        run = {"old_keyframes": n_old, "ms_per_call_median": float(np.median(ms)), "ms_per_call_min": float(ms.min()),
+               "matches_per_s": float(n_old * 1e3 / np.median(ms)), "descriptor_pairs_per_s": float(pairs * 1e3 / np.median(ms)),
+               "matched_mean": float(np.mean(counts))}
+        if n_old == max(olds) and not a.no_kernels:
+            from torch.profiler import ProfilerActivity, profile
+            with profile(activities=[ProfilerActivity.CUDA, ProfilerActivity.CPU]) as prof:
+                store.match(cur, idx)
+                torch.cuda.synchronize()
+            run["kernels_us"] = _kernel_times(prof)
+        out["match"].append(run)
+    store.close()
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()

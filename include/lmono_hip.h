@@ -275,7 +275,20 @@ int lmono_debug_bounds(lmono_ctx *, unsigned long long *out4);
  * lmono_outlier_scores: Estimator::outliersRejection's statistic FACTOR_WEIGHT * mean reprojection error
  *   (src/image_process/Estimator.cc:104-190); -1 for tracks shorter than track_cnt.
  * lmono_shift_depth: FeatureManager::removeBackShiftDepth as called by Estimator::slideWindowOld
- *   (FeatureManager.cc:540-590, Estimator.cc:744-763) for the tracks anchored at the dropped frame.               */
+ *   (FeatureManager.cc:540-590, Estimator.cc:744-763) for the tracks anchored at the dropped frame.
+ * Malformed descriptors are refused on the host, before anything is uploaded or launched, with LMONO_EINVAL, a message in
+ * lmono_last_error and the output arrays untouched (the kernels index Rs / Ps / pts by these arrays without a check of their own):
+ *   - feat_off[0] != 0, or feat_off / obs_off not ascending (equal neighbours -- an empty window, a track without
+ *     observations -- are fine), or obs_off[0] < 0;
+ *   - start_frame[f] < 0, or start_frame[f] + nobs_f > 11 for a track with nobs_f > 0 observations (a window has 11 frames);
+ *   - track_cnt < 1;
+ *   - lmono_triangulate only: window_size outside 0..10, refine_max_iter > LMONO_FEAT_MAX_REFINE_ITER (the reference runs 50;
+ *     refine_max_iter < 0 means "linear step only": solve_flag_h is then not written);
+ *   - lmono_shift_depth: n < 0;  lmono_shift_depth_batch: track_off_h[0] != 0 or track_off_h not ascending.
+ * Degenerate numerics are NOT refused, they are the reference's: lmono_outlier_scores of a track with a single observation (possible
+ * only under track_cnt = 1) has no reprojection to average and returns the 0 / 0 of its mean, NaN; a depth <= 0 or a reprojected
+ * z of 0 gives the score the division gives (finite, inf or NaN); lmono_shift_depth* returns -1 for every shifted z <= 0.    */
+#define LMONO_FEAT_MAX_REFINE_ITER 1000
 int lmono_triangulate(lmono_ctx *, int n_windows, const int *feat_off_h, const double *Rs_h, const double *Ps_h, const double *tlc_h,
                       const int *start_frame_h, const int *obs_off_h, const double *pts_h, double *depth_h, int *solve_flag_h,
                       int track_cnt, int window_size, double factor_weight, int refine_max_iter);

@@ -291,7 +291,8 @@ __global__ __launch_bounds__(256) void k_depth_refine(FeatBatch B)
 // other in every evaluation: ~110 us per Estimator frame for ~150 tracks, a chain of ~3000 dependent fp64 instructions per thread and evaluation on a
 // fraction of one compute unit.  Here every (track, observation) pair of the window is an ITEM; an evaluation computes the items side by side on 1024
 // threads, leaves (cost, h, g) of each in LDS, and the track's thread adds its items in observation order -- the same terms in the same order as the walk,
-// so every sum, every decision and every result is the same bit for bit.  Windows above kDrItems items or 1024 tracks take the kernel above.
+// so a track's sums are the same bit for bit; the block sums over tracks group as the kernel above groups them while a window has <= 256 tracks (same
+// bits, asserted), differently above that (agreement at 1e-9 of the inverse depth asserted; a 600-track window still gave equal bytes on an MI355X).  Windows above kDrItems observations or 1024 tracks take the kernel above.
 constexpr int kDrT = 1024, kDrItems = 3072;
 __global__ __launch_bounds__(kDrT) void k_depth_refine_items(FeatBatch B)
 {

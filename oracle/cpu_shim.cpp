@@ -8,6 +8,7 @@
 // Only tests/ and bench.py's cpu_baseline leg build or run it; nothing under lmono_amd/ links it, and the product still fails without a GPU.
 // PARITY UNPINNED like the rest of oracle/ (DESIGN.md section 2).
 #include "../include/lmono_hip.h"
+#include "../lmono_amd/csrc/feat_check.hpp"      // the descriptor checks of the per-track entry points: the HIP library's own, plain C++
 
 #include <cstdint>
 #include <cstring>
@@ -107,15 +108,25 @@ int lmono_ba_batch_read(lmono_ctx *, lmono_ba_batch *b, double *poses_h, double 
     return LMONO_OK;
 }
 
-int lmono_triangulate(lmono_ctx *, int n_windows, const int *feat_off_h, const double *Rs_h, const double *Ps_h, const double *tlc_h,
+// the per-track entry points refuse what liblmono_hip.so refuses (feat_abi.hip: feat_setup), before they touch an output array
+static int feat_refuse(lmono_ctx *c, const char *bad)
+{
+    if (c) c->err = std::string("per-feature kernels: ") + bad;
+    return LMONO_EINVAL;
+}
+
+int lmono_triangulate(lmono_ctx *c, int n_windows, const int *feat_off_h, const double *Rs_h, const double *Ps_h, const double *tlc_h,
                       const int *start_frame_h, const int *obs_off_h, const double *pts_h, double *depth_h, int *solve_flag_h,
                       int track_cnt, int window_size, double factor_weight, int refine_max_iter)
 {
+    if (!c || n_windows <= 0 || !feat_off_h || !Rs_h || !Ps_h || !tlc_h || !start_frame_h || !obs_off_h || !pts_h || !depth_h) return LMONO_EINVAL;
+    const char *bad = lmono::feat_check_tracks(n_windows, feat_off_h, start_frame_h, obs_off_h, track_cnt);
+    if (!bad) bad = lmono::feat_check_refine(window_size, refine_max_iter, LMONO_FEAT_MAX_REFINE_ITER);
+    if (bad) return feat_refuse(c, bad);
     for (int w = 0; w < n_windows; w++) {
         const int f0 = feat_off_h[w], nf = feat_off_h[w + 1] - f0;
         if (nf <= 0) continue;
         lo_triangulate_init(Rs_h + (size_t)w * 99, Ps_h + (size_t)w * 33, tlc_h + (size_t)w * 16, nf, start_frame_h + f0, obs_off_h + f0, pts_h, depth_h + f0, track_cnt);
-        if (solve_flag_h) for (int f = 0; f < nf; f++) solve_flag_h[f0 + f] = 0;
         if (refine_max_iter >= 0) {
             std::vector<int32_t> flag((size_t)nf, 0);
             lo_depth_refine(Rs_h + (size_t)w * 99, Ps_h + (size_t)w * 33, tlc_h + (size_t)w * 16, nf, start_frame_h + f0, obs_off_h + f0, pts_h, depth_h + f0,
@@ -125,10 +136,12 @@ int lmono_triangulate(lmono_ctx *, int n_windows, const int *feat_off_h, const d
     }
     return LMONO_OK;
 }
-int lmono_outlier_scores(lmono_ctx *, int n_windows, const int *feat_off_h, const double *Rs_h, const double *Ps_h, const double *tlc_h,
+int lmono_outlier_scores(lmono_ctx *c, int n_windows, const int *feat_off_h, const double *Rs_h, const double *Ps_h, const double *tlc_h,
                          const int *start_frame_h, const int *obs_off_h, const double *pts_h, const double *depth_h,
                          int track_cnt, double factor_weight, double *score_h)
 {
+    if (!c || !score_h || n_windows <= 0 || !feat_off_h || !Rs_h || !Ps_h || !tlc_h || !start_frame_h || !obs_off_h || !pts_h || !depth_h) return LMONO_EINVAL;
+    if (const char *bad = lmono::feat_check_tracks(n_windows, feat_off_h, start_frame_h, obs_off_h, track_cnt)) return feat_refuse(c, bad);
     for (int w = 0; w < n_windows; w++) {
         const int f0 = feat_off_h[w], nf = feat_off_h[w + 1] - f0;
         if (nf > 0) lo_outlier_scores(Rs_h + (size_t)w * 99, Ps_h + (size_t)w * 33, tlc_h + (size_t)w * 16, nf, start_frame_h + f0, obs_off_h + f0, pts_h, depth_h + f0,
@@ -136,14 +149,18 @@ int lmono_outlier_scores(lmono_ctx *, int n_windows, const int *feat_off_h, cons
     }
     return LMONO_OK;
 }
-int lmono_shift_depth(lmono_ctx *, const double *back_R0, const double *back_P0, const double *R1, const double *P1, const double *tlc,
+int lmono_shift_depth(lmono_ctx *c, const double *back_R0, const double *back_P0, const double *R1, const double *P1, const double *tlc,
                       int n, const double *pt_i_h, const double *depth_h, double *depth_out_h)
 {
+    if (!c || !back_R0 || !back_P0 || !R1 || !P1 || !tlc || n < 0 || !pt_i_h || !depth_h || !depth_out_h) return LMONO_EINVAL;
     if (n > 0) lo_shift_depth(back_R0, back_P0, R1, P1, tlc, n, pt_i_h, depth_h, depth_out_h);
     return LMONO_OK;
 }
-int lmono_shift_depth_batch(lmono_ctx *, int n_windows, const double *frames_h, const int *track_off_h, const double *pt_i_h, const double *depth_h, double *depth_out_h)
+int lmono_shift_depth_batch(lmono_ctx *c, int n_windows, const double *frames_h, const int *track_off_h, const double *pt_i_h, const double *depth_h, double *depth_out_h)
 {
+    if (!c || n_windows <= 0 || !frames_h || !track_off_h) return LMONO_EINVAL;
+    if (const char *bad = lmono::feat_check_offsets(n_windows, track_off_h)) { c->err = std::string("lmono_shift_depth_batch: ") + bad; return LMONO_EINVAL; }
+    if (track_off_h[n_windows] > 0 && (!pt_i_h || !depth_h || !depth_out_h)) return LMONO_EINVAL;
     for (int w = 0; w < n_windows; w++) {
         const int f0 = track_off_h[w], n = track_off_h[w + 1] - f0;
         const double *fr = frames_h + (size_t)w * 40;

@@ -131,9 +131,12 @@ static double refine_eval(const double *Rs, const double *Ps, const double *tlc,
 }
 
 /* depth in/out (estimated_depth); solve_flag out (0 untouched, 1 ok, 2 failed), FeatureManager.cc:197-251 + setDepth */
-void lo_depth_refine(const double *Rs, const double *Ps, const double *tlc, int n_feat, const int32_t *start_frame, const int32_t *obs_off,
-                     const double *pts, double *depth, int32_t *solve_flag, int track_cnt, int window_size, double weight, int max_iter)
+/* info (may be NULL): [0] why the loop ended -- 0 gradient tolerance, 1 iteration limit, 2 five invalid steps, 3 parameter tolerance, 4 function
+ * tolerance, 5 radius <= 1e-32 --, [1] iterations, [2] the trust-region radius at the end.  A test classifies its windows by it. */
+static void depth_refine(const double *Rs, const double *Ps, const double *tlc, int n_feat, const int32_t *start_frame, const int32_t *obs_off,
+                         const double *pts, double *depth, int32_t *solve_flag, int track_cnt, int window_size, double weight, int max_iter, double *info)
 {
+    int why = 0;
     double *x = (double *)calloc((size_t)(n_feat + 1), sizeof(double)), *cand = (double *)malloc(sizeof(double) * (size_t)(n_feat + 1));
     double *h = (double *)malloc(sizeof(double) * (size_t)(n_feat + 1)), *g = (double *)malloc(sizeof(double) * (size_t)(n_feat + 1));
     double *scale = (double *)malloc(sizeof(double) * (size_t)(n_feat + 1)), *diag = (double *)malloc(sizeof(double) * (size_t)(n_feat + 1));
@@ -154,7 +157,7 @@ void lo_depth_refine(const double *Rs, const double *Ps, const double *tlc, int 
     double x_norm = 0, gmax = 0;
     for (int f = 0; f < n_feat; f++) if (act[f]) { x_norm += x[f] * x[f]; scale[f] = 1.0 / (1.0 + sqrt(h[f])); gmax = fmax(gmax, fabs(g[f])); }
     x_norm = sqrt(x_norm);
-    if (gmax > gradient_tol) while (iter < max_iter) {
+    if (gmax > gradient_tol) for (why = 1; iter < max_iter; ) {
         iter++;
         double model = 0;
         int ok = 1;
@@ -168,14 +171,14 @@ void lo_depth_refine(const double *Rs, const double *Ps, const double *tlc, int 
             step[f] = s;
             model += -(s * gs + 0.5 * s * hs * s);
         }
-        if (!ok || !(model > 0.0)) { if (++invalid >= 5) break; radius *= 0.5; reuse = 1; continue; }
+        if (!ok || !(model > 0.0)) { if (++invalid >= 5) { why = 2; break; } radius *= 0.5; reuse = 1; continue; }
         invalid = 0;
         double sn = 0;
         for (int f = 0; f < n_feat; f++) { cand[f] = x[f] + step[f] * scale[f]; if (act[f]) sn += (cand[f] - x[f]) * (cand[f] - x[f]); }
         sn = sqrt(sn);
         const double cc = refine_eval(Rs, Ps, tlc, n_feat, start_frame, obs_off, pts, cand, track_cnt, window_size, weight, NULL, NULL);
-        if (sn <= parameter_tol * (x_norm + parameter_tol)) break;
-        if (fabs(x_cost - cc) <= function_tol * x_cost) break;
+        if (sn <= parameter_tol * (x_norm + parameter_tol)) { why = 3; break; }
+        if (fabs(x_cost - cc) <= function_tol * x_cost) { why = 4; break; }
         const double rel = (x_cost - cc) / model;
         if (rel > min_rel) {
             memcpy(x, cand, sizeof(double) * (size_t)n_feat);
@@ -189,10 +192,11 @@ void lo_depth_refine(const double *Rs, const double *Ps, const double *tlc, int 
             dec = 2.0; reuse = 0;
             gmax = 0;
             for (int f = 0; f < n_feat; f++) if (act[f]) gmax = fmax(gmax, fabs(g[f]));
-            if (gmax <= gradient_tol) break;
+            if (gmax <= gradient_tol) { why = 0; break; }
         } else { radius /= dec; dec *= 2.0; reuse = 1; }
-        if (radius <= 1e-32) break;
+        if (radius <= 1e-32) { why = 5; break; }
     }
+    if (info) { info[0] = why; info[1] = iter; info[2] = radius; }
     for (int f = 0; f < n_feat; f++) {
         const int nobs = obs_off[f + 1] - obs_off[f];
         solve_flag[f] = 0;
@@ -201,6 +205,17 @@ void lo_depth_refine(const double *Rs, const double *Ps, const double *tlc, int 
         solve_flag[f] = (depth[f] < 0.1 || depth[f] > 300) ? 2 : 1;
     }
     free(x); free(cand); free(h); free(g); free(scale); free(diag); free(step); free(act);
+}
+
+void lo_depth_refine(const double *Rs, const double *Ps, const double *tlc, int n_feat, const int32_t *start_frame, const int32_t *obs_off,
+                     const double *pts, double *depth, int32_t *solve_flag, int track_cnt, int window_size, double weight, int max_iter)
+{
+    depth_refine(Rs, Ps, tlc, n_feat, start_frame, obs_off, pts, depth, solve_flag, track_cnt, window_size, weight, max_iter, NULL);
+}
+void lo_depth_refine_info(const double *Rs, const double *Ps, const double *tlc, int n_feat, const int32_t *start_frame, const int32_t *obs_off,
+                          const double *pts, double *depth, int32_t *solve_flag, int track_cnt, int window_size, double weight, int max_iter, double *info)
+{
+    depth_refine(Rs, Ps, tlc, n_feat, start_frame, obs_off, pts, depth, solve_flag, track_cnt, window_size, weight, max_iter, info);
 }
 
 /* score[f] = FACTOR_WEIGHT * mean_j ||reprojection error||, -1 for features with fewer than track_cnt observations */

@@ -359,8 +359,10 @@ def _feat_args(Rs, Ps, tlc, start, off, pts):
             np.ascontiguousarray(off, np.int32), np.ascontiguousarray(pts, np.float64).reshape(-1, 2))
 
 
-def triangulate(Rs, Ps, tlc, start, off, pts, depth, track_cnt=3, window_size=10, weight=1500.0, refine_iters=50):
-    """FeatureManager::triangulate: returns (depth_after_init, depth_after_refine, solve_flag)."""
+def triangulate(Rs, Ps, tlc, start, off, pts, depth, track_cnt=3, window_size=10, weight=1500.0, refine_iters=50, info=None):
+    """FeatureManager::triangulate: returns (depth_after_init, depth_after_refine, solve_flag).  info: a float64 array [3] that receives why the
+    refinement ended (0 gradient tolerance, 1 iteration limit, 2 five invalid steps, 3 parameter tolerance, 4 function tolerance, 5 radius), its
+    iterations and its final radius."""
     Rs, Ps, tlc, start, off, pts = _feat_args(Rs, Ps, tlc, start, off, pts)
     n = len(start)
     d = np.ascontiguousarray(depth, np.float64).copy()
@@ -369,9 +371,9 @@ def triangulate(Rs, Ps, tlc, start, off, pts, depth, track_cnt=3, window_size=10
     d0 = d.copy()
     flag = np.zeros(n, np.int32)
     if refine_iters >= 0:
-        lib().lo_depth_refine(_fp(Rs, C.c_double), _fp(Ps, C.c_double), _fp(tlc, C.c_double), C.c_int(n), _fp(start, C.c_int32),
-                              _fp(off, C.c_int32), _fp(pts, C.c_double), _fp(d, C.c_double), _fp(flag, C.c_int32), C.c_int(track_cnt),
-                              C.c_int(window_size), C.c_double(weight), C.c_int(refine_iters))
+        lib().lo_depth_refine_info(_fp(Rs, C.c_double), _fp(Ps, C.c_double), _fp(tlc, C.c_double), C.c_int(n), _fp(start, C.c_int32),
+                                   _fp(off, C.c_int32), _fp(pts, C.c_double), _fp(d, C.c_double), _fp(flag, C.c_int32), C.c_int(track_cnt),
+                                   C.c_int(window_size), C.c_double(weight), C.c_int(refine_iters), _fp(info, C.c_double) if info is not None else None)
     return d0, d, flag
 
 

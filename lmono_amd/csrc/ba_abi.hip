@@ -26,32 +26,28 @@ extern "C" int lmono_factor_eval_blocks(lmono_ctx *c, int kind, int count, const
     const FactorDims d = factor_dims(kind);
     double *p = nullptr, *cn = nullptr, *inf = nullptr, *r = nullptr, *J = nullptr;
     unsigned char *mk = nullptr;
-    int rc = LMONO_OK;
-    auto cleanup = [&]() { (void)hipFree(p); (void)hipFree(cn); (void)hipFree(inf); (void)hipFree(r); (void)hipFree(J); (void)hipFree(mk); };
-#define TRYF(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { c->err = std::string(#expr) + ": " + hipGetErrorString(e_); cleanup(); return LMONO_ENODEV; } } while (0)
-    TRYF(hipMalloc((void **)&p, sizeof(double) * d.np * count));
-    TRYF(hipMalloc((void **)&cn, sizeof(double) * d.nc * count));
-    TRYF(hipMalloc((void **)&inf, sizeof(double) * d.ni));
-    TRYF(hipMalloc((void **)&r, sizeof(double) * d.nr * count));
-    if (J_h) TRYF(hipMalloc((void **)&J, sizeof(double) * d.nj * count));
-    if (J_h && block_mask_h) {
-        TRYF(hipMalloc((void **)&mk, (size_t)count));
-        TRYF(hipMemcpy(mk, block_mask_h, (size_t)count, hipMemcpyHostToDevice));
-        // blocks the caller did not ask for keep the caller's bytes: start from the caller's J
-        TRYF(hipMemcpy(J, J_h, sizeof(double) * d.nj * count, hipMemcpyHostToDevice));
-    }
-    TRYF(hipMemcpy(p, params_h, sizeof(double) * d.np * count, hipMemcpyHostToDevice));
-    TRYF(hipMemcpy(cn, consts_h, sizeof(double) * d.nc * count, hipMemcpyHostToDevice));
-    TRYF(hipMemcpy(inf, info_h, sizeof(double) * d.ni, hipMemcpyHostToDevice));
-    rc = lmono_factor_eval_blocks_d(c, kind, count, p, cn, inf, r, J, mk);
-    if (rc == LMONO_OK) {
-        TRYF(hipStreamSynchronize(c->stream));
-        TRYF(hipMemcpy(r_h, r, sizeof(double) * d.nr * count, hipMemcpyDeviceToHost));
-        if (J_h) TRYF(hipMemcpy(J_h, J, sizeof(double) * d.nj * count, hipMemcpyDeviceToHost));
-    }
-#undef TRYF
-    cleanup();
-    return rc;
+    DevOwner mem;               // the call's six buffers: freed on every return
+    // every failure below answers LMONO_ENODEV with "<the HIP call>: <its error>"
+    auto bad = [&](hipError_t e, const char *call) { if (e != hipSuccess) c->err = std::string(call) + ": " + hipGetErrorString(e); return e != hipSuccess; };
+    auto no_mem = [&](bool allocated, const char *call) { return bad(allocated ? hipSuccess : hipGetLastError(), call); };
+    if (no_mem(mem.alloc(p, (size_t)d.np * count), "hipMalloc((void **)&p, sizeof(double) * d.np * count)") ||
+        no_mem(mem.alloc(cn, (size_t)d.nc * count), "hipMalloc((void **)&cn, sizeof(double) * d.nc * count)") ||
+        no_mem(mem.alloc(inf, (size_t)d.ni), "hipMalloc((void **)&inf, sizeof(double) * d.ni)") ||
+        no_mem(mem.alloc(r, (size_t)d.nr * count), "hipMalloc((void **)&r, sizeof(double) * d.nr * count)") ||
+        (J_h && no_mem(mem.alloc(J, (size_t)d.nj * count), "hipMalloc((void **)&J, sizeof(double) * d.nj * count)"))) return LMONO_ENODEV;
+    // a mask: blocks the caller did not ask for keep the caller's bytes, so J starts from the caller's J
+    if (J_h && block_mask_h &&
+        (no_mem(mem.alloc(mk, (size_t)count), "hipMalloc((void **)&mk, (size_t)count)") ||
+         bad(hipMemcpy(mk, block_mask_h, (size_t)count, hipMemcpyHostToDevice), "hipMemcpy(mk, block_mask_h, (size_t)count, hipMemcpyHostToDevice)") ||
+         bad(hipMemcpy(J, J_h, sizeof(double) * d.nj * count, hipMemcpyHostToDevice), "hipMemcpy(J, J_h, sizeof(double) * d.nj * count, hipMemcpyHostToDevice)"))) return LMONO_ENODEV;
+    if (bad(hipMemcpy(p, params_h, sizeof(double) * d.np * count, hipMemcpyHostToDevice), "hipMemcpy(p, params_h, sizeof(double) * d.np * count, hipMemcpyHostToDevice)") ||
+        bad(hipMemcpy(cn, consts_h, sizeof(double) * d.nc * count, hipMemcpyHostToDevice), "hipMemcpy(cn, consts_h, sizeof(double) * d.nc * count, hipMemcpyHostToDevice)") ||
+        bad(hipMemcpy(inf, info_h, sizeof(double) * d.ni, hipMemcpyHostToDevice), "hipMemcpy(inf, info_h, sizeof(double) * d.ni, hipMemcpyHostToDevice)")) return LMONO_ENODEV;
+    if (int rc = lmono_factor_eval_blocks_d(c, kind, count, p, cn, inf, r, J, mk)) return rc;
+    if (bad(hipStreamSynchronize(c->stream), "hipStreamSynchronize(c->stream)") ||
+        bad(hipMemcpy(r_h, r, sizeof(double) * d.nr * count, hipMemcpyDeviceToHost), "hipMemcpy(r_h, r, sizeof(double) * d.nr * count, hipMemcpyDeviceToHost)") ||
+        (J_h && bad(hipMemcpy(J_h, J, sizeof(double) * d.nj * count, hipMemcpyDeviceToHost), "hipMemcpy(J_h, J, sizeof(double) * d.nj * count, hipMemcpyDeviceToHost)"))) return LMONO_ENODEV;
+    return LMONO_OK;
 }
 
 extern "C" int lmono_factor_eval(lmono_ctx *c, int kind, int count, const double *params_h, const double *consts_h,

@@ -37,6 +37,15 @@ struct ColourCam {
     unsigned char mask[kMaxMorphK * kMaxMorphK];
 };
 
+// the pinhole model of a lmono_camera: intrinsics, their inverse, whether it distorts (ksize, blur and the mask are the map builder's to set)
+static void colour_cam_from(const lmono_camera &cam, ColourCam &k)
+{
+    k.w = cam.width; k.h = cam.height;
+    k.fx = cam.fx; k.fy = cam.fy; k.cx = cam.cx; k.cy = cam.cy; k.k1 = cam.k1; k.k2 = cam.k2; k.p1 = cam.p1; k.p2 = cam.p2;
+    k.ik11 = 1.0 / k.fx; k.ik13 = -k.cx / k.fx; k.ik22 = 1.0 / k.fy; k.ik23 = -k.cy / k.fy;
+    k.distort = !(k.k1 == 0.0 && k.k2 == 0.0 && k.p1 == 0.0 && k.p2 == 0.0);
+}
+
 struct ColourJob {
     ColourCam cam;
     const float4 *cloud;

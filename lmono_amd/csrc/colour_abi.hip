@@ -9,7 +9,7 @@ struct lmono_map_builder {
     int64_t map_cap = 0, map_n = 0;      // rgb_map (world frame), device resident
     int last_n = 0;                      // cloud size of the last frame
     int64_t last_off = 0;                // where the last frame's world cloud starts in rgb_map
-    std::vector<void *> allocs;
+    DevOwner mem;
     float4 *cloud = nullptr;             // staging of the host-buffer entry
     unsigned char *bgr = nullptr;
     unsigned int *key = nullptr;
@@ -23,21 +23,7 @@ struct lmono_map_builder {
     int jobs_cap = 0;
 };
 
-template <typename T> static bool mb_alloc(lmono_map_builder *m, T *&p, size_t n)
-{
-    void *q = nullptr;
-    if (hipMalloc(&q, (n ? n : 1) * sizeof(T)) != hipSuccess) return false;
-    m->allocs.push_back(q);
-    p = (T *)q;
-    return true;
-}
-
-extern "C" void lmono_map_builder_destroy(lmono_map_builder *m)
-{
-    if (!m) return;
-    for (void *p : m->allocs) (void)hipFree(p);
-    delete m;
-}
+extern "C" void lmono_map_builder_destroy(lmono_map_builder *m) { delete m; }
 
 extern "C" lmono_map_builder *lmono_map_builder_create(lmono_ctx *c, const lmono_camera *cam, int max_cloud_points, int64_t map_capacity_points)
 {
@@ -52,10 +38,7 @@ extern "C" lmono_map_builder *lmono_map_builder_create(lmono_ctx *c, const lmono
     lmono_map_builder *m = new lmono_map_builder();
     m->ctx = c;
     ColourCam &k = m->cam;
-    k.w = cam->width; k.h = cam->height;
-    k.fx = cam->fx; k.fy = cam->fy; k.cx = cam->cx; k.cy = cam->cy; k.k1 = cam->k1; k.k2 = cam->k2; k.p1 = cam->p1; k.p2 = cam->p2;
-    k.ik11 = 1.0 / k.fx; k.ik13 = -k.cx / k.fx; k.ik22 = 1.0 / k.fy; k.ik23 = -k.cy / k.fy;
-    k.distort = !(k.k1 == 0.0 && k.k2 == 0.0 && k.p1 == 0.0 && k.p2 == 0.0);
+    colour_cam_from(*cam, k);
     k.ksize = cam->kernel_size; k.blur = cam->blur_type == 0 ? 0 : 1;
     {   // cv::getStructuringElement: FULL -> MORPH_RECT, CROSS -> MORPH_CROSS, anything else -> MORPH_ELLIPSE (Map_Builder.cc:343-355)
         const int K = k.ksize, r = K / 2;
@@ -77,8 +60,8 @@ extern "C" lmono_map_builder *lmono_map_builder_create(lmono_ctx *c, const lmono
     m->max_pts = max_cloud_points;
     m->map_cap = map_capacity_points;
     const size_t np = (size_t)k.w * k.h;
-    bool ok = mb_alloc(m, m->cloud, (size_t)max_cloud_points) && mb_alloc(m, m->bgr, np * 3) && mb_alloc(m, m->key, np) && mb_alloc(m, m->depth, np) &&
-              mb_alloc(m, m->row_cnt, (size_t)k.h) && mb_alloc(m, m->cam_out, np) && mb_alloc(m, m->map, (size_t)map_capacity_points) && mb_alloc(m, m->tab, 1);
+    bool ok = m->mem.alloc(m->cloud, (size_t)max_cloud_points) && m->mem.alloc(m->bgr, np * 3) && m->mem.alloc(m->key, np) && m->mem.alloc(m->depth, np) &&
+              m->mem.alloc(m->row_cnt, (size_t)k.h) && m->mem.alloc(m->cam_out, np) && m->mem.alloc(m->map, (size_t)map_capacity_points) && m->mem.alloc(m->tab, 1);
     if (ok) {
         // cv::bilateralFilter(src, dst, 5, 1.5, 2.0) weight tables (Map_Builder.cc:398): d = 5 -> radius 2, taps with r <= radius in row-major order
         BilateralTab t{};
@@ -128,18 +111,14 @@ extern "C" int lmono_associate_to_map_batch(lmono_ctx *c, int n_streams, lmono_m
 {
     if (!c || n_streams <= 0 || !mbs || !xyzi_d || !n_points || !transforms || !bgr_d || !q_wc || !t_wc) return LMONO_EINVAL;
     for (int s = 0; s < n_streams; s++) {
-        if (!mbs[s] || mbs[s]->ctx != c || !bgr_d[s] || n_points[s] < 0 || n_points[s] >= (1 << 24) || (n_points[s] > 0 && !xyzi_d[s])) { c->err = "lmono_associate_to_map_batch: bad stream arguments"; return LMONO_EINVAL; }
-        for (int u = 0; u < s; u++) if (mbs[u] == mbs[s]) { c->err = "lmono_associate_to_map_batch: map builders must be distinct"; return LMONO_EINVAL; }
+        const int fault = batch_handle_fault(c, s, mbs);
+        if (fault == kHandleForeign || !bgr_d[s] || n_points[s] < 0 || n_points[s] >= (1 << 24) || (n_points[s] > 0 && !xyzi_d[s])) { c->err = "lmono_associate_to_map_batch: bad stream arguments"; return LMONO_EINVAL; }
+        if (fault == kHandleRepeated) { c->err = "lmono_associate_to_map_batch: map builders must be distinct"; return LMONO_EINVAL; }
         if (mbs[s]->map_n + (int64_t)mbs[s]->cam.w * mbs[s]->cam.h > mbs[s]->map_cap) { c->err = "lmono_associate_to_map_batch: rgb_map is full (clear it or create it larger)"; return LMONO_ECAPACITY; }
     }
     lmono_map_builder *lead = mbs[0];
-    if (lead->jobs_cap < n_streams) {
-        int cap = std::max(lead->jobs_cap, 1);
-        while (cap < n_streams) cap <<= 1;
-        ColourJob *jb = nullptr; int *rs = nullptr;
-        if (!mb_alloc(lead, jb, (size_t)cap) || !mb_alloc(lead, rs, (size_t)cap * 2)) { c->err = "lmono_associate_to_map_batch: job table allocation failed"; return LMONO_ENOMEM; }
-        lead->jobs = jb; lead->results = rs; lead->jobs_cap = cap;
-    }
+    // an outgrown table is freed at once: every call that launched anything and returned LMONO_OK ended synchronised, and hipFree waits for the device in any case
+    if (!job_table(lead->mem, lead->jobs, lead->results, lead->jobs_cap, n_streams, 2)) { c->err = "lmono_associate_to_map_batch: job table allocation failed"; return LMONO_ENOMEM; }
     std::vector<ColourJob> jobs((size_t)n_streams);
     int max_n = 0, max_tiles = 0, max_h = 0;
     std::vector<int> ks;

@@ -18,7 +18,7 @@ struct lmono_keyframes {
     float2 *win_uv = nullptr;                            // [max_kf][512]
     uint32_t *win_desc = nullptr;                        // [max_kf][512][8]
     std::vector<int> n_kp_h, n_win_h;                    // per stored keyframe
-    std::vector<void *> allocs;
+    DevOwner mem;
     // job table + results of a batch led by this store
     KfJob *jobs = nullptr;
     int *res = nullptr;
@@ -31,28 +31,7 @@ struct lmono_keyframes {
     float2 *m_uv = nullptr, *m_norm = nullptr;
 };
 
-template <typename T> static bool kf_alloc(lmono_keyframes *k, T *&p, size_t n)
-{
-    void *q = nullptr;
-    if (hipMalloc(&q, (n ? n : 1) * sizeof(T)) != hipSuccess) return false;
-    k->allocs.push_back(q);
-    p = (T *)q;
-    return true;
-}
-template <typename T> static void kf_release(lmono_keyframes *k, T *&p)      // nothing that reads p is in flight: every call ends synchronised
-{
-    if (!p) return;
-    (void)hipFree((void *)p);
-    k->allocs.erase(std::find(k->allocs.begin(), k->allocs.end(), (void *)p));
-    p = nullptr;
-}
-
-extern "C" void lmono_keyframes_destroy(lmono_keyframes *k)
-{
-    if (!k) return;
-    for (void *p : k->allocs) (void)hipFree(p);
-    delete k;
-}
+extern "C" void lmono_keyframes_destroy(lmono_keyframes *k) { delete k; }
 
 extern "C" int lmono_keyframes_clear(lmono_ctx *c, lmono_keyframes *k)
 {
@@ -82,30 +61,15 @@ extern "C" lmono_keyframes *lmono_keyframes_create(lmono_ctx *c, const lmono_cam
     lmono_keyframes *k = new lmono_keyframes();
     k->ctx = c;
     k->w = cam->width; k->h = cam->height; k->max_kf = max_keyframes; k->max_kp = max_keypoints; k->thr = fast_threshold ? fast_threshold : 20;
-    ColourCam &m = k->cam;
-    m.w = cam->width; m.h = cam->height;
-    m.fx = cam->fx; m.fy = cam->fy; m.cx = cam->cx; m.cy = cam->cy; m.k1 = cam->k1; m.k2 = cam->k2; m.p1 = cam->p1; m.p2 = cam->p2;
-    m.ik11 = 1.0 / m.fx; m.ik13 = -m.cx / m.fx; m.ik22 = 1.0 / m.fy; m.ik23 = -m.cy / m.fy;
-    m.distort = !(m.k1 == 0.0 && m.k2 == 0.0 && m.p1 == 0.0 && m.p2 == 0.0);
+    colour_cam_from(*cam, k->cam);
+    DevOwner &m = k->mem;
     const size_t np = (size_t)k->w * k->h, slots = (size_t)max_keyframes, per = (size_t)max_keypoints;
-    bool ok = kf_alloc(k, k->image, np * 3) && kf_alloc(k, k->blur, np) && kf_alloc(k, k->score, np) && kf_alloc(k, k->row_cnt, (size_t)k->h) && kf_alloc(k, k->row_off, (size_t)k->h) &&
-              kf_alloc(k, k->pat, 256) && kf_alloc(k, k->n_kp_d, slots) && kf_alloc(k, k->kp, slots * per) && kf_alloc(k, k->norm, slots * per) && kf_alloc(k, k->desc, slots * per * 8) &&
-              kf_alloc(k, k->win_uv, slots * kKfMaxWin) && kf_alloc(k, k->win_desc, slots * kKfMaxWin * 8);
+    bool ok = m.alloc(k->image, np * 3) && m.alloc(k->blur, np) && m.alloc(k->score, np) && m.alloc(k->row_cnt, (size_t)k->h) && m.alloc(k->row_off, (size_t)k->h) &&
+              m.alloc(k->pat, 256) && m.alloc(k->n_kp_d, slots) && m.alloc(k->kp, slots * per) && m.alloc(k->norm, slots * per) && m.alloc(k->desc, slots * per * 8) &&
+              m.alloc(k->win_uv, slots * kKfMaxWin) && m.alloc(k->win_desc, slots * kKfMaxWin * 8);
     ok = ok && hipMemcpy(k->pat, pat, sizeof(pat), hipMemcpyHostToDevice) == hipSuccess && hipMemset(k->n_kp_d, 0, slots * sizeof(int)) == hipSuccess;
     if (!ok) { c->err = "lmono_keyframes_create: device allocation failed"; lmono_keyframes_destroy(k); return nullptr; }
     return k;
-}
-
-static int kf_job_table(lmono_ctx *c, lmono_keyframes *lead, int n)
-{
-    if (lead->jobs_cap >= n) return LMONO_OK;
-    int cap = std::max(lead->jobs_cap, 1);
-    while (cap < n) cap <<= 1;
-    kf_release(lead, lead->jobs); kf_release(lead, lead->res);
-    lead->jobs_cap = 0;
-    if (!kf_alloc(lead, lead->jobs, (size_t)cap) || !kf_alloc(lead, lead->res, (size_t)cap * 2)) { c->err = "lmono_keyframes_add_batch: job table allocation failed"; return LMONO_ENOMEM; }
-    lead->jobs_cap = cap;
-    return LMONO_OK;
 }
 
 extern "C" int lmono_keyframes_add_batch(lmono_ctx *c, int n, lmono_keyframes *const *kfs, const uint8_t *const *image_d, int format, const int *n_window,
@@ -113,14 +77,15 @@ extern "C" int lmono_keyframes_add_batch(lmono_ctx *c, int n, lmono_keyframes *c
 {
     if (!c || n <= 0 || !kfs || !image_d || !n_window || !window_uv_h || (format != LMONO_TRACK_GREY8 && format != LMONO_TRACK_BGR8)) return LMONO_EINVAL;
     for (int s = 0; s < n; s++) {
-        if (!kfs[s] || kfs[s]->ctx != c || !image_d[s] || n_window[s] < 0 || n_window[s] > kKfMaxWin || (n_window[s] > 0 && !window_uv_h[s])) {
+        const int fault = batch_handle_fault(c, s, kfs);
+        if (fault == kHandleForeign || !image_d[s] || n_window[s] < 0 || n_window[s] > kKfMaxWin || (n_window[s] > 0 && !window_uv_h[s])) {
             c->err = "lmono_keyframes_add_batch: bad stream arguments (0 <= n_window <= 512)"; return LMONO_EINVAL;
         }
-        for (int u = 0; u < s; u++) if (kfs[u] == kfs[s]) { c->err = "lmono_keyframes_add_batch: stores must be distinct"; return LMONO_EINVAL; }
+        if (fault == kHandleRepeated) { c->err = "lmono_keyframes_add_batch: stores must be distinct"; return LMONO_EINVAL; }
         if (kfs[s]->n_kf >= kfs[s]->max_kf) { c->err = "lmono_keyframes_add: the store is full"; return LMONO_ECAPACITY; }
     }
     lmono_keyframes *lead = kfs[0];
-    if (int rc = kf_job_table(c, lead, n)) return rc;
+    if (!job_table(lead->mem, lead->jobs, lead->res, lead->jobs_cap, n, 2)) { c->err = "lmono_keyframes_add_batch: job table allocation failed"; return LMONO_ENOMEM; }
     std::vector<KfJob> jobs((size_t)n);
     int max_tiles = 1, max_h = 1, max_pts = 1;
     for (int s = 0; s < n; s++) {
@@ -222,14 +187,13 @@ extern "C" int lmono_keyframes_match(lmono_ctx *c, lmono_keyframes *k, int cur, 
         return LMONO_OK;
     }
     if (k->match_cap < n_old) {
-        int cap = std::max(k->match_cap, 4);
-        while (cap < n_old) cap <<= 1;
-        kf_release(k, k->old_slot); kf_release(k, k->m_keys); kf_release(k, k->m_status); kf_release(k, k->m_index); kf_release(k, k->m_dist);
-        kf_release(k, k->m_uv); kf_release(k, k->m_norm); kf_release(k, k->m_counts);
+        // eight arrays of one capacity (nothing reads them now: every call ends synchronised).  match_cap is 0 from a failed growth to the next call, which grows all eight again
+        const int old = k->match_cap;
+        int cap = 0;
         k->match_cap = 0;
-        const size_t e = (size_t)cap * kKfMaxWin;
-        if (!kf_alloc(k, k->old_slot, (size_t)cap) || !kf_alloc(k, k->m_keys, e) || !kf_alloc(k, k->m_status, e) || !kf_alloc(k, k->m_index, e) || !kf_alloc(k, k->m_dist, e) ||
-            !kf_alloc(k, k->m_uv, e) || !kf_alloc(k, k->m_norm, e) || !kf_alloc(k, k->m_counts, (size_t)cap)) { c->err = "lmono_keyframes_match: device allocation failed"; return LMONO_ENOMEM; }
+        auto grow = [&](auto *&p, size_t per) { cap = old; return k->mem.grow_replace(p, cap, (size_t)n_old, /*floor=*/4, per); };
+        if (!grow(k->old_slot, 1) || !grow(k->m_keys, kKfMaxWin) || !grow(k->m_status, kKfMaxWin) || !grow(k->m_index, kKfMaxWin) || !grow(k->m_dist, kKfMaxWin) ||
+            !grow(k->m_uv, kKfMaxWin) || !grow(k->m_norm, kKfMaxWin) || !grow(k->m_counts, 1)) { c->err = "lmono_keyframes_match: device allocation failed"; return LMONO_ENOMEM; }
         k->match_cap = cap;
     }
     const size_t e = (size_t)n_old * n_win;

@@ -13,7 +13,7 @@ struct lmono_scan_batch {
     bool grid_built = false;       // k_grid_build has run for this registration
     std::vector<int64_t> off_h;
     bool validation_pending = false;   // lmono_odom_shard_main_d ran: lmono_odom_shard_validate is the batch's first (whole) validation
-    std::vector<void *> allocs;
+    DevOwner mem;
     BatchView v{};
     int64_t *off_d = nullptr;
     float *in_owned = nullptr;     // staging buffer of lmono_scanreg_batch_h (pts_cap points), allocated on first use
@@ -38,20 +38,10 @@ struct lmono_scan_batch {
     int last_chains = 0, last_lead = 0, last_first = 0;
 };
 
-template <typename T>
-static bool dalloc(lmono_scan_batch *b, T *&p, size_t count)
-{
-    void *q = nullptr;
-    if (hipMalloc(&q, (count > 0 ? count : 1) * sizeof(T)) != hipSuccess) return false;
-    b->allocs.push_back(q);
-    p = (T *)q;
-    return true;
-}
-
 extern "C" void lmono_batch_destroy(lmono_scan_batch *b)
 {
     if (!b) return;
-    for (void *p : b->allocs) (void)hipFree(p);
+    b->mem.clear();
     for (auto &e : b->rep_ev) if (e) (void)hipEventDestroy(e);
     if (b->staged_ev) (void)hipEventDestroy(b->staged_ev);
     if (b->in_free_ev) (void)hipEventDestroy(b->in_free_ev);
@@ -66,23 +56,24 @@ extern "C" lmono_scan_batch *lmono_batch_create(lmono_ctx *c, int n_cap, int64_t
     b->ctx = c; b->n_cap = n_cap; b->pts_cap = pts_cap;
     BatchView &v = b->v;
     const size_t T = (size_t)pts_cap, N = (size_t)n_cap;
+    DevOwner &m = b->mem;
     bool ok = true;
-    ok = ok && dalloc(b, b->off_d, N + 1);
-    ok = ok && dalloc(b, v.cloud, T) && dalloc(b, v.curv, T) && dalloc(b, v.label, T) && dalloc(b, v.gap, T);
-    ok = ok && dalloc(b, v.ring_tmp, T);
-    ok = ok && dalloc(b, v.seg_hist, ((T >> 10) + N + 1) * 64) && dalloc(b, v.scan_ends, N * 2) && dalloc(b, v.scan_half, N) && dalloc(b, v.scan_ori, N * 2);
-    ok = ok && dalloc(b, v.ring_begin, N * 65) && dalloc(b, v.n_cloud, N) && dalloc(b, v.status, N);
-    ok = ok && dalloc(b, v.sel_sharp, N * 64 * 6 * 20) && dalloc(b, v.sel_sharp_n, N * 64 * 6);
-    ok = ok && dalloc(b, v.sel_flat, N * 64 * 6 * 4) && dalloc(b, v.sel_flat_n, N * 64 * 6);
-    ok = ok && dalloc(b, v.lf_tmp, T) && dalloc(b, v.lf_n, N * 64) && dalloc(b, v.vox_todo, N * 64 + 1) && dalloc(b, v.sel_todo, N * 64 + 1) && dalloc(b, v.li_todo, N * 2 + 1);
-    ok = ok && dalloc(b, v.sharp, N * kMaxSharp) && dalloc(b, v.less_sharp, N * kMaxLessSharp);
-    ok = ok && dalloc(b, v.flat, N * kMaxFlat) && dalloc(b, v.less_flat, T);
-    ok = ok && dalloc(b, v.feat_n, N * 4) && dalloc(b, v.line_first_ge, N * 2 * 66) && dalloc(b, v.line_last_le, N * 2 * 66);
-    ok = ok && dalloc(b, v.cg_cell, N * kCornerTable) && dalloc(b, v.sg_cell, N * kSurfTable);
-    ok = ok && dalloc(b, v.cg_pts, N * kMaxLessSharp) && dalloc(b, v.sg_pts, T) && dalloc(b, v.grid_mask, N * 2);
-    ok = ok && dalloc(b, v.lbc_pts, N * kMaxLessSharp + kLbPad) && dalloc(b, v.lbs_pts, T + kLbPad) && dalloc(b, v.lb_start, N * 2 * (kLineKeys + 1)) && dalloc(b, v.lb_elev, N * 2 * 66);
-    ok = ok && dalloc(b, b->incr, N * 7) && dalloc(b, b->poses, N * 7) && dalloc(b, b->xq, 8);
-    ok = ok && dalloc(b, b->corr_pair, (size_t)kMaxQueries * 4) && dalloc(b, b->crec_pair, (size_t)kMaxQueries * 4);
+    ok = ok && m.alloc(b->off_d, N + 1);
+    ok = ok && m.alloc(v.cloud, T) && m.alloc(v.curv, T) && m.alloc(v.label, T) && m.alloc(v.gap, T);
+    ok = ok && m.alloc(v.ring_tmp, T);
+    ok = ok && m.alloc(v.seg_hist, ((T >> 10) + N + 1) * 64) && m.alloc(v.scan_ends, N * 2) && m.alloc(v.scan_half, N) && m.alloc(v.scan_ori, N * 2);
+    ok = ok && m.alloc(v.ring_begin, N * 65) && m.alloc(v.n_cloud, N) && m.alloc(v.status, N);
+    ok = ok && m.alloc(v.sel_sharp, N * 64 * 6 * 20) && m.alloc(v.sel_sharp_n, N * 64 * 6);
+    ok = ok && m.alloc(v.sel_flat, N * 64 * 6 * 4) && m.alloc(v.sel_flat_n, N * 64 * 6);
+    ok = ok && m.alloc(v.lf_tmp, T) && m.alloc(v.lf_n, N * 64) && m.alloc(v.vox_todo, N * 64 + 1) && m.alloc(v.sel_todo, N * 64 + 1) && m.alloc(v.li_todo, N * 2 + 1);
+    ok = ok && m.alloc(v.sharp, N * kMaxSharp) && m.alloc(v.less_sharp, N * kMaxLessSharp);
+    ok = ok && m.alloc(v.flat, N * kMaxFlat) && m.alloc(v.less_flat, T);
+    ok = ok && m.alloc(v.feat_n, N * 4) && m.alloc(v.line_first_ge, N * 2 * 66) && m.alloc(v.line_last_le, N * 2 * 66);
+    ok = ok && m.alloc(v.cg_cell, N * kCornerTable) && m.alloc(v.sg_cell, N * kSurfTable);
+    ok = ok && m.alloc(v.cg_pts, N * kMaxLessSharp) && m.alloc(v.sg_pts, T) && m.alloc(v.grid_mask, N * 2);
+    ok = ok && m.alloc(v.lbc_pts, N * kMaxLessSharp + kLbPad) && m.alloc(v.lbs_pts, T + kLbPad) && m.alloc(v.lb_start, N * 2 * (kLineKeys + 1)) && m.alloc(v.lb_elev, N * 2 * 66);
+    ok = ok && m.alloc(b->incr, N * 7) && m.alloc(b->poses, N * 7) && m.alloc(b->xq, 8);
+    ok = ok && m.alloc(b->corr_pair, (size_t)kMaxQueries * 4) && m.alloc(b->crec_pair, (size_t)kMaxQueries * 4);
     if (!ok) {
         c->err = "lmono_batch_create: hipMalloc failed";
         lmono_batch_destroy(b);
@@ -160,6 +151,15 @@ static int scanreg_launch(lmono_ctx *c, lmono_scan_batch *b, int scan0, int n_sc
 extern "C" int lmono_scanreg_batch(lmono_ctx *c, lmono_scan_batch *b, const float *xyzi_d, const int64_t *offsets_h,
                                    int n_scans, int n_lines, float min_range);
 
+// the batch's own input buffer (pts_cap points of xyzi), allocated by the first call that stages host points
+static int batch_own_input(lmono_ctx *c, lmono_scan_batch *b)
+{
+    if (b->in_owned || b->mem.alloc(b->in_owned, (size_t)b->pts_cap * 4)) return LMONO_OK;
+    const hipError_t e = hipGetLastError();
+    c->err = std::string("hipMalloc(&q, (size_t)(b->pts_cap > 0 ? b->pts_cap : 1) * 16): ") + hipGetErrorString(e);      // the words this failure has always had
+    return e == hipErrorOutOfMemory ? LMONO_ENOMEM : LMONO_ENODEV;
+}
+
 extern "C" int lmono_scanreg_batch_h(lmono_ctx *c, lmono_scan_batch *b, const float *xyzi_h, const int64_t *offsets_h,
                                      int n_scans, int n_lines, float min_range)
 {
@@ -168,12 +168,7 @@ extern "C" int lmono_scanreg_batch_h(lmono_ctx *c, lmono_scan_batch *b, const fl
     const int64_t total = offsets_h[n_scans];
     if (total < 0 || total > b->pts_cap) { c->err = "batch: too many points"; return LMONO_ECAPACITY; }
     HIP_TRY(c, hipSetDevice(c->device));
-    if (!b->in_owned) {
-        void *q = nullptr;
-        HIP_TRY(c, hipMalloc(&q, (size_t)(b->pts_cap > 0 ? b->pts_cap : 1) * 16));
-        b->allocs.push_back(q);
-        b->in_owned = (float *)q;
-    }
+    if (int rc = batch_own_input(c, b)) return rc;
     if (total > 0) {
         // staged: the caller's (pageable) buffer is free again when this returns
         HIP_TRY(c, hipMemcpyAsync(b->in_owned, xyzi_h, (size_t)total * 16, hipMemcpyHostToDevice, c->stream));
@@ -217,12 +212,7 @@ extern "C" int lmono_batch_stage_h(lmono_ctx *c, lmono_scan_batch *b, const floa
     if (total_points > b->pts_cap) { c->err = "batch: too many points"; return LMONO_ECAPACITY; }
     HIP_TRY(c, hipSetDevice(c->device));
     if (!c->copy_stream) HIP_TRY(c, hipStreamCreateWithFlags(&c->copy_stream, hipStreamNonBlocking));
-    if (!b->in_owned) {
-        void *q = nullptr;
-        HIP_TRY(c, hipMalloc(&q, (size_t)(b->pts_cap > 0 ? b->pts_cap : 1) * 16));
-        b->allocs.push_back(q);
-        b->in_owned = (float *)q;
-    }
+    if (int rc = batch_own_input(c, b)) return rc;
     if (!b->staged_ev) HIP_TRY(c, hipEventCreateWithFlags(&b->staged_ev, hipEventDisableTiming));
     if (!b->in_free_ev) HIP_TRY(c, hipEventCreateWithFlags(&b->in_free_ev, hipEventDisableTiming));
     // the front end of this batch's previous registration may still read the staging buffer
@@ -348,12 +338,13 @@ extern "C" int lmono_batch_get_curvature(lmono_ctx *c, lmono_scan_batch *b, int 
 static int ensure_odom_ws(lmono_ctx *c, lmono_scan_batch *b, int n_chains)
 {
     if (n_chains <= b->chains_cap) return LMONO_OK;
-    // (re)allocate; old buffers stay in allocs and are freed with the batch
-    bool ok = dalloc(b, b->state, (size_t)n_chains * 8) && dalloc(b, b->corr, (size_t)n_chains * kMaxQueries * 4) &&
-              dalloc(b, b->lm_info, (size_t)n_chains * 4) && dalloc(b, b->crec, (size_t)n_chains * kMaxQueries * 4) &&
-              dalloc(b, b->seed, (size_t)n_chains * kMaxQueries) && dalloc(b, b->wl, 8 * ((size_t)n_chains * kMaxQueries + 1)) &&
-              dalloc(b, b->ws, (size_t)n_chains * 8) && dalloc(b, b->resid_d, (size_t)n_chains) && dalloc(b, b->rstat, (size_t)n_chains * 4) &&
-              dalloc(b, b->rcount, (size_t)n_chains + 2);
+    // the grow_keep policy, sized by hand: exactly n_chains (no doubling), and the outgrown buffers stay owned until the batch is destroyed
+    DevOwner &m = b->mem;
+    bool ok = m.alloc(b->state, (size_t)n_chains * 8) && m.alloc(b->corr, (size_t)n_chains * kMaxQueries * 4) &&
+              m.alloc(b->lm_info, (size_t)n_chains * 4) && m.alloc(b->crec, (size_t)n_chains * kMaxQueries * 4) &&
+              m.alloc(b->seed, (size_t)n_chains * kMaxQueries) && m.alloc(b->wl, 8 * ((size_t)n_chains * kMaxQueries + 1)) &&
+              m.alloc(b->ws, (size_t)n_chains * 8) && m.alloc(b->resid_d, (size_t)n_chains) && m.alloc(b->rstat, (size_t)n_chains * 4) &&
+              m.alloc(b->rcount, (size_t)n_chains + 2);
     if (!ok) { c->err = "odometry workspace: hipMalloc failed"; return LMONO_ENOMEM; }
     b->chains_cap = n_chains;
     return LMONO_OK;
@@ -688,6 +679,7 @@ struct lmono_odom_stream {
     lmono_ctx *ctx = nullptr;
     lmono_scan_batch *batch = nullptr;
     float *in_d = nullptr;
+    DevOwner mem;
     int cap_pts = 0, n_slots = 0, slot = 0;
     long long frame = 0;
     double para[8] = { 0, 0, 0, 1, 0, 0, 0, 0 };       // q_last_curr (x y z w), t_last_curr
@@ -698,7 +690,6 @@ extern "C" void lmono_odom_stream_destroy(lmono_odom_stream *s)
 {
     if (!s) return;
     if (s->batch) lmono_batch_destroy(s->batch);
-    if (s->in_d) (void)hipFree(s->in_d);
     delete s;
 }
 
@@ -710,7 +701,7 @@ extern "C" lmono_odom_stream *lmono_odom_stream_create(lmono_ctx *c, int max_poi
     lmono_odom_stream *s = new lmono_odom_stream();
     s->ctx = c; s->cap_pts = max_points; s->n_slots = history + 1;
     s->batch = lmono_batch_create(c, s->n_slots, (int64_t)s->n_slots * max_points);
-    if (!s->batch || hipMalloc((void **)&s->in_d, (size_t)s->n_slots * max_points * 16) != hipSuccess) { c->err = "lmono_odom_stream_create: allocation failed"; lmono_odom_stream_destroy(s); return nullptr; }
+    if (!s->batch || !s->mem.alloc(s->in_d, (size_t)s->n_slots * max_points * 4)) { c->err = "lmono_odom_stream_create: allocation failed"; lmono_odom_stream_destroy(s); return nullptr; }
     lmono_scan_batch *b = s->batch;
     b->off_h.resize(s->n_slots + 1);
     for (int i = 0; i <= s->n_slots; i++) b->off_h[i] = (int64_t)i * max_points;

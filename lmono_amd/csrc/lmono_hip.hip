@@ -28,6 +28,7 @@ using namespace lmono;
 struct EvSet { hipEvent_t e[10]; bool reg = false, odom = false; std::vector<hipEvent_t> kev; int n_kev = 0; };  // kev: (begin, mid, end) per odometry launch pair
 
 #include "host_workers.hpp"
+#include "dev_owner.hpp"
 
 // per-thread tables of lmono_mapper_process_batch's update plan (indexed by cube: 21 x 21 x 11)
 struct MapPlanScratch {
@@ -330,6 +331,16 @@ extern "C" void *lmono_host_alloc(lmono_ctx *c, size_t bytes)
     return p;
 }
 extern "C" void lmono_host_free(lmono_ctx *c, void *p) { if (c && p) (void)hipHostFree(p); }
+
+// hs[s] as the s-th handle of a batched call: a handle of c that no earlier stream names, null or another context's, or hs[u] again (u < s).
+// The entry points ask per stream, inside their own loop: which of a stream's faults is reported first, and in which words, stays theirs
+enum { kHandleOk = 0, kHandleForeign, kHandleRepeated };
+template <typename H> static int batch_handle_fault(const lmono_ctx *c, int s, H *const *hs)
+{
+    if (!hs[s] || hs[s]->ctx != c) return kHandleForeign;
+    for (int u = 0; u < s; u++) if (hs[u] == hs[s]) return kHandleRepeated;
+    return kHandleOk;
+}
 
 #include "lidar_abi.hip"
 #include "ba_abi.hip"

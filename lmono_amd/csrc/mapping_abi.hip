@@ -183,8 +183,7 @@ struct lmono_mapper {
     int cen[3] = { 10, 10, 5 };
     double q_wmap_wodom[4] = { 0, 0, 0, 1 }, t_wmap_wodom[3] = { 0, 0, 0 };
     std::vector<Seg> cube[2];
-    std::vector<void *> allocs;
-    std::vector<void *> pinned;                 // hipHostMalloc'ed mail boxes
+    DevOwner mem;                               // device buffers and the pinned mail boxes
     int *pin_i = nullptr; double *pin_x = nullptr; int *pin_cube = nullptr; int *pin_nout = nullptr; char *pin_blob = nullptr;
     size_t pin_i_cap = 0, pin_x_cap = 0, pin_cube_cap = 0, pin_nout_cap = 0, pin_blob_cap = 0;
     float4 *arena[2][2] = { { nullptr, nullptr }, { nullptr, nullptr } };   // [type][half]
@@ -229,15 +228,6 @@ struct lmono_mapper {
     int bump_seen[2] = { 0, 0 }, nmap_seen[2] = { 0, 0 };
 };
 
-template <typename T> static bool mp_alloc(lmono_mapper *m, T *&p, size_t n)
-{
-    void *q = nullptr;
-    if (hipMalloc(&q, (n > 0 ? n : 1) * sizeof(T)) != hipSuccess) return false;
-    m->allocs.push_back(q);
-    p = (T *)q;
-    return true;
-}
-
 extern "C" void lmono_mapper_destroy(lmono_mapper *m)
 {
     if (!m) return;
@@ -246,9 +236,7 @@ extern "C" void lmono_mapper_destroy(lmono_mapper *m)
     if (m->ev_side) (void)hipEventDestroy(m->ev_side);
     if (m->ev_sizes) (void)hipEventDestroy(m->ev_sizes);
     for (hipEvent_t e : { m->ev_commit, m->ev_assign, m->ev_pose, m->ev_solve }) if (e) (void)hipEventDestroy(e);
-    for (void *q : m->allocs) (void)hipFree(q);
-    for (void *q : m->pinned) (void)hipHostFree(q);
-    delete m;
+    delete m;                   // its memory goes last
 }
 
 extern "C" lmono_mapper *lmono_mapper_create(lmono_ctx *c, float line_res, float plane_res)
@@ -263,32 +251,28 @@ extern "C" lmono_mapper *lmono_mapper_create(lmono_ctx *c, float line_res, float
     while (m->tcap < kMapNeighMax + 1) m->tcap <<= 1;
     bool ok = true;
     for (int t = 0; t < 2 && ok; t++) {
-        ok = ok && mp_alloc(m, m->arena[t][0], (size_t)kMapArena) && mp_alloc(m, m->arena[t][1], (size_t)kMapArena) &&
-             mp_alloc(m, m->stack[t], (size_t)kMapStackMax) && mp_alloc(m, m->newpts[t], (size_t)kMapStackMax) &&
-             mp_alloc(m, m->neigh[t], (size_t)kMapNeighMax) && mp_alloc(m, m->sorted[t], (size_t)kMapNeighMax) &&
-             mp_alloc(m, m->cat[t], (size_t)kMapNeighMax + kMapStackMax) &&
-             mp_alloc(m, m->vk[t], (size_t)2 * (kMapNeighMax + kMapStackMax)) && mp_alloc(m, m->vi[t], (size_t)2 * (kMapNeighMax + kMapStackMax)) &&
-             mp_alloc(m, m->slot[t], (size_t)kMapNeighMax) && mp_alloc(m, m->rank[t], (size_t)kMapNeighMax) &&
-             mp_alloc(m, m->cube_of[t], (size_t)kMapStackMax) && mp_alloc(m, m->pos[t], (size_t)kMapStackMax) &&
-             mp_alloc(m, m->cells[t], (size_t)m->tcap) && mp_alloc(m, m->vws[t], m->vws_cap);
+        ok = ok && m->mem.alloc(m->arena[t][0], (size_t)kMapArena) && m->mem.alloc(m->arena[t][1], (size_t)kMapArena) &&
+             m->mem.alloc(m->stack[t], (size_t)kMapStackMax) && m->mem.alloc(m->newpts[t], (size_t)kMapStackMax) &&
+             m->mem.alloc(m->neigh[t], (size_t)kMapNeighMax) && m->mem.alloc(m->sorted[t], (size_t)kMapNeighMax) &&
+             m->mem.alloc(m->cat[t], (size_t)kMapNeighMax + kMapStackMax) &&
+             m->mem.alloc(m->vk[t], (size_t)2 * (kMapNeighMax + kMapStackMax)) && m->mem.alloc(m->vi[t], (size_t)2 * (kMapNeighMax + kMapStackMax)) &&
+             m->mem.alloc(m->slot[t], (size_t)kMapNeighMax) && m->mem.alloc(m->rank[t], (size_t)kMapNeighMax) &&
+             m->mem.alloc(m->cube_of[t], (size_t)kMapStackMax) && m->mem.alloc(m->pos[t], (size_t)kMapStackMax) &&
+             m->mem.alloc(m->cells[t], (size_t)m->tcap) && m->mem.alloc(m->vws[t], m->vws_cap);
     }
     m->jobs_bytes = 1 << 20;
     m->nout_cap = 1024;
-    ok = ok && mp_alloc(m, m->masks, 4) && mp_alloc(m, m->nout, 2 * 256) && mp_alloc(m, m->nout_big, m->nout_cap) && mp_alloc(m, m->stats, 8) && mp_alloc(m, m->x, 8) &&
-         mp_alloc(m, m->rec, (size_t)2 * kMapStackMax) && mp_alloc(m, m->nn_tmp, (size_t)10 * kMapStackMax) && mp_alloc(m, (char *&)m->jobs, m->jobs_bytes) && mp_alloc(m, m->stream_d, 1) &&
-         mp_alloc(m, m->solve_part, (size_t)kMsEvals * kMsMaxK * 28);
+    ok = ok && m->mem.alloc(m->masks, 4) && m->mem.alloc(m->nout, 2 * 256) && m->mem.alloc(m->nout_big, m->nout_cap) && m->mem.alloc(m->stats, 8) && m->mem.alloc(m->x, 8) &&
+         m->mem.alloc(m->rec, (size_t)2 * kMapStackMax) && m->mem.alloc(m->nn_tmp, (size_t)10 * kMapStackMax) && m->mem.alloc((char *&)m->jobs, m->jobs_bytes) && m->mem.alloc(m->stream_d, 1) &&
+         m->mem.alloc(m->solve_part, (size_t)kMsEvals * kMsMaxK * 28);
     ok = ok && hipStreamCreateWithFlags(&m->side, hipStreamNonBlocking) == hipSuccess && hipEventCreateWithFlags(&m->ev_side, hipEventDisableTiming) == hipSuccess &&
          hipEventCreateWithFlags(&m->ev_sizes, hipEventDisableTiming) == hipSuccess;
     constexpr size_t kFrameBlob = 4096;
-    ok = ok && mp_alloc(m, m->dev, 1) && mp_alloc(m, m->upd, 1) && mp_alloc(m, m->fblob[0], kFrameBlob) && mp_alloc(m, m->fblob[1], kFrameBlob) && mp_alloc(m, m->cube_of_d, (size_t)2 * kMapStackMax);
+    ok = ok && m->mem.alloc(m->dev, 1) && m->mem.alloc(m->upd, 1) && m->mem.alloc(m->fblob[0], kFrameBlob) && m->mem.alloc(m->fblob[1], kFrameBlob) && m->mem.alloc(m->cube_of_d, (size_t)2 * kMapStackMax);
     for (int t = 0; t < 2 && ok; t++)
-        ok = ok && mp_alloc(m, m->vk_s[t], (size_t)2 * kMapStackMax) && mp_alloc(m, m->vi_s[t], (size_t)2 * kMapStackMax) && mp_alloc(m, m->vws_s[t], vox_ws_ints(kMapStackMax));
+        ok = ok && m->mem.alloc(m->vk_s[t], (size_t)2 * kMapStackMax) && m->mem.alloc(m->vi_s[t], (size_t)2 * kMapStackMax) && m->mem.alloc(m->vws_s[t], vox_ws_ints(kMapStackMax));
     for (hipEvent_t *e : { &m->ev_commit, &m->ev_assign, &m->ev_pose, &m->ev_solve }) ok = ok && hipEventCreateWithFlags(e, hipEventDisableTiming) == hipSuccess;
-    if (ok) {
-        void *q = nullptr;
-        ok = hipHostMalloc(&q, 2 * kFrameBlob + 256, hipHostMallocDefault) == hipSuccess;
-        if (ok) { m->pinned.push_back(q); m->fstage[0] = (char *)q; m->fstage[1] = (char *)q + kFrameBlob; m->pin_back = (char *)q + 2 * kFrameBlob; }
-    }
+    if (ok && (ok = m->mem.pinned(m->fstage[0], 2 * kFrameBlob + 256))) { m->fstage[1] = m->fstage[0] + kFrameBlob; m->pin_back = m->fstage[0] + 2 * kFrameBlob; }
     if (!ok) { c->err = "lmono_mapper_create: device allocation failed"; lmono_mapper_destroy(m); return nullptr; }
     return m;
 }
@@ -333,25 +317,14 @@ static int mapper_compact(lmono_mapper *m, int t)
 namespace {
 template <typename T> int mp_grow(lmono_ctx *c, lmono_mapper *m, T *&p, size_t &cap, size_t need)
 {
-    if (need <= cap) return LMONO_OK;
-    size_t nc = cap ? cap : 1024;
-    while (nc < need) nc <<= 1;
-    T *q = nullptr;
-    if (!mp_alloc(m, q, nc)) { c->err = "lmono_mapper: allocation failed"; return LMONO_ENOMEM; }
-    p = q; cap = nc;
+    if (!m->mem.grow_keep(p, cap, need, /*floor=*/1024)) { c->err = "lmono_mapper: allocation failed"; return LMONO_ENOMEM; }     // kept: kernels in flight may still read the old buffer
     return LMONO_OK;
 }
 // pinned host mail boxes of the frame's read-backs (a copy into pageable memory holds the calling thread until it is done; into pinned memory it is
 // asynchronous -- the host goes on enqueueing): grown on demand, freed with the mapper
 template <typename T> int pin_grow(lmono_ctx *c, lmono_mapper *m, T *&p, size_t &cap, size_t need)
 {
-    if (need <= cap) return LMONO_OK;
-    size_t nc = cap ? cap : 1024;
-    while (nc < need) nc <<= 1;
-    void *q = nullptr;
-    if (hipHostMalloc(&q, nc * sizeof(T), hipHostMallocDefault) != hipSuccess) { c->err = "lmono_mapper: pinned allocation failed"; return LMONO_ENOMEM; }
-    m->pinned.push_back(q);
-    p = (T *)q; cap = nc;
+    if (!m->mem.grow_keep_pinned(p, cap, need, /*floor=*/1024)) { c->err = "lmono_mapper: pinned allocation failed"; return LMONO_ENOMEM; }
     return LMONO_OK;
 }
 // job tables of one phase for every stream go through one pinned-free staging path: a scratch device buffer owned by the
@@ -368,12 +341,10 @@ struct JobScratch {
     {
         used = (used + 255) & ~(size_t)255;
         if (used + bytes > owner->jobs_bytes) {
-            void *q = nullptr;
             size_t nb = owner->jobs_bytes;
             while (nb < bytes || nb < 2 * (used + bytes)) nb <<= 1;
-            if (hipMalloc(&q, nb) != hipSuccess) { c->err = "lmono_mapper: job scratch allocation failed"; return LMONO_ENOMEM; }
-            owner->allocs.push_back(q);
-            owner->jobs = q; owner->jobs_bytes = nb; used = 0;
+            if (!owner->mem.alloc((char *&)owner->jobs, nb)) { c->err = "lmono_mapper: job scratch allocation failed"; return LMONO_ENOMEM; }      // keep mode: the old scratch stays owned
+            owner->jobs_bytes = nb; used = 0;
         }
         last = (char *)owner->jobs + used;
         used += bytes;

@@ -12,36 +12,12 @@ struct lmono_pose_graph {
     PgView v{};
     int n = 0, n_edges = 0, w = 0;
     int64_t reduce_count = 0;
-    std::vector<void *> allocs;
+    DevOwner mem;
     std::vector<double> pitch_h, roll_h, x0_h;
     std::vector<int> pos_h;
 };
 
-template <typename T> static bool pg_upload(lmono_pose_graph *g, const T *&dst, const std::vector<T> &src)
-{
-    void *q = nullptr;
-    if (hipMalloc(&q, std::max<size_t>(src.size(), 1) * sizeof(T)) != hipSuccess) return false;
-    g->allocs.push_back(q);
-    if (!src.empty() && hipMemcpy(q, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice) != hipSuccess) return false;
-    dst = (const T *)q;
-    return true;
-}
-template <typename T> static bool pg_alloc(lmono_pose_graph *g, T *&dst, size_t count)
-{
-    void *q = nullptr;
-    if (hipMalloc(&q, std::max<size_t>(count, 1) * sizeof(T)) != hipSuccess) return false;
-    g->allocs.push_back(q);
-    if (hipMemset(q, 0, std::max<size_t>(count, 1) * sizeof(T)) != hipSuccess) return false;
-    dst = (T *)q;
-    return true;
-}
-
-extern "C" void lmono_pose_graph_destroy(lmono_pose_graph *g)
-{
-    if (!g) return;
-    for (void *p : g->allocs) (void)hipFree(p);
-    delete g;
-}
+extern "C" void lmono_pose_graph_destroy(lmono_pose_graph *g) { delete g; }
 
 // mathutils::R2ypr (include/utils/math_utils.h:187-202) of the rotation of q (x y z w), degrees
 static void pg_q2ypr(const double *q, double *ypr)
@@ -158,12 +134,13 @@ extern "C" lmono_pose_graph *lmono_pose_graph_create(lmono_ctx *c, int n, const 
     g->reduce_count = (int64_t)(hsz + 5 * (size_t)n);
     PgView &v = g->v;
     v.n = n; v.w = w; v.n_edges = ne;
-    bool ok = pg_upload(g, v.ea, ea) && pg_upload(g, v.eb, eb) && pg_upload(g, v.eloop, el) && pg_upload(g, v.emeas, em) &&
-              pg_upload(g, v.inc_start, inc_start) && pg_upload(g, v.inc_edge, inc_edge) && pg_upload(g, v.pos, pos) && pg_upload(g, v.node_at, node_at) &&
-              pg_upload(g, v.pitch, g->pitch_h) && pg_upload(g, v.roll, g->roll_h) &&
-              pg_alloc(g, v.x, (size_t)n * 4) && pg_alloc(g, v.cand, (size_t)n * 4) && pg_alloc(g, v.lin, (size_t)g->reduce_count) &&
-              pg_alloc(g, v.cur, (size_t)g->reduce_count) && pg_alloc(g, v.Aw, hsz) && pg_alloc(g, v.scale, (size_t)n * 4) && pg_alloc(g, v.diag, (size_t)n * 4) &&
-              pg_alloc(g, v.gs, (size_t)n * 4) && pg_alloc(g, v.sol, (size_t)n * 4) && pg_alloc(g, v.st, 1);
+    DevOwner &m = g->mem;
+    bool ok = m.upload(v.ea, ea) && m.upload(v.eb, eb) && m.upload(v.eloop, el) && m.upload(v.emeas, em) &&
+              m.upload(v.inc_start, inc_start) && m.upload(v.inc_edge, inc_edge) && m.upload(v.pos, pos) && m.upload(v.node_at, node_at) &&
+              m.upload(v.pitch, g->pitch_h) && m.upload(v.roll, g->roll_h) &&
+              m.alloc_zero(v.x, (size_t)n * 4) && m.alloc_zero(v.cand, (size_t)n * 4) && m.alloc_zero(v.lin, (size_t)g->reduce_count) &&
+              m.alloc_zero(v.cur, (size_t)g->reduce_count) && m.alloc_zero(v.Aw, hsz) && m.alloc_zero(v.scale, (size_t)n * 4) && m.alloc_zero(v.diag, (size_t)n * 4) &&
+              m.alloc_zero(v.gs, (size_t)n * 4) && m.alloc_zero(v.sol, (size_t)n * 4) && m.alloc_zero(v.st, 1);
     ok = ok && hipMemcpy(v.x, x.data(), x.size() * sizeof(double), hipMemcpyHostToDevice) == hipSuccess;
     g->x0_h = x; g->pos_h = pos;
     if (!ok) { c->err = "lmono_pose_graph_create: device allocation failed"; lmono_pose_graph_destroy(g); return nullptr; }

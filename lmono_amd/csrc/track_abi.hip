@@ -21,28 +21,14 @@ struct lmono_tracker {
     float2 *rej_prev = nullptr, *rej_cur = nullptr;      // staging of the diagnostic call
     int32_t last_stats[4] = { -1, -1, -1, -1 };
     double last_F[9] = {};
-    std::vector<void *> allocs;
+    DevOwner mem;
     // job table + counts of a batch led by this tracker
     TrkJob *jobs = nullptr;
     int *counts = nullptr;
     int jobs_cap = 0;
 };
 
-template <typename T> static bool trk_alloc(lmono_tracker *t, T *&p, size_t n)
-{
-    void *q = nullptr;
-    if (hipMalloc(&q, (n ? n : 1) * sizeof(T)) != hipSuccess) return false;
-    t->allocs.push_back(q);
-    p = (T *)q;
-    return true;
-}
-
-extern "C" void lmono_tracker_destroy(lmono_tracker *t)
-{
-    if (!t) return;
-    for (void *p : t->allocs) (void)hipFree(p);
-    delete t;
-}
+extern "C" void lmono_tracker_destroy(lmono_tracker *t) { delete t; }
 
 extern "C" int lmono_tracker_reset(lmono_ctx *c, lmono_tracker *t)
 {
@@ -67,11 +53,7 @@ extern "C" lmono_tracker *lmono_tracker_create(lmono_ctx *c, const lmono_camera 
     t->ctx = c;
     TrkJob &j = t->job;
     j.w = cam->width; j.h = cam->height; j.max_cnt = max_cnt; j.min_dist = min_dist; j.lk_n = -1;
-    ColourCam &k = j.cam;
-    k.w = cam->width; k.h = cam->height;
-    k.fx = cam->fx; k.fy = cam->fy; k.cx = cam->cx; k.cy = cam->cy; k.k1 = cam->k1; k.k2 = cam->k2; k.p1 = cam->p1; k.p2 = cam->p2;
-    k.ik11 = 1.0 / k.fx; k.ik13 = -k.cx / k.fx; k.ik22 = 1.0 / k.fy; k.ik23 = -k.cy / k.fy;
-    k.distort = !(k.k1 == 0.0 && k.k2 == 0.0 && k.p1 == 0.0 && k.p2 == 0.0);
+    colour_cam_from(*cam, j.cam);
     {   // rows of cv::circle(mask, pt, MIN_DIST, 0, -1): the filled midpoint circle of OpenCV's drawing.cpp
         int err = 0, dx = min_dist, dy = 0, plus = 1, minus = 2 * min_dist - 1;
         for (int i = 0; i <= kTrkMaxRadius; i++) j.hw[i] = 0;
@@ -91,18 +73,19 @@ extern "C" lmono_tracker *lmono_tracker_create(lmono_ctx *c, const lmono_camera 
         lw[j.n_levels] = w2; lh[j.n_levels] = h2; j.n_levels++;
     }
     const size_t np = (size_t)j.w * j.h;
+    DevOwner &m = t->mem;
     bool ok = true;
     for (int b = 0; b < 2 && ok; b++)
         for (int l = 0; l < j.n_levels && ok; l++) {
             TrkLevel &L = t->pyr[b].lv[l];
             L.w = lw[l]; L.h = lh[l];
-            ok = trk_alloc(t, L.img, (size_t)L.w * L.h) && trk_alloc(t, L.dx, (size_t)L.w * L.h) && trk_alloc(t, L.dy, (size_t)L.w * L.h);
+            ok = m.alloc(L.img, (size_t)L.w * L.h) && m.alloc(L.dx, (size_t)L.w * L.h) && m.alloc(L.dy, (size_t)L.w * L.h);
         }
-    ok = ok && trk_alloc(t, j.st, 1) && trk_alloc(t, j.pts, kTrkMaxPts) && trk_alloc(t, j.un, kTrkMaxPts) && trk_alloc(t, j.ids, kTrkMaxPts) && trk_alloc(t, j.cnt, kTrkMaxPts) &&
-         trk_alloc(t, j.cur_pts, kTrkMaxPts) && trk_alloc(t, j.rev_pts, kTrkMaxPts) && trk_alloc(t, j.st_f, kTrkMaxPts) && trk_alloc(t, j.st_b, kTrkMaxPts) &&
-         trk_alloc(t, j.kept_pix, kTrkMaxPts) && trk_alloc(t, j.resp, np) && trk_alloc(t, j.cand, np) && trk_alloc(t, j.new_pts, kTrkMaxPts) &&
-         trk_alloc(t, j.rec, kTrkMaxPts) && trk_alloc(t, t->lk_pts, kTrkMaxPts) && trk_alloc(t, t->image, np * 3) &&
-         trk_alloc(t, t->rej_st, kTrkMaxPts) && trk_alloc(t, t->rej_stats, 4) && trk_alloc(t, t->rej_F, 9) && trk_alloc(t, t->rej_prev, kTrkMaxPts) && trk_alloc(t, t->rej_cur, kTrkMaxPts);
+    ok = ok && m.alloc(j.st, 1) && m.alloc(j.pts, kTrkMaxPts) && m.alloc(j.un, kTrkMaxPts) && m.alloc(j.ids, kTrkMaxPts) && m.alloc(j.cnt, kTrkMaxPts) &&
+         m.alloc(j.cur_pts, kTrkMaxPts) && m.alloc(j.rev_pts, kTrkMaxPts) && m.alloc(j.st_f, kTrkMaxPts) && m.alloc(j.st_b, kTrkMaxPts) &&
+         m.alloc(j.kept_pix, kTrkMaxPts) && m.alloc(j.resp, np) && m.alloc(j.cand, np) && m.alloc(j.new_pts, kTrkMaxPts) &&
+         m.alloc(j.rec, kTrkMaxPts) && m.alloc(t->lk_pts, kTrkMaxPts) && m.alloc(t->image, np * 3) &&
+         m.alloc(t->rej_st, kTrkMaxPts) && m.alloc(t->rej_stats, 4) && m.alloc(t->rej_F, 9) && m.alloc(t->rej_prev, kTrkMaxPts) && m.alloc(t->rej_cur, kTrkMaxPts);
     ok = ok && hipMemset(j.st, 0, sizeof(TrkState)) == hipSuccess && hipMemset(j.resp, 0, np * sizeof(float)) == hipSuccess;
     if (!ok) { c->err = "lmono_tracker_create: device allocation failed"; lmono_tracker_destroy(t); return nullptr; }
     return t;
@@ -143,17 +126,7 @@ extern "C" int lmono_tracker_reject_stats(lmono_ctx *c, lmono_tracker *t, int32_
 
 static int trk_job_table(lmono_ctx *c, lmono_tracker *lead, int n_streams, const char *who)
 {
-    if (lead->jobs_cap >= n_streams) return LMONO_OK;
-    int cap = std::max(lead->jobs_cap, 1);
-    while (cap < n_streams) cap <<= 1;
-    TrkJob *jb = nullptr; int *cn = nullptr;
-    if (!trk_alloc(lead, jb, (size_t)cap) || !trk_alloc(lead, cn, (size_t)cap)) { c->err = std::string(who) + ": job table allocation failed"; return LMONO_ENOMEM; }
-    for (void *old : { (void *)lead->jobs, (void *)lead->counts }) {      // the outgrown table (no launch that reads it is in flight: every call ends synchronised)
-        if (!old) continue;
-        (void)hipFree(old);
-        lead->allocs.erase(std::find(lead->allocs.begin(), lead->allocs.end(), old));
-    }
-    lead->jobs = jb; lead->counts = cn; lead->jobs_cap = cap;
+    if (!job_table(lead->mem, lead->jobs, lead->counts, lead->jobs_cap, n_streams, 1)) { c->err = std::string(who) + ": job table allocation failed"; return LMONO_ENOMEM; }
     return LMONO_OK;
 }
 
@@ -164,9 +137,10 @@ extern "C" int lmono_tracker_track_batch(lmono_ctx *c, int n_streams, lmono_trac
 {
     if (!c || n_streams <= 0 || !trks || !times || !image_d || !n_out || (format != LMONO_TRACK_GREY8 && format != LMONO_TRACK_BGR8)) return LMONO_EINVAL;
     for (int s = 0; s < n_streams; s++) {
-        if (!trks[s] || trks[s]->ctx != c || !image_d[s]) { c->err = "lmono_tracker_track_batch: bad stream arguments"; return LMONO_EINVAL; }
+        const int fault = batch_handle_fault(c, s, trks);
+        if (fault == kHandleForeign || !image_d[s]) { c->err = "lmono_tracker_track_batch: bad stream arguments"; return LMONO_EINVAL; }
         if (trks[s]->stale) { c->err = "lmono_tracker_track_batch: an earlier frame of this tracker failed half way; call lmono_tracker_reset"; return LMONO_EINVAL; }
-        for (int u = 0; u < s; u++) if (trks[u] == trks[s]) { c->err = "lmono_tracker_track_batch: trackers must be distinct"; return LMONO_EINVAL; }
+        if (fault == kHandleRepeated) { c->err = "lmono_tracker_track_batch: trackers must be distinct"; return LMONO_EINVAL; }
         if (records_out && records_out[s] && (!caps || caps[s] < trks[s]->job.max_cnt)) { c->err = "lmono_tracker_track_batch: record capacity below max_cnt"; return LMONO_ECAPACITY; }
     }
     lmono_tracker *lead = trks[0];

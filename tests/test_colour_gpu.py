@@ -162,3 +162,38 @@ def test_cpp_map_build_writes_the_colour_map(oracle, tmp_path):
     assert (out / "cloud_cam_last.bin").read_bytes() == a.tobytes() and (out / "cloud_world_last.bin").read_bytes() == b.tobytes()
     rec = (out / "mapping_recorder.txt").read_text().split("\n")
     assert len(rec) == n + 1 and all(line.endswith(" ") and line.startswith("%f" % stamps[k]) for k, line in enumerate(rec[:n]))
+
+
+def test_lead_builder_job_table_grows_and_is_reused(oracle, gpu_ctx):
+    """lmono_associate_to_map_batch with 1, then 2, then 5 builders led by the same first builder: its job table grows twice (the outgrown
+    one is freed at once) and every stream's depth map and clouds equal those of a single builder.  8 x 8 is the smallest image of this file."""
+    import torch
+    import lmono_amd
+    w = h = 8
+    oc, gc = _cam(oracle, w=w, h=h, scale=w / 1241.0)
+    oc.cy = gc.cy = h / 2.0
+    M = CC.lidar_to_camera()
+    q, t = np.array([0.0, 0.0, 0.0, 1.0]), np.array([1.0, 2.0, 3.0])
+    clouds = [CC.random_cloud(20000, seed=70 + s, zmax=80.0) for s in range(5)]
+    images = [CC.noise_image(h, w, seed=80 + s) for s in range(5)]
+    ref = []
+    for s in range(5):
+        mb = lmono_amd.MapBuilder(gpu_ctx, gc, max_cloud_points=len(clouds[s]))
+        n = mb.associate(clouds[s], M, images[s], q, t)
+        ref.append((n, mb.depth(), mb.cloud(0), mb.cloud(1)))
+        mb.close()
+    assert all(r[0] > 0 for r in ref)
+    dc = [torch.from_numpy(c).to("cuda:0") for c in clouds]; di = [torch.from_numpy(i).to("cuda:0") for i in images]
+    torch.cuda.synchronize()
+    lead = lmono_amd.MapBuilder(gpu_ctx, gc, max_cloud_points=16, map_capacity_points=3 * w * h)
+    for n_streams in (1, 2, 5):
+        mbs = [lead] + [lmono_amd.MapBuilder(gpu_ctx, gc, max_cloud_points=16, map_capacity_points=w * h) for _ in range(n_streams - 1)]
+        n = lmono_amd.MapBuilder.associate_batch(gpu_ctx, mbs, [x.data_ptr() for x in dc[:n_streams]], [len(c) for c in clouds[:n_streams]], [M] * n_streams,
+                                                 [x.data_ptr() for x in di[:n_streams]], [q] * n_streams, [t] * n_streams)
+        for s in range(n_streams):
+            assert n[s] == ref[s][0] and (mbs[s].depth() == ref[s][1]).all()
+            assert mbs[s].cloud(0).tobytes() == ref[s][2].tobytes() and mbs[s].cloud(1).tobytes() == ref[s][3].tobytes(), (n_streams, s)
+        for m in mbs[1:]:
+            m.close()
+    assert lead.map().tobytes() == np.concatenate([ref[0][3]] * 3).tobytes()
+    lead.close()

@@ -378,3 +378,42 @@ def test_host_mirror_keyframe_test_equals_python_path(gpu_ctx, tmp_path):
     assert res.stdout.splitlines() == lines
     assert count > 0
     trk.close(); kf.close()
+
+
+def test_lead_store_tables_grow_and_are_reused(gpu_ctx):
+    """add_batch led by one store with 1, then 3, then 5 stores (its job table grows 1 -> 4 -> 8 entries), then on that store matches
+    against 3, 9, 17 and 3 old keyframes (the eight match arrays grow 4 -> 16 -> 32 entries and are reused): every result equals the
+    restatement.  320 x 240 is the smallest image of this file."""
+    import torch
+    import lmono_amd
+    w, h, n = 320, 240, 5
+    pat = _pattern()
+    gc, rc = _cam(w, h)
+    imgs = [s5.Sequence(w, h, 1, seed=50 + s).frames[0] for s in range(n)]
+    uvs = [_window_points(w, h, 40 + 10 * s, 60 + s) for s in range(n)]
+    refs = [K.KeyFrameRef(rc, pat, imgs[s], uvs[s]) for s in range(n)]
+    dev = [torch.from_numpy(np.ascontiguousarray(i)).to("cuda:0") for i in imgs]
+    torch.cuda.synchronize()
+    lead = lmono_amd.KeyFrames(gpu_ctx, gc, pat, 24, 4096)
+    for rnd, n_stores in enumerate((1, 3, 5)):
+        stores = [lead] + [lmono_amd.KeyFrames(gpu_ctx, gc, pat, 1, 4096) for _ in range(n_stores - 1)]
+        idx, nkp = lmono_amd.KeyFrames.add_batch(stores, [t.data_ptr() for t in dev[:n_stores]], uvs[:n_stores])
+        for s in range(n_stores):
+            assert (idx[s], nkp[s]) == (rnd if s == 0 else 0, len(refs[s].keypoints))
+            _check_keyframe(stores[s].get(idx[s]), refs[s], "%d stores, stream %d" % (n_stores, s))
+        for k in stores[1:]:
+            k.close()
+    rng = np.random.default_rng(61)
+    olds = [(refs[0].keypoints, refs[0].norm, refs[0].descriptors)] * 3 + [_random_old(rng, int(v)) for v in rng.integers(1, 600, 17)]
+    for kp, nm, de in olds[3:]:
+        lead.load(kp, nm, de)
+    cur = np.stack([olds[3 + i % 17][2][i % len(olds[3 + i % 17][2])] for i in range(64)])
+    cur[::2, 3] ^= np.uint32(0x00f0f00f)                     # every other one 12 bits away from its source
+    ci = lead.load(np.zeros((0, 2), np.float32), np.zeros((0, 2), np.float32), np.zeros((0, 8), np.uint32), rng.uniform(0, 300, (64, 2)).astype(np.float32), cur)
+    assert ci == 20
+    for n_old in (3, 9, 17, 3):
+        which = list(range(20 - n_old, 20))
+        got = lead.match(ci, which)
+        _check_match(got, cur, [olds[o] for o in which])
+        assert got["counts"].sum() > 0
+    lead.close()

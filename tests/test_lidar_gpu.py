@@ -515,3 +515,18 @@ def test_fall_back_search_changes_nothing_in_any_schedule(oracle, gpu_ctx, n_lin
             assert np.array_equal(a, b_)
     ref = oracle.run_sequence(xyzi, off, n_lines, min_range)
     assert np.abs(out[0][0] - ref["incr"]).max() < 1e-9
+
+
+def test_odometry_workspace_regrown_for_more_chains(oracle, gpu_ctx):
+    """One batch runs the odometry with one chain and then with two: the workspace is allocated again at the larger size (the outgrown one
+    stays with the batch).  The two-chain increments equal those of a fresh batch that only ever ran two chains."""
+    w = oracle.S1World(n_az=500)
+    xyzi, off = w.scans(w.trajectory(4))
+    batch = _register(gpu_ctx, xyzi, off)
+    one, _ = batch.odometry(1, 0)
+    two, _ = batch.odometry(2, 1)
+    fresh = _register(gpu_ctx, xyzi, off)
+    ref, _ = fresh.odometry(2, 1)
+    assert two.tobytes() == ref.tobytes()
+    assert np.abs(one[1:, 4:]).max() > 0.1 and np.abs(two[1:, 4:]).max() > 0.1      # both runs found the motion (~0.8 m per scan)
+    batch.close(); fresh.close()

@@ -216,3 +216,43 @@ def test_bgr_reset_and_error_returns(gpu_ctx):
         fresh.lk(np.zeros((3, 2), np.float32))
     for t in (tr, tg, fresh):
         t.close()
+
+
+def test_lead_tracker_job_table_grows_and_is_reused(gpu_ctx):
+    """One lead tracker drives batches of 1, 3, 5 and 1 streams: its job table grows twice (1 -> 4 -> 8 entries) and is then reused.  The
+    other trackers of a batch are fresh, the lead goes on from the batch before; every stream's records at every frame equal those of a
+    single-stream tracker fed the same frames.  63 x 47 is the smallest image of this file (two pyramid levels)."""
+    import ctypes
+    import torch
+    import lmono_amd
+    w, h, n_frames, sizes = 63, 47, 3, (1, 3, 5, 1)
+    gc, _ = _cam(w, h)
+    rng = np.random.default_rng(41)
+    # blocky noise moved by (1, 0.5) px per frame: corners at the block joints, tracked from frame to frame
+    worlds = [np.kron(rng.integers(0, 256, (16, 20), dtype=np.uint8), np.ones((4, 4), np.uint8)) for _ in range(max(sizes))]
+    frames = [[np.ascontiguousarray(wd[f // 2:f // 2 + h, f:f + w]) for f in range(n_frames)] for wd in worlds]
+    cnts = [30, 17, 40, 8, 25]
+
+    def single(s, n_rounds):
+        tr = lmono_amd.FeatureTracker(gpu_ctx, gc, cnts[s], 4)
+        out = [tr.track(0.05 * k, frames[s][k % n_frames]) for k in range(n_rounds * n_frames)]
+        tr.close()
+        return out
+    ref = [single(s, len(sizes) if s == 0 else 1) for s in range(max(sizes))]
+    assert all(len(r) > 0 for r in ref[0]) and any((r["track_cnt"] > 1).any() for r in ref[0])
+    lead = lmono_amd.FeatureTracker(gpu_ctx, gc, cnts[0], 4)
+    for rnd, n in enumerate(sizes):
+        batch = lmono_amd.FeatureTrackerBatch(gpu_ctx, [gc] * n, cnts[:n], 4)
+        batch.trackers[0].close()
+        batch.trackers[0] = lead
+        batch._handles = (ctypes.c_void_p * n)(*[t.h for t in batch.trackers])
+        for f in range(n_frames):
+            dev = [torch.from_numpy(frames[s][f]).to("cuda:0") for s in range(n)]
+            torch.cuda.synchronize()
+            out = batch.track([0.05 * (rnd * n_frames + f)] + [0.05 * f] * (n - 1), [d.data_ptr() for d in dev])
+            _same(out[0], ref[0][rnd * n_frames + f], "lead, batch of %d, frame %d" % (n, f))
+            for s in range(1, n):
+                _same(out[s], ref[s][f], "stream %d of %d, frame %d" % (s, n, f))
+        for t in batch.trackers[1:]:
+            t.close()
+    lead.close()

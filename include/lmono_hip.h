@@ -474,7 +474,8 @@ int lmono_tracker_reject_f(lmono_ctx *, lmono_tracker *, int n, const float *pre
  * one rounding) are definitions of this project, written out in DESIGN.md 6f: parity with cv::FAST and cv::GaussianBlur is unpinned.
  * BRIEF and the search follow the reference's source statement by statement.  The test pattern is an argument (the reference reads
  * brief_pattern.yml from BRIEF_PATTERN_FILE at run time).  Keypoints are in row-major order (y, then x).
- * Not provided: db.query / db.add (DBoW2; the vocabulary is absent), PnPRANSAC and everything behind it (:551-688), the USE_ORB
+ * PnPRANSAC and the rest of findConnection (:296-351, :551-688) are lmono_keyframes_verify below.
+ * Not provided: db.query / db.add (DBoW2; the vocabulary is absent: the caller chooses the candidate old keyframes), the USE_ORB
  * branch, the thumbnail, distributionValidation (dead code), every DEBUG_IMAGE product.                                              */
 typedef struct { int8_t x1[256], y1[256], x2[256], y2[256]; } lmono_brief_pattern;   /* every offset in -63..63 */
 typedef struct lmono_keyframes lmono_keyframes;
@@ -512,6 +513,46 @@ int lmono_keyframes_images(lmono_ctx *, lmono_keyframes *, uint8_t *blur_h, uint
  * [m][2], window descriptors [m][8]; call once with NULL arrays for the counts */
 int lmono_keyframes_get(lmono_ctx *, lmono_keyframes *, int index, int *n_keypoints, float *keypoints_h, float *norm_h, uint32_t *descriptors_h,
                         int *n_window, float *window_uv_h, uint32_t *window_descriptors_h);
+
+/* ---- loop verification -------------------------------------------------------------------------------------------
+ * KeyFrame::PnPRANSAC (KeyFrame.cc:296-351) and the gates of findConnection (:551-688).  The PnP step is a RANSAC of this project's
+ * own definition, written out in DESIGN.md 6g: exactly n_hyp hypotheses of 4 pairs each from the counter-based sample stream of the
+ * tracker's rejection keyed by (seed, a caller-given key, hypothesis, draw), every one 12 damped Gauss-Newton steps from the guess in
+ * fp64 (K = I), scored against `threshold` on the normalised plane; the winner (most inliers, then the lowest hypothesis) is refitted
+ * over its inliers.  Parity with cv::solvePnPRansac is unpinned.  Fewer than 4 pairs: the step does not run (stats all -1); no valid
+ * hypothesis or fewer than 4 inliers: status all 0 and the pose is the guess unchanged.  Poses are t (x y z), q (x y z w).            */
+typedef struct {
+    double threshold;                 /* 0 -> 10.0 / 460.0 (:328)                                    */
+    int32_t n_hyp;                    /* 0 -> 256, at most 1024                                      */
+    uint32_t seed;
+    int32_t min_brief_loop_num;       /* MIN_BRIEF_LOOP_NUM, 0 -> 25                                 */
+    int32_t min_pnp_loop_num;         /* MIN_PNP_LOOP_NUM, 0 -> 5                                    */
+    double angle_threshold;           /* ANGLE_THRESHOLD (degrees), 0 -> 30                          */
+    double trans_threshold;           /* TRANS_THRESHOLD (m), 0 -> 20                                */
+} lmono_pnp_params;
+/* The PnP step alone on n (1..65535) independent problems in one launch (params may be NULL: the defaults; the gates are not read).
+ * counts_h [n] pairs per problem (0..512; more: LMONO_ECAPACITY); points_3d_h [sum][3] and points_2d_h [sum][2] (normalised image
+ * points) concatenated in problem order; guess_tq_h [n][7] camera-from-world; keys_h [n] the sample stream's key of each problem.
+ * Outputs: status_h [sum] (1: inlier of the winner), pose_tq_h [n][7] (optional), stats_h [n][4] (optional) = valid hypotheses, best
+ * hypothesis, the winner's inliers, refit steps run (all -1: the step did not run).  A problem's bytes do not depend on its batch. */
+int lmono_pnp_ransac(lmono_ctx *, const lmono_pnp_params *, int n, const int32_t *counts_h, const float *points_3d_h, const float *points_2d_h,
+                     const double *guess_tq_h, const uint32_t *keys_h, uint8_t *status_h, double *pose_tq_h, int32_t *stats_h);
+/* findConnection of keyframe `cur` against n_old stored keyframes: lmono_keyframes_match, the matched pairs compacted on the device,
+ * the PnP step over every candidate in one launch (key: cur << 16 | old index -- a store holds at most 65535 keyframes, so no two pairs
+ * of one store share a key; a candidate whose match count is at or below
+ * min_brief_loop_num skips it, :557), one read-back, then on the host :341-350, :570-588 and :636-682.
+ * point_3d_h [n_window of cur][3]: point_3d of the current keyframe's window points (world frame); vio_tq [7]: origin_vio_T / _R;
+ * ex_tq [7]: tlc, qlc (camera in body); old_tq_h [n_old][7]: T_w_i, R_w_i of the old keyframes, or NULL (then channel_h must be NULL).
+ * Outputs (any may be NULL), per candidate: brief_counts_h [n_old]; pnp_inliers_h [n_old] (0 when the step did not run or failed);
+ * status_h [n_old][n_window] after both reductions; pnp_tq_old_h [n_old][7] PnP_T_old, PnP_R_old; loop_info_h [n_old][8] in the
+ * layout lmono_pose_graph_create reads; has_loop_h [n_old]: count > min_brief_loop_num && inliers > min_pnp_loop_num &&
+ * |relative_euler| < angle_threshold && |relative_t| < trans_threshold; channel_h [n_old][15]: old_T, old_Q (w x y z), correct_T,
+ * correct_Q (w x y z), cur; relative_euler_h [n_old][3] (degrees); pose_tq_h [n_old][7] and stats_h [n_old][4] as in lmono_pnp_ransac.
+ * Where the step did not run or failed, the pose is the guess of :308-312 and everything derived from a pose is derived from it. */
+int lmono_keyframes_verify(lmono_ctx *, lmono_keyframes *, int cur, int n_old, const int32_t *old_indices, const float *point_3d_h, const double *vio_tq,
+                           const double *ex_tq, const double *old_tq_h, const lmono_pnp_params *, int32_t *brief_counts_h, int32_t *pnp_inliers_h,
+                           uint8_t *status_h, double *pnp_tq_old_h, double *loop_info_h, uint8_t *has_loop_h, double *channel_h, double *relative_euler_h,
+                           double *pose_tq_h, int32_t *stats_h);
 
 /* ---- loop-closure pose graph -- NEW FEATURE, no counterpart in the reference --------------------------
  * The reference detects loops and publishes loop_info = relative_t, relative_q (w x y z), relative_yaw

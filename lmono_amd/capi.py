@@ -19,7 +19,7 @@ SYMBOLS = [
     "lmono_tracker_create", "lmono_tracker_destroy", "lmono_tracker_reset", "lmono_tracker_track", "lmono_tracker_track_batch", "lmono_tracker_pyramid",
     "lmono_tracker_response", "lmono_tracker_lk", "lmono_tracker_set_reject_f", "lmono_tracker_reject_stats", "lmono_tracker_reject_f",
     "lmono_keyframes_create", "lmono_keyframes_destroy", "lmono_keyframes_clear", "lmono_keyframes_size", "lmono_keyframes_add", "lmono_keyframes_add_batch",
-    "lmono_keyframes_load", "lmono_keyframes_match", "lmono_keyframes_images", "lmono_keyframes_get",
+    "lmono_keyframes_load", "lmono_keyframes_match", "lmono_keyframes_images", "lmono_keyframes_get", "lmono_keyframes_verify", "lmono_pnp_ransac",
     "lmono_pose_graph_create", "lmono_pose_graph_destroy", "lmono_pose_graph_reset", "lmono_pose_graph_info", "lmono_pose_graph_order", "lmono_pose_graph_reduce_buffer", "lmono_pose_graph_set_reduce_buffer", "lmono_pose_graph_linearise",
     "lmono_pose_graph_step", "lmono_pose_graph_optimize", "lmono_pose_graph_result", "lmono_factor_eval", "lmono_factor_eval_d", "lmono_factor_eval_blocks", "lmono_factor_eval_blocks_d",
     "lmono_triangulate", "lmono_outlier_scores", "lmono_shift_depth", "lmono_shift_depth_batch", "lmono_marginalize", "lmono_marg_evaluate", "lmono_marg_second_new", "lmono_ba_batch_create", "lmono_ba_batch_update", "lmono_ba_batch_destroy", "lmono_ba_solve", "lmono_ba_batch_reset", "lmono_ba_batch_read", "lmono_debug_bounds",
@@ -105,6 +105,7 @@ def load_library():
     L.lmono_pose_prefix_d.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
     L.lmono_pose_rebase_d.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int]
     L.lmono_timing_read.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+    L.lmono_pnp_ransac.argtypes = [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 8
     _lib = L
     return L
 
@@ -1022,6 +1023,36 @@ def _keyframes_prototypes(L):
     L.lmono_keyframes_match.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 7
     L.lmono_keyframes_images.argtypes = [C.c_void_p] * 4
     L.lmono_keyframes_get.argtypes = [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 7
+    L.lmono_keyframes_verify.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 16
+
+
+class PnPParams(C.Structure):
+    """lmono_pnp_params: the PnP threshold on the normalised plane, hypothesis count and sample seed, and the gates of findConnection
+    (MIN_BRIEF_LOOP_NUM, MIN_PNP_LOOP_NUM, ANGLE_THRESHOLD in degrees, TRANS_THRESHOLD in m).  A field left 0 takes its default:
+    10 / 460, 256, 25, 5, 30, 20."""
+    _fields_ = [("threshold", C.c_double), ("n_hyp", C.c_int32), ("seed", C.c_uint32), ("min_brief_loop_num", C.c_int32), ("min_pnp_loop_num", C.c_int32),
+                ("angle_threshold", C.c_double), ("trans_threshold", C.c_double)]
+
+
+def pnp_ransac(ctx, points_3d, points_2d, guess_tq, keys=None, params=None):
+    """The PnP step of the loop verification (lmono_pnp_ransac) on a batch of problems in one launch.  points_3d: a list
+    of [m, 3] arrays (m <= 512), points_2d: a list of [m, 2] normalised image points, guess_tq: [n, 7] camera-from-world guesses
+    t (x y z), q (x y z w), keys: [n] uint32 sample-stream keys (default 0) -> (list of status [m] uint8, pose [n, 7], stats [n, 4])."""
+    L = ctx.L
+    p3 = [np.ascontiguousarray(a, np.float32).reshape(-1, 3) for a in points_3d]
+    p2 = [np.ascontiguousarray(a, np.float32).reshape(-1, 2) for a in points_2d]
+    n = len(p3)
+    g = np.ascontiguousarray(guess_tq, np.float64).reshape(-1, 7)
+    ky = np.zeros(n, np.uint32) if keys is None else np.ascontiguousarray(keys, np.uint32).reshape(-1)
+    if len(p2) != n or len(g) != n or len(ky) != n or any(len(a) != len(b) for a, b in zip(p3, p2)):
+        raise LmonoError("pnp_ransac: points_3d, points_2d, guess_tq and keys differ in length")
+    cnt = np.array([len(a) for a in p3], np.int32)
+    a3 = np.concatenate(p3 + [np.zeros((1, 3), np.float32)]); a2 = np.concatenate(p2 + [np.zeros((1, 2), np.float32)])
+    st = np.zeros(int(cnt.sum()) + 1, np.uint8); pose = np.zeros((n, 7)); stats = np.zeros((n, 4), np.int32)
+    ctx.check(L.lmono_pnp_ransac(ctx.h, C.byref(params) if params is not None else None, n, cnt.ctypes.data, a3.ctypes.data, a2.ctypes.data, g.ctypes.data,
+                                 ky.ctypes.data, st.ctypes.data, pose.ctypes.data, stats.ctypes.data))
+    off = np.concatenate([[0], np.cumsum(cnt)])
+    return [st[off[i]:off[i + 1]].copy() for i in range(n)], pose, stats
 
 
 class KeyFrames:
@@ -1122,6 +1153,35 @@ class KeyFrames:
         self.ctx.check(self.ctx.L.lmono_keyframes_match(self.ctx.h, self.h, int(cur), n, old.ctypes.data, st.ctypes.data, ix.ctypes.data, di.ctypes.data,
                                                         uv.ctypes.data, nm.ctypes.data, cnt.ctypes.data))
         return {"status": st, "index": ix, "dist": di, "old_uv": uv, "old_norm": nm, "counts": cnt}
+
+    def verify(self, cur, old_indices, point_3d, vio_tq, ex_tq, old_tq=None, params=None):
+        """findConnection of keyframe cur against each of old_indices (lmono_keyframes_verify): the match, the PnP step
+        and the gates.  point_3d: [n_window, 3] world points of cur's window points; vio_tq, ex_tq: [7] t (x y z), q (x y z w) of the
+        body and of the camera in the body; old_tq: [n_old, 7] poses of the old keyframes (for the 15-value channel) or None.
+        -> dict of per-candidate arrays: counts, inliers, status [n_old, n_window], pnp_tq_old [n_old, 7], loop_info [n_old, 8],
+        has_loop [n_old] bool, channel [n_old, 15] or None, relative_euler [n_old, 3], pose [n_old, 7], stats [n_old, 4]; and, ready
+        for PoseGraph(poses, loops, loop_info): loops [k, 2] (old, cur) and loops_info [k, 8] of the candidates with has_loop."""
+        old = np.ascontiguousarray(old_indices, np.int32).reshape(-1)
+        nw = C.c_int(0)
+        self.ctx.check(self.ctx.L.lmono_keyframes_get(self.ctx.h, self.h, int(cur), None, None, None, None, C.addressof(nw), None, None))
+        n, m = len(old), nw.value
+        p3 = np.ascontiguousarray(point_3d, np.float32).reshape(-1, 3)
+        if len(p3) != m:
+            raise LmonoError("verify: point_3d must have one row per window point of the current keyframe (%d)" % m)
+        vio = np.ascontiguousarray(vio_tq, np.float64).reshape(7); ex = np.ascontiguousarray(ex_tq, np.float64).reshape(7)
+        otq = None if old_tq is None else np.ascontiguousarray(old_tq, np.float64).reshape(-1, 7)
+        if otq is not None and len(otq) != n:
+            raise LmonoError("verify: old_tq must have one pose per old index")
+        cnt = np.zeros(n, np.int32); inl = np.zeros(n, np.int32); st = np.zeros((n, m), np.uint8); tq = np.zeros((n, 7)); li = np.zeros((n, 8))
+        hl = np.zeros(n, np.uint8); ch = None if otq is None else np.zeros((n, 15)); eu = np.zeros((n, 3)); pose = np.zeros((n, 7)); stats = np.zeros((n, 4), np.int32)
+        self.ctx.check(self.ctx.L.lmono_keyframes_verify(self.ctx.h, self.h, int(cur), n, old.ctypes.data, p3.ctypes.data if m else None, vio.ctypes.data, ex.ctypes.data,
+                                                         None if otq is None else otq.ctypes.data, C.byref(params) if params is not None else None,
+                                                         cnt.ctypes.data, inl.ctypes.data, st.ctypes.data, tq.ctypes.data, li.ctypes.data, hl.ctypes.data,
+                                                         None if ch is None else ch.ctypes.data, eu.ctypes.data, pose.ctypes.data, stats.ctypes.data))
+        has = hl.astype(bool)
+        loops = np.stack([old[has], np.full(int(has.sum()), int(cur), np.int32)], 1).astype(np.int32)
+        return {"counts": cnt, "inliers": inl, "status": st, "pnp_tq_old": tq, "loop_info": li, "has_loop": has, "channel": ch, "relative_euler": eu,
+                "pose": pose, "stats": stats, "loops": loops, "loops_info": li[has]}
 
     def clear(self):
         self.ctx.check(self.ctx.L.lmono_keyframes_clear(self.ctx.h, self.h))

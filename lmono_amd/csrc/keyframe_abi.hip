@@ -1,6 +1,7 @@
 // keyframe_abi.hip -- C ABI of the keyframe descriptor store (included by lmono_hip.hip after lmono_ctx is defined)
 #pragma once
 #include "keyframe.hip"
+#include "pnp.hip"
 
 struct lmono_keyframes {
     lmono_ctx *ctx = nullptr;
@@ -29,6 +30,14 @@ struct lmono_keyframes {
     unsigned int *m_keys = nullptr;
     unsigned char *m_status = nullptr;
     float2 *m_uv = nullptr, *m_norm = nullptr;
+    // lmono_keyframes_verify (pnp_abi.hip): the current keyframe's 3-D points, and per candidate job, status, pose [7] and stats [4]
+    int verify_cap = 0;
+    float *v_p3 = nullptr;
+    PnpJob *v_jobs = nullptr;
+    std::vector<PnpJob> v_jobs_h;                        // the upload's source: outlives every early return
+    unsigned char *v_status = nullptr;
+    double *v_pose = nullptr;
+    int *v_stats = nullptr;
 };
 
 extern "C" void lmono_keyframes_destroy(lmono_keyframes *k) { delete k; }
@@ -172,20 +181,11 @@ extern "C" int lmono_keyframes_load(lmono_ctx *c, lmono_keyframes *k, int n_keyp
     return LMONO_OK;
 }
 
-extern "C" int lmono_keyframes_match(lmono_ctx *c, lmono_keyframes *k, int cur, int n_old, const int32_t *old_indices, uint8_t *status_h, int32_t *index_h, int32_t *dist_h,
-                                     float *old_uv_h, float *old_norm_h, int32_t *counts_h)
+// The search of lmono_keyframes_match queued on the stream, its results left in the store's m_* arrays (nothing is read back or waited
+// for).  The arguments are the caller's to check; n_win of cur is > 0.  Shared with lmono_keyframes_verify (pnp_abi.hip)
+static int kf_match_launch(lmono_ctx *c, lmono_keyframes *k, int cur, int n_old, const int32_t *old_indices, int max_kp)
 {
-    if (!c || !k || k->ctx != c || cur < 0 || cur >= k->n_kf || n_old < 1 || n_old > 65535 || !old_indices) return LMONO_EINVAL;
-    int max_kp = 0;
-    for (int o = 0; o < n_old; o++) {
-        if (old_indices[o] < 0 || old_indices[o] >= k->n_kf) { c->err = "lmono_keyframes_match: an old index is not a stored keyframe"; return LMONO_EINVAL; }
-        max_kp = std::max(max_kp, k->n_kp_h[(size_t)old_indices[o]]);
-    }
     const int n_win = k->n_win_h[(size_t)cur];
-    if (n_win == 0) {
-        for (int o = 0; o < n_old && counts_h; o++) counts_h[o] = 0;
-        return LMONO_OK;
-    }
     if (k->match_cap < n_old) {
         // eight arrays of one capacity (nothing reads them now: every call ends synchronised).  match_cap is 0 from a failed growth to the next call, which grows all eight again
         const int old = k->match_cap;
@@ -207,7 +207,25 @@ extern "C" int lmono_keyframes_match(lmono_ctx *c, lmono_keyframes *k, int cur, 
     k_kf_match<<<dim3(shares, (unsigned)n_old), kKfT, 0, c->stream>>>(mj);
     if (int rc = check_launch(c, "k_kf_match")) return rc;
     k_kf_match_finish<<<(unsigned)n_old, kKfMaxWin, 0, c->stream>>>(mj);
-    if (int rc = check_launch(c, "k_kf_match_finish")) return rc;
+    return check_launch(c, "k_kf_match_finish");
+}
+
+extern "C" int lmono_keyframes_match(lmono_ctx *c, lmono_keyframes *k, int cur, int n_old, const int32_t *old_indices, uint8_t *status_h, int32_t *index_h, int32_t *dist_h,
+                                     float *old_uv_h, float *old_norm_h, int32_t *counts_h)
+{
+    if (!c || !k || k->ctx != c || cur < 0 || cur >= k->n_kf || n_old < 1 || n_old > 65535 || !old_indices) return LMONO_EINVAL;
+    int max_kp = 0;
+    for (int o = 0; o < n_old; o++) {
+        if (old_indices[o] < 0 || old_indices[o] >= k->n_kf) { c->err = "lmono_keyframes_match: an old index is not a stored keyframe"; return LMONO_EINVAL; }
+        max_kp = std::max(max_kp, k->n_kp_h[(size_t)old_indices[o]]);
+    }
+    const int n_win = k->n_win_h[(size_t)cur];
+    if (n_win == 0) {
+        for (int o = 0; o < n_old && counts_h; o++) counts_h[o] = 0;
+        return LMONO_OK;
+    }
+    if (int rc = kf_match_launch(c, k, cur, n_old, old_indices, max_kp)) return rc;
+    const size_t e = (size_t)n_old * n_win;
     if (status_h) HIP_TRY(c, hipMemcpyAsync(status_h, k->m_status, e, hipMemcpyDeviceToHost, c->stream));
     if (index_h) HIP_TRY(c, hipMemcpyAsync(index_h, k->m_index, sizeof(int) * e, hipMemcpyDeviceToHost, c->stream));
     if (dist_h) HIP_TRY(c, hipMemcpyAsync(dist_h, k->m_dist, sizeof(int) * e, hipMemcpyDeviceToHost, c->stream));

@@ -1,5 +1,6 @@
 // lmono_amd/host/keyframe.cpp -- see keyframe.hpp
 #include "keyframe.hpp"
+#include "../csrc/pnp.hip"      // plain C++ here: pnp_guess, pnp_after
 #include <cstdlib>
 #include <fstream>
 #include <map>
@@ -116,6 +117,54 @@ bool KeyFrame::findConnection(const KeyFrame *old_kf, std::vector<Point2f> &matc
     reduceVector(matched_2d_cur, status); reduceVector(matched_2d_old, status); reduceVector(matched_2d_cur_norm, status);
     reduceVector(matched_2d_old_norm, status); reduceVector(matched_3d, status); reduceVector(matched_id, status);
     return (int)matched_2d_cur.size() > MIN_BRIEF_LOOP_NUM;                                                               // :557
+}
+
+void KeyFrame::PnPRANSAC(const std::vector<Point2f> &matched_2d_old_norm, const std::vector<Point3f> &matched_3d, std::vector<unsigned char> &status,
+                         double *PnP_T_old, double *PnP_q_old, uint32_t key)
+{
+    if (matched_2d_old_norm.size() != matched_3d.size()) throw std::runtime_error("PnPRANSAC: matched_2d_old_norm and matched_3d differ in length");
+    const int32_t m = (int32_t)matched_3d.size();
+    lmono::PnpPose G;
+    lmono::pnp_guess(origin_vio_tq, ex_tq, G);                                   // :308-312
+    double guess[7] = { G.t[0], G.t[1], G.t[2], G.q[0], G.q[1], G.q[2], G.q[3] }, pose[7];
+    const size_t at = status.size();
+    status.resize(at + (size_t)m + 1);                                           // + 1: an address to hand over when m is 0
+    store_.hip().check(lmono_pnp_ransac(store_.hip().get(), &pnp_params, 1, &m, m ? &matched_3d[0].x : nullptr, m ? &matched_2d_old_norm[0].x : nullptr, guess, &key,
+                                        &status[at], pose, nullptr), "lmono_pnp_ransac");
+    status.resize(at + (size_t)m);
+    lmono::PnpLoop L;
+    lmono::pnp_after(pose, origin_vio_tq, ex_tq, 0.0, 0.0, L);                   // :341-350
+    for (int e = 0; e < 3; e++) PnP_T_old[e] = L.t_old[e];
+    for (int e = 0; e < 4; e++) PnP_q_old[e] = L.q_old[e];
+}
+
+bool KeyFrame::findConnection(const KeyFrame *old_kf)
+{
+    const size_t n = point_2d_uv.size();
+    if (point_3d.size() != n || point_2d_norm.size() != n || point_id.size() != n) throw std::runtime_error("findConnection: point_3d, point_2d_norm and point_id must match point_2d_uv");
+    const int32_t old_index = old_kf->store_index;
+    std::vector<unsigned char> status(n + 1);
+    std::vector<Point2f> old_norm(n + 1);
+    int32_t brief = 0, inliers = 0;
+    uint8_t has = 0;
+    double info[8], channel[15];
+    lmono_ctx *c = store_.hip().get();
+    store_.hip().check(lmono_keyframes_verify(c, store_.get(), store_index, 1, &old_index, n ? &point_3d[0].x : nullptr, origin_vio_tq, ex_tq, old_kf->T_w_i_tq, &pnp_params,
+                                              &brief, &inliers, status.data(), nullptr, info, &has, channel, nullptr, nullptr, nullptr), "lmono_keyframes_verify");
+    matched_brief = brief; matched_pnp = inliers;
+    if (!has) return false;                                                      // :689-690
+    // the matched old points of the survivors: the search's output for this pair, reduced by the status after both reductions
+    store_.hip().check(lmono_keyframes_match(c, store_.get(), store_index, 1, &old_index, nullptr, nullptr, nullptr, nullptr, &old_norm[0].x, nullptr), "lmono_keyframes_match");
+    status.resize(n); old_norm.resize(n);
+    point_loop_2d_norm = point_2d_norm; point_old_2d_norm = old_norm; point_loop_id = point_id;              // :590-592
+    reduceVector(point_loop_2d_norm, status); reduceVector(point_old_2d_norm, status); reduceVector(point_loop_id, status);
+    has_loop = true; loop_index = old_kf->index;                                 // :636-637
+    for (int e = 0; e < 8; e++) loop_info[e] = info[e];
+    published.stamp = time_stamp; published.points.clear();
+    for (size_t i = 0; i < point_old_2d_norm.size(); i++) published.points.push_back({ point_old_2d_norm[i].x, point_old_2d_norm[i].y, (float)point_loop_id[i] });
+    for (int e = 0; e < 14; e++) published.t_q_index[e] = channel[e];
+    published.t_q_index[14] = (double)index;                                     // :681: the keyframe's own index, not its slot in the store
+    return true;
 }
 
 } // namespace lmono_host

@@ -1,7 +1,8 @@
 // lmono_amd/host/keyframe.hpp -- host-side mirror of KeyFrame (mono_lidar_mapping/include/loop_detection/KeyFrame.h) over the device
 // keyframe store of the C ABI (lmono_keyframes_*).  A KeyFrame keeps the reference's members on the host (they are read
 // back once, when it is built) and its slot in the store; searchByBRIEFDes and findConnection run the search on the device.
-// Not mirrored: the DBoW2 database, PnPRANSAC and what follows it (KeyFrame.cc:551-688), the USE_ORB branch, the thumbnail, DEBUG_IMAGE.
+// PnPRANSAC and findConnection to its end (KeyFrame.cc:296-351, :551-688) run on the device too (lmono_pnp_ransac, lmono_keyframes_verify).
+// Not mirrored: the DBoW2 database, the USE_ORB branch, the thumbnail, DEBUG_IMAGE; the ROS message of :644-684 is the plain struct LoopMessage.
 #pragma once
 #include <array>
 #include <string>
@@ -15,6 +16,14 @@ struct Point3f { float x, y, z; };
 typedef std::array<uint32_t, 8> BriefBits;           // BRIEF::bitset of 256 bits: bit i is bit i & 31 of word i >> 5
 
 constexpr int MIN_BRIEF_LOOP_NUM = 25;               // kitti_config_00.yaml:48
+
+// what :644-684 publishes on pub_matched_points_: one point (old normalised x, y, feature id) per verified match and the channel
+// [old_T, old_Q (w x y z), correct_T, correct_Q (w x y z), index]
+struct LoopMessage {
+    double stamp = 0.0;
+    std::vector<Point3f> points;
+    double t_q_index[15] = { 0 };
+};
 
 // BRIEF_PATTERN_FILE: an OpenCV-YAML file in the list layout of the reference's brief_pattern.yml (`x1:` followed by one `- <integer>` line
 // per entry, likewise y1, x2, y2).  Throws std::runtime_error unless it finds exactly 256 entries per key, each in -63..63.
@@ -50,6 +59,16 @@ public:
     bool findConnection(const KeyFrame *old_kf, std::vector<Point2f> &matched_2d_cur, std::vector<Point2f> &matched_2d_old, std::vector<Point2f> &matched_2d_cur_norm,
                         std::vector<Point2f> &matched_2d_old_norm, std::vector<Point3f> &matched_3d, std::vector<int> &matched_id);
 
+    // KeyFrame.cc:296-351: solvePnPRansac of the matched pairs from the guess of :308-312 (origin_vio_tq, ex_tq) -> status (appended, one
+    // byte per pair), PnP_T_old [3] and PnP_q_old [4] (x y z w).  The RANSAC is the definition of DESIGN.md 6g (lmono_pnp_ransac);
+    // key selects its sample stream
+    void PnPRANSAC(const std::vector<Point2f> &matched_2d_old_norm, const std::vector<Point3f> &matched_3d, std::vector<unsigned char> &status,
+                   double *PnP_T_old, double *PnP_q_old, uint32_t key = 0);
+    // KeyFrame.cc:354-691 in one device call (lmono_keyframes_verify): the match, PnPRANSAC, the three gates.  On true it has set has_loop,
+    // loop_index, loop_info, point_loop_2d_norm, point_old_2d_norm, point_loop_id and published.  matched_brief / matched_pnp: the counts
+    // compared with MIN_BRIEF_LOOP_NUM and MIN_PNP_LOOP_NUM
+    bool findConnection(const KeyFrame *old_kf);
+
     double time_stamp;
     int index;
     int store_index;                                  // slot in the device store
@@ -61,6 +80,14 @@ public:
     int sequence;
     bool has_loop;
     int loop_index;
+    // poses as t (x y z), q (x y z w): origin_vio_T / origin_vio_R, T_w_i / R_w_i, and the camera in the body (tlc, qlc); identity until set
+    double origin_vio_tq[7] = { 0, 0, 0, 0, 0, 0, 1 }, T_w_i_tq[7] = { 0, 0, 0, 0, 0, 0, 1 }, ex_tq[7] = { 0, 0, 0, 0, 0, 0, 1 };
+    lmono_pnp_params pnp_params = { 0.0, 0, 0u, 0, 0, 0.0, 0.0 };      // zeros: the defaults of kitti_loop_config_04.yaml
+    double loop_info[8] = { 0 };                      // relative_t, relative_q (w x y z), relative_yaw (:638-640)
+    std::vector<Point2f> point_loop_2d_norm, point_old_2d_norm;
+    std::vector<int> point_loop_id;
+    LoopMessage published;
+    int matched_brief = 0, matched_pnp = 0;
 
 private:
     KeyFrameStore &store_;

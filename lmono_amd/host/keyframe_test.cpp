@@ -1,10 +1,13 @@
 // lmono_amd/host/keyframe_test.cpp -- frames of an image sequence -> FeatureTracker::trackImage -> a KeyFrame from frame k and one from frame
 // k + delta (window points: the tracker's points of that frame) -> findConnection up to the MIN_BRIEF_LOOP_NUM gate.  Prints the matches.
-//   keyframe_test <frames.raw> <brief_pattern.yml> [k [delta]]
+//   keyframe_test <frames.raw> <brief_pattern.yml> [k [delta [verify]]]
+// With `verify` the same lines are followed by findConnection to its end (PnPRANSAC, the gates, loop_info, the published message): the
+// scene is taken as a fronto-parallel plane at 10 m in front of each camera, the current camera shifted by (0.3, 0.1, 0) m in the world.
 // frames.raw: a text line "<width> <height> <frames>" followed by frames * height * width grey bytes.
 #include <cstdio>
 #include <cstdlib>
 #include <fstream>
+#include <string>
 #include <vector>
 #include "feature_tracker.hpp"
 #include "keyframe.hpp"
@@ -13,8 +16,9 @@ using namespace lmono_host;
 
 int main(int argc, char **argv)
 {
-    if (argc < 3) { std::fprintf(stderr, "usage: keyframe_test <frames.raw> <brief_pattern.yml> [k [delta]]\n"); return 2; }
+    if (argc < 3) { std::fprintf(stderr, "usage: keyframe_test <frames.raw> <brief_pattern.yml> [k [delta [verify]]]\n"); return 2; }
     const int k = argc > 3 ? std::atoi(argv[3]) : 2, delta = argc > 4 ? std::atoi(argv[4]) : 6;
+    const bool verify = argc > 5 && std::string(argv[5]) == "verify";
     try {
         std::ifstream in(argv[1], std::ios::binary);
         int W = 0, H = 0, N = 0;
@@ -37,7 +41,9 @@ int main(int argc, char **argv)
             if (f != k && f != k + delta) continue;
             std::vector<Point3f> p3; std::vector<Point2f> uv, nm; std::vector<int> id;
             for (const lmono_track_record &r : tracker.records) {
-                p3.push_back({ r.x_n, r.y_n, 1.f });            // no depth in this driver: the normalised ray stands in for point_3d
+                // no depth in this driver: the normalised ray stands in for point_3d; with `verify` the ray at 10 m, moved into the world by the camera's shift
+                if (verify) p3.push_back({ r.x_n * 10.f + (f == k ? 0.f : 0.3f), r.y_n * 10.f + (f == k ? 0.f : 0.1f), 10.f });
+                else p3.push_back({ r.x_n, r.y_n, 1.f });
                 uv.push_back({ r.u, r.v }); nm.push_back({ r.x_n, r.y_n }); id.push_back(r.id);
             }
             kfs.emplace_back(store, 0.1 * f, (int)kfs.size(), img, LMONO_TRACK_GREY8, p3, uv, nm, id, 0);
@@ -48,6 +54,32 @@ int main(int argc, char **argv)
         for (size_t i = 0; i < ids.size(); i++)
             std::printf("MATCH %d cur %.9g %.9g old %.9g %.9g old_norm %.9g %.9g\n", ids[i], cur[i].x, cur[i].y, old[i].x, old[i].y, old_n[i].x, old_n[i].y);
         std::printf("keyframe_test ok: %zu of %zu window points matched, gate %d\n", ids.size(), kfs[1].point_2d_uv.size(), connected ? 1 : 0);
+        if (verify) {
+            KeyFrame &cur_kf = kfs[1];
+            cur_kf.origin_vio_tq[0] = 0.3; cur_kf.origin_vio_tq[1] = 0.1;
+            cur_kf.T_w_i_tq[0] = 0.3; cur_kf.T_w_i_tq[1] = 0.1;
+            // PnPRANSAC on the reduced vectors of the seven-argument findConnection above, as :560 calls it
+            std::vector<unsigned char> pnp_status;
+            double T_old[3], q_old[4];
+            cur_kf.PnPRANSAC(old_n, m3, pnp_status, T_old, q_old);
+            int pnp_in = 0;
+            for (unsigned char b : pnp_status) pnp_in += b;
+            std::printf("PNPRANSAC pairs %zu inliers %d T_old %.17g %.17g %.17g q_old %.17g %.17g %.17g %.17g\n", pnp_status.size(), pnp_in, T_old[0], T_old[1], T_old[2],
+                        q_old[0], q_old[1], q_old[2], q_old[3]);
+            const bool loop = cur_kf.findConnection(&kfs[0]);
+            std::printf("VERIFY brief %d pnp %d has_loop %d loop_index %d\n", cur_kf.matched_brief, cur_kf.matched_pnp, loop ? 1 : 0, cur_kf.loop_index);
+            if (loop) {
+                std::printf("LOOP_INFO");
+                for (int e = 0; e < 8; e++) std::printf(" %.9g", cur_kf.loop_info[e]);
+                std::printf("\nCHANNEL");
+                for (int e = 0; e < 15; e++) std::printf(" %.9g", cur_kf.published.t_q_index[e]);
+                std::printf("\n");
+                for (size_t i = 0; i < cur_kf.point_loop_id.size(); i++)
+                    std::printf("LOOP_POINT %d cur_norm %.9g %.9g old_norm %.9g %.9g published %.9g %.9g %.9g\n", cur_kf.point_loop_id[i], cur_kf.point_loop_2d_norm[i].x,
+                                cur_kf.point_loop_2d_norm[i].y, cur_kf.point_old_2d_norm[i].x, cur_kf.point_old_2d_norm[i].y, cur_kf.published.points[i].x,
+                                cur_kf.published.points[i].y, cur_kf.published.points[i].z);
+            }
+        }
     } catch (const std::exception &e) {
         std::fprintf(stderr, "keyframe_test: %s\n", e.what());
         return 1;

@@ -1,7 +1,8 @@
 """scripts/keyframe_bench.py -- throughput of the device keyframe descriptors (lmono_keyframes_*): keyframes/s of
 lmono_keyframes_add_batch for 1, 8, 64 streams at 1241 x 376 with 150 window points, images resident on the device; matches/s of
 lmono_keyframes_match for one current keyframe against 4 and against 1024 stored keyframes; per-kernel times of one 64-stream add and
-of one 1024-keyframe match from the torch profiler's device events.  Prints one JSON line.  One process; run it under `timeout`;
+of one 1024-keyframe match from the torch profiler's device events; verifies/s of lmono_keyframes_verify (match, PnP RANSAC,
+gates) for the same current keyframe against 4 and 1024 candidates, with the device time of k_pnp_ransac.  Prints one JSON line.  One process; run it under `timeout`;
 exits non-zero on any HIP error.
 
   timeout 300 python scripts/keyframe_bench.py [--pattern tests/golden/brief_pattern.yml] [--streams 1,8,64] [--old 4,1024]
@@ -21,8 +22,9 @@ sys.path.insert(0, ROOT)
 def _kernel_times(prof):
     kern = {}
     for e in prof.key_averages():
-        if "k_kf_" in e.key:
-            name = e.key[e.key.index("k_kf_"):].split("(")[0]
+        tag = "k_kf_" if "k_kf_" in e.key else ("k_pnp_" if "k_pnp_" in e.key else None)
+        if tag:
+            name = e.key[e.key.index(tag):].split("(")[0]
             name = name.split("E")[0] if e.key.startswith("_Z") else name
             us = getattr(e, "device_time_total", None)
             if us is None:
@@ -58,7 +60,7 @@ def main():
     ctx = lmono_amd.Context(0)
     cam = lmono_amd.Camera(w, h, 718.856, 718.856, 607.1928, 185.2157, 0.0, 0.0, 0.0, 0.0, 5, 0, 0)
     out = {"bench": "keyframe", "width": w, "height": h, "window": a.window, "max_keypoints": a.max_keypoints, "calls": a.calls, "warmup": a.warmup,
-           "add": [], "match": []}
+           "add": [], "match": [], "verify": []}
     for n in [int(x) for x in a.streams.split(",")]:
         stores = [lmono_amd.KeyFrames(ctx, cam, pat, 2, a.max_keypoints) for _ in range(n)]
         ms, nkp = [], None
@@ -118,6 +120,30 @@ def main():
                 torch.cuda.synchronize()
             run["kernels_us"] = _kernel_times(prof)
         out["match"].append(run)
+    # the same keyframe verified against the same candidates: the window points back-projected to a plane at 10 m, the body at the origin.
+    # Every candidate above the MIN_BRIEF_LOOP_NUM gate runs the full, fixed hypothesis count, so the time does not depend on the geometry
+    K = np.array([[cam.fx, cam.cx], [cam.fy, cam.cy]])
+    p3 = np.stack([(uv[:, 0] - K[0, 1]) / K[0, 0] * 10.0, (uv[:, 1] - K[1, 1]) / K[1, 0] * 10.0, np.full(len(uv), 10.0)], 1).astype(np.float32)
+    ident = np.array([0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 1.0])
+    for n_old in olds:
+        idx = list(range(n_old))
+        ms, v = [], None
+        for f in range(n_img):
+            t0 = time.perf_counter()
+            v = store.verify(cur, idx, p3, ident, ident)                                 # synchronises before it returns
+            dt = (time.perf_counter() - t0) * 1e3
+            if f >= a.warmup:
+                ms.append(dt)
+        ms = np.array(ms)
+        run = {"old_keyframes": n_old, "ms_per_call_median": float(np.median(ms)), "ms_per_call_min": float(ms.min()),
+               "verifies_per_s": float(n_old * 1e3 / np.median(ms)), "pnp_ran": int((v["stats"][:, 0] >= 0).sum()), "loops": int(v["has_loop"].sum())}
+        if not a.no_kernels:
+            from torch.profiler import ProfilerActivity, profile
+            with profile(activities=[ProfilerActivity.CUDA, ProfilerActivity.CPU]) as prof:
+                store.verify(cur, idx, p3, ident, ident)
+                torch.cuda.synchronize()
+            run["kernels_us"] = _kernel_times(prof)
+        out["verify"].append(run)
     store.close()
     print(json.dumps(out))
 

@@ -311,6 +311,8 @@ int lmono_shift_depth_batch(lmono_ctx *, int n_windows, const double *frames_h, 
  * reference passes the never-initialised right_pt here).  Kept blocks, in this order: ex, pose1 .. pose10 (n = 66).
  * lin_J_h [n_windows][66*66] = linearized_jacobians, lin_r_h [n_windows][66] = linearized_residuals (defined up to an
  * orthogonal row transform: compare J^T J and J^T r); status_h bit 0: H_mm needed the eps = 1e-8 cut; bit 1: the QL iteration of the eigen-decomposition hit its 60-sweep cap on an eigenvalue (never seen).
+ * Refused with LMONO_EINVAL before any launch: offsets that do not start at 0 or descend, a null inv_depth / obs_feat / obs_j / obs_pts array
+ * while the counts say it is not empty, observations not grouped by track, obs_j outside 1..10, the same frame twice in one track.
  * lmono_marg_evaluate: residual = r0 + J dx with x0_h / x_h [n_windows][11][7] (ex, pose1..pose10).               */
 int lmono_marginalize(lmono_ctx *, int n_windows, const int *feat_off_h, const int *obs_off_h, const double *poses_h, const double *ex_h,
                       const double *inv_depth_h, const int *obs_feat_h, const int *obs_j_h, const double *obs_pts_h,

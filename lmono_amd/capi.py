@@ -298,7 +298,7 @@ class Context:
         W = len(windows)
         feat_off = np.concatenate([[0], np.cumsum([len(w["invd"]) for w in windows])]).astype(np.int32)
         obs_off = np.concatenate([[0], np.cumsum([len(w["obs_j"]) for w in windows])]).astype(np.int32)
-        cat = lambda k, dt: np.ascontiguousarray(np.concatenate([np.asarray(w[k], dt).reshape(len(w[k]), -1) for w in windows]).ravel(), dt)
+        cat = lambda k, dt: np.ascontiguousarray(np.concatenate([np.asarray(w[k], dt).ravel() for w in windows]), dt)      # (a window may have no tracks)
         poses = np.ascontiguousarray([w["poses"] for w in windows], np.float64); ex = np.ascontiguousarray([w["ex"] for w in windows], np.float64)
         invd = cat("invd", np.float64); of = cat("obs_feat", np.int32); oj = cat("obs_j", np.int32); pts = cat("pts", np.float64)
         l01 = np.ascontiguousarray([w["laser01"] for w in windows], np.float64)

@@ -135,15 +135,25 @@ extern "C" int lmono_marginalize(lmono_ctx *c, int n_windows, const int *feat_of
 {
     if (!c || n_windows <= 0 || !feat_off_h || !obs_off_h || !poses_h || !ex_h || !laser01_h || !laser_info_h || !mono_info_h || !lin_J_h || !lin_r_h) return LMONO_EINVAL;
     HIP_TRY(c, hipSetDevice(c->device));
+    const char *bad = feat_check_offsets(n_windows, feat_off_h);
+    if (!bad) bad = feat_check_offsets(n_windows, obs_off_h);
+    if (bad) { c->err = std::string("lmono_marginalize: ") + bad; return LMONO_EINVAL; }
     const int TF = feat_off_h[n_windows], TO = obs_off_h[n_windows];
+    // an array that the counts say is not empty must be there: up() takes a null source for scratch that nothing has to fill, and the kernel would read it
+    if ((TF > 0 && !inv_depth_h) || (TO > 0 && (!obs_feat_h || !obs_j_h || !obs_pts_h))) {
+        c->err = "lmono_marginalize: inv_depth / obs_feat / obs_j / obs_pts must not be null when there are tracks / observations"; return LMONO_EINVAL;
+    }
     std::vector<int> fo((size_t)TF + 1, 0);
     for (int w = 0; w < n_windows; w++) {
         if (feat_off_h[w + 1] - feat_off_h[w] > kMargMaxF0) { c->err = "lmono_marginalize: more than 160 tracks anchored at frame 0"; return LMONO_ECAPACITY; }
         int o = obs_off_h[w];
         for (int f = feat_off_h[w]; f < feat_off_h[w + 1]; f++) {
             fo[f] = o;
+            unsigned seen = 0;      // frames of this track so far: the kernel keeps ONE W_d row per (track, frame) and assigns it
             while (o < obs_off_h[w + 1] && obs_feat_h[o] == f - feat_off_h[w]) {
                 if (obs_j_h[o] < 1 || obs_j_h[o] > 10) { c->err = "lmono_marginalize: observation frame must be 1..10"; return LMONO_EINVAL; }
+                if (seen & (1u << obs_j_h[o])) { c->err = "lmono_marginalize: a track is observed twice in the same frame"; return LMONO_EINVAL; }
+                seen |= 1u << obs_j_h[o];
                 o++;
             }
         }

@@ -165,6 +165,7 @@ __device__ __forceinline__ double mg_sum8(double v)
 __device__ __forceinline__ double mg_get2(double v0, double v1, int i) { const double a = mg_readlane_d(v0, i & 63), b = mg_readlane_d(v1, i & 63); return i < 64 ? a : b; }     // (both lanes read, a scalar select: no branch)
 __device__ __forceinline__ void mg_set2(double &v0, double &v1, int i, double x, int lane) { if (lane == i) v0 = x; if (64 + lane == i) v1 = x; }
 
+constexpr double kMgTinyE = 1e-150;      // sub-diagonal elements below this count as zero in the QL iteration (their squares leave the normal range)
 __device__ __noinline__ void marg_eig_ql(double *A, int n, MargEigWork &W, int tid)
 {
     const int lane = tid & 63, wave = tid >> 6;
@@ -291,9 +292,12 @@ __device__ __noinline__ void marg_eig_ql(double *A, int n, MargEigWork &W, int t
                 int m;
                 {
                     const int m0 = l + lane, m1 = l + 64 + lane;
+                    // (negligible against its neighbours, or below kMgTinyE: a sweep squares e[m - 1] in its first step, the square of a smaller one
+                    // underflows, x == 0 is then met before any rotation, nothing changes and the 60-sweep cap flags a failure -- seen with H' ~ 1e-170.
+                    // Dropping such an element moves eigenvalues by < 1e-150, far below anything the eps cut keeps.)
                     bool s0 = m0 >= n - 1, s1 = m1 >= n - 1;
-                    if (!s0) { const double dd = fabs(W.d[m0]) + fabs(W.d[m0 + 1]); s0 = fabs(W.e[m0]) <= 2.220446049250313e-16 * dd; }
-                    if (!s1) { const double dd = fabs(W.d[m1]) + fabs(W.d[m1 + 1]); s1 = fabs(W.e[m1]) <= 2.220446049250313e-16 * dd; }
+                    if (!s0) { const double dd = fabs(W.d[m0]) + fabs(W.d[m0 + 1]), ee = fabs(W.e[m0]); s0 = ee <= 2.220446049250313e-16 * dd || ee < kMgTinyE; }
+                    if (!s1) { const double dd = fabs(W.d[m1]) + fabs(W.d[m1 + 1]), ee = fabs(W.e[m1]); s1 = ee <= 2.220446049250313e-16 * dd || ee < kMgTinyE; }
                     const unsigned long long b0 = __ballot(s0), b1 = __ballot(s1);
                     m = b0 ? l + (int)__builtin_ctzll(b0) : l + 64 + (int)__builtin_ctzll(b1 | (1ull << 63));
                     if (m > n - 1) m = n - 1;

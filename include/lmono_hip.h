@@ -477,7 +477,7 @@ int lmono_tracker_reject_f(lmono_ctx *, lmono_tracker *, int n, const float *pre
  * BRIEF and the search follow the reference's source statement by statement.  The test pattern is an argument (the reference reads
  * brief_pattern.yml from BRIEF_PATTERN_FILE at run time).  Keypoints are in row-major order (y, then x).
  * PnPRANSAC and the rest of findConnection (:296-351, :551-688) are lmono_keyframes_verify below.
- * Not provided: db.query / db.add (DBoW2; the vocabulary is absent: the caller chooses the candidate old keyframes), the USE_ORB
+ * db.query / db.add and LoopDetector::detectLoop are lmono_keyframes_query / _detect_loop further below.  Not provided: the USE_ORB
  * branch, the thumbnail, distributionValidation (dead code), every DEBUG_IMAGE product.                                              */
 typedef struct { int8_t x1[256], y1[256], x2[256], y2[256]; } lmono_brief_pattern;   /* every offset in -63..63 */
 typedef struct lmono_keyframes lmono_keyframes;
@@ -555,6 +555,49 @@ int lmono_keyframes_verify(lmono_ctx *, lmono_keyframes *, int cur, int n_old, c
                            const double *ex_tq, const double *old_tq_h, const lmono_pnp_params *, int32_t *brief_counts_h, int32_t *pnp_inliers_h,
                            uint8_t *status_h, double *pnp_tq_old_h, double *loop_info_h, uint8_t *has_loop_h, double *channel_h, double *relative_euler_h,
                            double *pose_tq_h, int32_t *stats_h);
+
+/* ---- loop detection ----------------------------------------------------------------------------------------------
+ * LoopDetector::detectLoop (mono_lidar_mapping/src/loop_detection/LoopDetector.cc:167-260): the BRIEF vocabulary tree, the BoW vector of
+ * a keyframe, db.query and the score rules, for TF_IDF weighting and L1_NORM scoring (the pair the reference's vocabulary uses; any
+ * other is refused).  The stored keyframes are the database: entry e is keyframe e of the store, and a query of keyframe `cur` sees the
+ * entries before it, as the reference queries before it adds.  Every sum is sequential fp64 in the order DESIGN.md 6h writes out, and
+ * equal scores order by entry id.  Parity with a compiled DBoW2 is unpinned.  Not provided: the direct index, delete_entry, the other
+ * scoring and weighting types. */
+typedef struct lmono_brief_vocabulary lmono_brief_vocabulary;
+/* BriefVocabulary::loadBin (VocabularyBinary.hpp; TemplatedVocabulary.h:1500-1560) from the file's records: k, L, scoringType (0: L1_NORM),
+ * weightingType (0: TF_IDF); n_nodes records node_id / parent_id / weight / descriptors [n_nodes][8] (uint32: bit i is bit i & 31 of word
+ * i >> 5, the bytes of the file's 4 x uint64); n_words records word_node_id / word_id.  Node 0 is the root and has no record; the children
+ * of a node are the records that name it as parent, in file order.  NULL with the reason in lmono_last_error, before anything is uploaded,
+ * for: k outside 2..64, L outside 1..10, other types, n_nodes outside 1..16777215, node ids that are not exactly 1..n_nodes, a parent
+ * outside 0..n_nodes or equal to its node, a negative or non-finite weight, more than k children, a node unreachable from the root or
+ * deeper than L, words that are not a bijection between 0..n_words-1 and the leaves. */
+lmono_brief_vocabulary *lmono_brief_vocabulary_create(lmono_ctx *, int k, int L, int scoring, int weighting, int n_nodes, const int32_t *node_id, const int32_t *parent_id,
+                                                      const double *weight, const uint32_t *descriptors, int n_words, const int32_t *word_node_id, const int32_t *word_id);
+/* the handle goes; a store the vocabulary is attached to keeps the device tree alive */
+void lmono_brief_vocabulary_destroy(lmono_brief_vocabulary *);
+/* TemplatedVocabulary::transform(feature, word_id, weight) (:1217-1258) of n descriptors [n][8]: from the root to the child at the
+ * smallest Hamming distance (the first of equal children) until a leaf -> word_h [n], weight_h [n] (either may be NULL) */
+int lmono_brief_vocabulary_transform(lmono_ctx *, lmono_brief_vocabulary *, int n, const uint32_t *desc_h, int32_t *word_h, double *weight_h);
+/* db.setVocabulary (LoopDetector.cc:29): attach a vocabulary to a store (NULL detaches and frees the store's BoW arrays).  One vocabulary
+ * serves any number of stores.  LMONO_ECAPACITY for a store created with max_keypoints > 16384.  BoW vectors are built lazily, by the
+ * three calls below, for every stored keyframe that has none yet; lmono_keyframes_clear and this call forget them. */
+int lmono_keyframes_set_vocabulary(lmono_ctx *, lmono_keyframes *, lmono_brief_vocabulary *);
+/* the BoW vector of stored keyframe `index` (TemplatedVocabulary.h:1065-1121, BowVector.cpp:34-84): words of weight > 0 in ascending id,
+ * value = the weight added once per occurrence, divided by the L1 norm -> *n_out entries in word_h / value_h (room for the keyframe's
+ * corner count; either may be NULL) */
+int lmono_keyframes_bow(lmono_ctx *, lmono_keyframes *, int index, int *n_out, int32_t *word_h, double *value_h);
+/* db.query(brief_descriptors of cur, ret, max_results, max_id) (TemplatedDatabase.h:656-723): entry e < cur is admitted iff e < max_id ||
+ * max_id == -1 || e == cur - 1; admitted entries that share a word with cur, ordered by Score descending (ties: the lower id), cut to
+ * max_results (1..16) -> *n_out, id_h, score_h (room for max_results).  A pure function of the store's contents below cur. */
+int lmono_keyframes_query(lmono_ctx *, lmono_keyframes *, int cur, int max_results, int max_id, int *n_out, int32_t *id_h, double *score_h);
+/* LoopDetector::detectLoop (:181-259, without DEBUG_IMAGE): ret = query(cur, 4, cur - loop_search_gap) -> *n_out, id_h [4], score_h [4];
+ * *loop_index_out: -1 when cur - loop_search_gap < 0, else the rule of :200-259 with its constants 0.05 and 0.015 (-1: no loop).
+ * LMONO_EINVAL before any launch: no vocabulary attached, cur not a stored keyframe. */
+int lmono_keyframes_detect_loop(lmono_ctx *, lmono_keyframes *, int cur, int loop_search_gap, int *loop_index_out, int *n_out, int32_t *id_h, double *score_h);
+/* ... of keyframe cur [s] of n distinct stores that share one vocabulary: every phase is one launch over all streams, one read-back;
+ * loop_index_out [n], n_out [n], id_h [n][4], score_h [n][4].  A stream's bytes do not depend on the batch it travels in. */
+int lmono_keyframes_detect_loop_batch(lmono_ctx *, int n, lmono_keyframes *const *stores, const int *cur, int loop_search_gap, int *loop_index_out, int *n_out,
+                                      int32_t *id_h, double *score_h);
 
 /* ---- loop-closure pose graph -- NEW FEATURE, no counterpart in the reference --------------------------
  * The reference detects loops and publishes loop_info = relative_t, relative_q (w x y z), relative_yaw

@@ -20,6 +20,8 @@ SYMBOLS = [
     "lmono_tracker_response", "lmono_tracker_lk", "lmono_tracker_set_reject_f", "lmono_tracker_reject_stats", "lmono_tracker_reject_f",
     "lmono_keyframes_create", "lmono_keyframes_destroy", "lmono_keyframes_clear", "lmono_keyframes_size", "lmono_keyframes_add", "lmono_keyframes_add_batch",
     "lmono_keyframes_load", "lmono_keyframes_match", "lmono_keyframes_images", "lmono_keyframes_get", "lmono_keyframes_verify", "lmono_pnp_ransac",
+    "lmono_brief_vocabulary_create", "lmono_brief_vocabulary_destroy", "lmono_brief_vocabulary_transform", "lmono_keyframes_set_vocabulary", "lmono_keyframes_bow",
+    "lmono_keyframes_query", "lmono_keyframes_detect_loop", "lmono_keyframes_detect_loop_batch",
     "lmono_pose_graph_create", "lmono_pose_graph_destroy", "lmono_pose_graph_reset", "lmono_pose_graph_info", "lmono_pose_graph_order", "lmono_pose_graph_reduce_buffer", "lmono_pose_graph_set_reduce_buffer", "lmono_pose_graph_linearise",
     "lmono_pose_graph_step", "lmono_pose_graph_optimize", "lmono_pose_graph_result", "lmono_factor_eval", "lmono_factor_eval_d", "lmono_factor_eval_blocks", "lmono_factor_eval_blocks_d",
     "lmono_triangulate", "lmono_outlier_scores", "lmono_shift_depth", "lmono_shift_depth_batch", "lmono_marginalize", "lmono_marg_evaluate", "lmono_marg_second_new", "lmono_ba_batch_create", "lmono_ba_batch_update", "lmono_ba_batch_destroy", "lmono_ba_solve", "lmono_ba_batch_reset", "lmono_ba_batch_read", "lmono_debug_bounds",
@@ -1024,6 +1026,247 @@ def _keyframes_prototypes(L):
     L.lmono_keyframes_images.argtypes = [C.c_void_p] * 4
     L.lmono_keyframes_get.argtypes = [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 7
     L.lmono_keyframes_verify.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 16
+    L.lmono_brief_vocabulary_create.restype = C.c_void_p
+    L.lmono_brief_vocabulary_create.argtypes = [C.c_void_p] + [C.c_int] * 5 + [C.c_void_p] * 4 + [C.c_int, C.c_void_p, C.c_void_p]
+    L.lmono_brief_vocabulary_destroy.restype = None
+    L.lmono_brief_vocabulary_destroy.argtypes = [C.c_void_p]
+    L.lmono_brief_vocabulary_transform.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.lmono_keyframes_set_vocabulary.argtypes = [C.c_void_p] * 3
+    L.lmono_keyframes_bow.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.lmono_keyframes_query.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.lmono_keyframes_detect_loop.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 4
+    L.lmono_keyframes_detect_loop_batch.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 4
+
+
+# ---- BRIEF vocabulary: the file layout of the reference's VocabularyBinary.hpp, the checks, a trainer
+_VOC_NODE = np.dtype([("node_id", "<i4"), ("parent_id", "<i4"), ("weight", "<f8"), ("descriptor", "<u4", (8,))])      # 48 B: 4 x uint64 little-endian = 8 x uint32
+_VOC_WORD = np.dtype([("node_id", "<i4"), ("word_id", "<i4")])
+_VOC_KEYS = ("k", "L", "scoring", "weighting", "node_id", "parent_id", "weight", "descriptors", "word_node_id", "word_id")
+_POP8 = np.array([bin(i).count("1") for i in range(256)], np.int32)
+
+
+def _voc_arrays(voc):
+    """The arrays of a vocabulary dict in the types the C ABI reads."""
+    return (np.ascontiguousarray(voc["node_id"], np.int32).reshape(-1), np.ascontiguousarray(voc["parent_id"], np.int32).reshape(-1),
+            np.ascontiguousarray(voc["weight"], np.float64).reshape(-1), np.ascontiguousarray(voc["descriptors"], np.uint32).reshape(-1, 8),
+            np.ascontiguousarray(voc["word_node_id"], np.int32).reshape(-1), np.ascontiguousarray(voc["word_id"], np.int32).reshape(-1))
+
+
+def check_brief_vocabulary(voc):
+    """The checks lmono_brief_vocabulary_create makes on the host, in its order and words -> None for a well-formed vocabulary, else the
+    reason.  voc: dict with k, L, scoring, weighting (ints), node_id, parent_id, weight [nNodes], descriptors [nNodes, 8] uint32,
+    word_node_id, word_id [nWords]; node 0 is the root and has no record."""
+    k, L = int(voc["k"]), int(voc["L"])
+    nid, par, wt, de, wn, wi = _voc_arrays(voc)
+    n, nw = len(nid), len(wn)
+    if k < 2 or k > 64:
+        return "brief vocabulary: k outside 2..64"
+    if L < 1 or L > 10:
+        return "brief vocabulary: L outside 1..10"
+    if int(voc["scoring"]) != 0 or int(voc["weighting"]) != 0:
+        return "brief vocabulary: only L1_NORM scoring (0) with TF_IDF weighting (0) is built"
+    if n < 1 or n > 16777215:
+        return "brief vocabulary: nNodes outside 1..16777215"
+    if nw < 1 or nw > n:
+        return "brief vocabulary: nWords outside 1..nNodes"
+    if not (len(par) == len(wt) == len(de) == n) or len(wi) != nw:
+        return "brief vocabulary: a null array"
+    if not np.array_equal(np.sort(nid), np.arange(1, n + 1)):
+        return "brief vocabulary: nodeIds are not exactly 1..nNodes, each once"
+    if ((par < 0) | (par > n) | (par == nid)).any():
+        return "brief vocabulary: a parentId outside 0..nNodes or equal to its own nodeId"
+    if not (np.isfinite(wt) & (wt >= 0)).all():
+        return "brief vocabulary: a weight that is negative or not finite"
+    n_children = np.bincount(par, minlength=n + 1)
+    if n_children.max() > k:
+        return "brief vocabulary: an inner node with more than k children"
+    depth = np.full(n + 1, -1, np.int64)
+    depth[0] = 0
+    level = np.array([0])
+    for lv in range(1, L + 1):
+        level = nid[np.isin(par, level)]
+        depth[level] = lv
+    if (depth < 0).any():
+        return "brief vocabulary: a node unreachable from the root, or deeper than L"
+    bad = "brief vocabulary: the words are not a bijection between 0..nWords-1 and the leaves"
+    if int((n_children == 0).sum()) != nw or not np.array_equal(np.sort(wi), np.arange(nw)):
+        return bad
+    if ((wn < 1) | (wn > n)).any() or len(np.unique(wn)) != nw or (n_children[wn] != 0).any():
+        return bad
+    return None
+
+
+def load_brief_vocabulary(path):
+    """A vocabulary file in the layout of VocabularyBinary.hpp (6 int32 k, L, scoringType, weightingType, nNodes, nWords; nNodes records of
+    48 B; nWords records of 8 B) -> dict of plain arrays (see check_brief_vocabulary).  The bytes are not judged here."""
+    with open(path, "rb") as f:
+        raw = f.read()
+    if len(raw) < 24:
+        raise LmonoError("%s: shorter than the header of a vocabulary file" % path)
+    k, L, scoring, weighting, n, nw = (int(v) for v in np.frombuffer(raw, "<i4", 6))
+    if n < 0 or nw < 0 or len(raw) != 24 + 48 * n + 8 * nw:
+        raise LmonoError("%s: %d bytes, but the header (nNodes %d, nWords %d) asks for %d" % (path, len(raw), n, nw, 24 + 48 * n + 8 * nw))
+    nodes = np.frombuffer(raw, _VOC_NODE, n, 24)
+    words = np.frombuffer(raw, _VOC_WORD, nw, 24 + 48 * n)
+    return {"k": k, "L": L, "scoring": scoring, "weighting": weighting, "node_id": nodes["node_id"].astype(np.int32), "parent_id": nodes["parent_id"].astype(np.int32),
+            "weight": nodes["weight"].astype(np.float64), "descriptors": nodes["descriptor"].astype(np.uint32), "word_node_id": words["node_id"].astype(np.int32),
+            "word_id": words["word_id"].astype(np.int32)}
+
+
+def save_brief_vocabulary(path, voc):
+    """The inverse of load_brief_vocabulary: 24 + 48 nNodes + 8 nWords bytes."""
+    nid, par, wt, de, wn, wi = _voc_arrays(voc)
+    nodes = np.zeros(len(nid), _VOC_NODE)
+    nodes["node_id"] = nid; nodes["parent_id"] = par; nodes["weight"] = wt; nodes["descriptor"] = de
+    words = np.zeros(len(wn), _VOC_WORD)
+    words["node_id"] = wn; words["word_id"] = wi
+    with open(path, "wb") as f:
+        f.write(np.array([voc["k"], voc["L"], voc["scoring"], voc["weighting"], len(nid), len(wn)], "<i4").tobytes())
+        f.write(nodes.tobytes())
+        f.write(words.tobytes())
+
+
+def _mix32(x):
+    """The hash of DESIGN.md 6e (item 4a.2) on uint32."""
+    x &= 0xFFFFFFFF
+    x ^= x >> 16; x = (x * 0x7feb352d) & 0xFFFFFFFF
+    x ^= x >> 15; x = (x * 0x846ca68b) & 0xFFFFFFFF
+    x ^= x >> 16
+    return x
+
+
+def _hamming_to(desc, centre):
+    """[n, 8] uint32 x [8] uint32 -> int32 [n]."""
+    return _POP8[(desc ^ centre[None, :]).view(np.uint8)].sum(1).astype(np.int32)
+
+
+def _voc_words_of(voc, desc):
+    """The word of every descriptor by the descent of 6h (the nearest child, ties to the first in file order) -> int32 [n]."""
+    nid, par, wt, de, wn, wi = _voc_arrays(voc)
+    kids = {}
+    for r in range(len(nid)):
+        kids.setdefault(int(par[r]), []).append(r)
+    word_of = {int(a): int(b) for a, b in zip(wn, wi)}
+    out = np.zeros(len(desc), np.int32)
+    for i, d in enumerate(desc):
+        node = 0
+        while node in kids:
+            rows = kids[node]
+            node = int(nid[rows[int(np.argmin(_hamming_to(de[rows], d)))]])         # argmin: the first of equal distances
+        out[i] = word_of[node]
+    return out
+
+
+def train_brief_vocabulary(descriptor_sets, k, L, seed=0):
+    """A vocabulary from this project's own descriptors: hierarchical k-majority clustering of DESIGN.md 6h (a definition of this project,
+    deterministic in seed; offline tooling, plain numpy).  descriptor_sets: a list of [n_i, 8] uint32 arrays (one per image) -> dict."""
+    sets = [np.ascontiguousarray(s, np.uint32).reshape(-1, 8) for s in descriptor_sets]
+    if not (2 <= int(k) <= 64) or not (1 <= int(L) <= 10):
+        raise LmonoError("train_brief_vocabulary: k in 2..64 and L in 1..10")
+    desc = np.concatenate(sets) if sets else np.zeros((0, 8), np.uint32)
+    if len(desc) == 0:
+        raise LmonoError("train_brief_vocabulary: no descriptors")
+    nodes = []                       # (parent id, descriptor); node id = position + 1
+
+    def new_node(parent, d):
+        nodes.append((parent, np.array(d, np.uint32)))
+        return len(nodes)
+
+    def distinct(idx):
+        seen, out = set(), []
+        for i in idx:
+            key = desc[i].tobytes()
+            if key not in seen:
+                seen.add(key); out.append(i)
+        return out
+
+    def split(node, idx, level):
+        """The children of `node` (at `level`) over the descriptors idx."""
+        if len(idx) <= k:
+            for i in distinct(idx):
+                new_node(node, desc[i])
+            return
+        d = desc[idx]
+        first = _mix32(int(seed) ^ node) % len(idx)
+        centres = [d[first].copy()]
+        nearest = _hamming_to(d, centres[0])
+        while len(centres) < k:
+            far = int(np.argmax(nearest))                  # the farthest from its nearest centre, ties to the lowest index
+            if nearest[far] == 0:
+                break
+            centres.append(d[far].copy())
+            nearest = np.minimum(nearest, _hamming_to(d, centres[-1]))
+        centres = np.stack(centres)
+        bits = np.unpackbits(d.view(np.uint8), axis=1, bitorder="little")
+        assign = None
+        for _ in range(10):
+            dist = np.stack([_hamming_to(d, c) for c in centres], 1)
+            now = np.argmin(dist, 1)                       # ties to the lowest centre
+            if assign is not None and np.array_equal(now, assign):
+                break
+            assign = now
+            for c in range(len(centres)):
+                members = bits[assign == c]
+                if len(members):                           # an empty cluster keeps its centre
+                    vote = (2 * members.sum(0) > len(members)).astype(np.uint8)      # a tie gives bit 0
+                    centres[c] = np.packbits(vote, bitorder="little").view(np.uint32)
+        groups = [(c, [idx[i] for i in np.nonzero(assign == c)[0]]) for c in range(len(centres))]
+        groups = [(new_node(node, centres[c]), g) for c, g in groups if g]
+        if level + 1 < L:
+            for child, g in groups:
+                if len(g) > 1:
+                    split(child, g, level + 1)
+
+    split(0, list(range(len(desc))), 0)
+    parent = np.array([p for p, _ in nodes], np.int32)
+    node_id = np.arange(1, len(nodes) + 1, dtype=np.int32)
+    leaves = node_id[~np.isin(node_id, parent)]
+    voc = {"k": int(k), "L": int(L), "scoring": 0, "weighting": 0, "node_id": node_id, "parent_id": parent, "weight": np.zeros(len(nodes)),
+           "descriptors": np.stack([d for _, d in nodes]), "word_node_id": leaves.astype(np.int32), "word_id": np.arange(len(leaves), dtype=np.int32)}
+    # setNodeWeights (TemplatedVocabulary.h:942-): idf over the descriptor sets, by the words the finished tree gives them
+    n_i = np.zeros(len(leaves), np.int64)
+    for s in sets:
+        n_i[np.unique(_voc_words_of(voc, s))] += 1
+    weight = np.zeros(len(nodes))
+    for w, leaf in enumerate(leaves):
+        weight[leaf - 1] = float(np.log(len(sets) / n_i[w])) if n_i[w] > 0 else 0.0
+    voc["weight"] = weight
+    return voc
+
+
+class BriefVocabulary:
+    """A BRIEF vocabulary tree on the device (lmono_brief_vocabulary_*).  voc: the dict of load_brief_vocabulary /
+    train_brief_vocabulary; a malformed one is refused by the library with its reason."""
+
+    def __init__(self, ctx, voc):
+        self.ctx = ctx
+        ctx._children.add(self)
+        _keyframes_prototypes(ctx.L)
+        nid, par, wt, de, wn, wi = _voc_arrays(voc)
+        if not (len(par) == len(wt) == len(de) == len(nid)) or len(wi) != len(wn):
+            raise LmonoError("BriefVocabulary: the node arrays (and the word arrays) differ in length")
+        self.h = ctx.L.lmono_brief_vocabulary_create(ctx.h, int(voc["k"]), int(voc["L"]), int(voc["scoring"]), int(voc["weighting"]), len(nid), nid.ctypes.data,
+                                                     par.ctypes.data, wt.ctypes.data, de.ctypes.data, len(wn), wn.ctypes.data, wi.ctypes.data)
+        if not self.h:
+            raise LmonoError("lmono_brief_vocabulary_create failed: " + ctx.last_error())
+
+    def transform(self, descriptors):
+        """-> (word int32 [n], weight float64 [n]) of descriptors [n, 8] uint32."""
+        de = np.ascontiguousarray(descriptors, np.uint32).reshape(-1, 8)
+        word = np.full(len(de), -1, np.int32); weight = np.zeros(len(de))
+        self.ctx.check(self.ctx.L.lmono_brief_vocabulary_transform(self.ctx.h, self.h, len(de), de.ctypes.data, word.ctypes.data, weight.ctypes.data))
+        return word, weight
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.ctx.L.lmono_brief_vocabulary_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class PnPParams(C.Structure):
@@ -1182,6 +1425,44 @@ class KeyFrames:
         loops = np.stack([old[has], np.full(int(has.sum()), int(cur), np.int32)], 1).astype(np.int32)
         return {"counts": cnt, "inliers": inl, "status": st, "pnp_tq_old": tq, "loop_info": li, "has_loop": has, "channel": ch, "relative_euler": eu,
                 "pose": pose, "stats": stats, "loops": loops, "loops_info": li[has]}
+
+    def set_vocabulary(self, vocabulary):
+        """Attach a BriefVocabulary (None detaches): the store keeps the device tree alive on its own."""
+        self.ctx.check(self.ctx.L.lmono_keyframes_set_vocabulary(self.ctx.h, self.h, vocabulary.h if vocabulary is not None else None))
+
+    def bow(self, index):
+        """The BoW vector of a stored keyframe -> (word int32 [m] ascending, value float64 [m])."""
+        nk = C.c_int(0)
+        self.ctx.check(self.ctx.L.lmono_keyframes_get(self.ctx.h, self.h, int(index), C.addressof(nk), None, None, None, None, None, None))
+        word = np.zeros(nk.value + 1, np.int32); val = np.zeros(nk.value + 1); n = C.c_int(0)
+        self.ctx.check(self.ctx.L.lmono_keyframes_bow(self.ctx.h, self.h, int(index), C.addressof(n), word.ctypes.data, val.ctypes.data))
+        return word[:n.value].copy(), val[:n.value].copy()
+
+    def query(self, cur, max_results=4, max_id=-1):
+        """db.query of keyframe cur against the keyframes before it (queryL1) -> (id int32 [n], Score float64 [n]), best first."""
+        ids = np.zeros(16, np.int32); sc = np.zeros(16); n = C.c_int(0)
+        self.ctx.check(self.ctx.L.lmono_keyframes_query(self.ctx.h, self.h, int(cur), int(max_results), int(max_id), C.addressof(n), ids.ctypes.data, sc.ctypes.data))
+        return ids[:n.value].copy(), sc[:n.value].copy()
+
+    def detect_loop(self, cur, loop_search_gap=100):
+        """LoopDetector::detectLoop of keyframe cur -> (loop index or -1, id int32 [n <= 4], Score float64 [n])."""
+        ids = np.zeros(4, np.int32); sc = np.zeros(4); n = C.c_int(0); loop = C.c_int(-1)
+        self.ctx.check(self.ctx.L.lmono_keyframes_detect_loop(self.ctx.h, self.h, int(cur), int(loop_search_gap), C.addressof(loop), C.addressof(n), ids.ctypes.data, sc.ctypes.data))
+        return loop.value, ids[:n.value].copy(), sc[:n.value].copy()
+
+    @classmethod
+    def detect_loop_batch(cls, stores, curs, loop_search_gap=100):
+        """detect_loop of one keyframe in each of several distinct stores that share a vocabulary, every phase one launch ->
+        list of (loop index, ids, Scores)."""
+        n = len(stores)
+        ctx = stores[0].ctx
+        cur = np.ascontiguousarray(curs, np.int32).reshape(-1)
+        if len(cur) != n:
+            raise LmonoError("detect_loop_batch needs one keyframe index per store")
+        hs = (C.c_void_p * n)(*[s.h for s in stores])
+        loop = np.full(n, -1, np.int32); cnt = np.zeros(n, np.int32); ids = np.zeros((n, 4), np.int32); sc = np.zeros((n, 4))
+        ctx.check(ctx.L.lmono_keyframes_detect_loop_batch(ctx.h, n, hs, cur.ctypes.data, int(loop_search_gap), loop.ctypes.data, cnt.ctypes.data, ids.ctypes.data, sc.ctypes.data))
+        return [(int(loop[s]), ids[s, :cnt[s]].copy(), sc[s, :cnt[s]].copy()) for s in range(n)]
 
     def clear(self):
         self.ctx.check(self.ctx.L.lmono_keyframes_clear(self.ctx.h, self.h))

@@ -2,6 +2,14 @@
 #pragma once
 #include "keyframe.hip"
 #include "pnp.hip"
+#include "bow.hip"
+
+// a vocabulary tree on the device (bow_abi.hip): shared by its handle and by every store it is attached to, freed with the last of them
+struct BowVocDev {
+    lmono_ctx *ctx = nullptr;
+    BowVoc v{};
+    DevOwner mem;
+};
 
 struct lmono_keyframes {
     lmono_ctx *ctx = nullptr;
@@ -38,6 +46,20 @@ struct lmono_keyframes {
     unsigned char *v_status = nullptr;
     double *v_pose = nullptr;
     int *v_stats = nullptr;
+    // the loop detector's database (bow_abi.hip): the attached vocabulary, and the BoW vectors of keyframes [0, bow_done)
+    std::shared_ptr<BowVocDev> voc;
+    int bow_done = 0;
+    int *bow_word = nullptr, *bow_n = nullptr;           // [max_kf][max_kp], [max_kf]
+    double *bow_val = nullptr;                           // [max_kf][max_kp]
+    double *q_s = nullptr;                               // [max_kf] score sums and flags of a query of this store
+    int *q_flag = nullptr;
+    // job tables and results of a build / query batch led by this store
+    BowWordsJob *b_wjobs = nullptr;
+    BowVecJob *b_vjobs = nullptr;
+    int b_cap = 0;
+    BowQueryJob *q_jobs = nullptr;
+    BowResult *q_out = nullptr;
+    int q_cap = 0;
 };
 
 extern "C" void lmono_keyframes_destroy(lmono_keyframes *k) { delete k; }
@@ -46,6 +68,7 @@ extern "C" int lmono_keyframes_clear(lmono_ctx *c, lmono_keyframes *k)
 {
     if (!c || !k || k->ctx != c) return LMONO_EINVAL;
     k->n_kf = 0; k->n_kp_h.clear(); k->n_win_h.clear();
+    k->bow_done = 0;
     return LMONO_OK;
 }
 

@@ -350,4 +350,5 @@ template <typename H> static int batch_handle_fault(const lmono_ctx *c, int s, H
 #include "track_abi.hip"
 #include "keyframe_abi.hip"
 #include "pnp_abi.hip"
+#include "bow_abi.hip"
 #include "posegraph_abi.hip"

@@ -1,7 +1,9 @@
 // lmono_amd/host/keyframe.cpp -- see keyframe.hpp
 #include "keyframe.hpp"
 #include "../csrc/pnp.hip"      // plain C++ here: pnp_guess, pnp_after
+#include <cmath>
 #include <cstdlib>
+#include <cstring>
 #include <fstream>
 #include <map>
 
@@ -165,6 +167,88 @@ bool KeyFrame::findConnection(const KeyFrame *old_kf)
     for (int e = 0; e < 14; e++) published.t_q_index[e] = channel[e];
     published.t_q_index[14] = (double)index;                                     // :681: the keyframe's own index, not its slot in the store
     return true;
+}
+
+LoopDetector::LoopDetector(KeyFrameStore &store, int loop_search_gap, double loop_search_time)
+    : LOOP_SEARCH_GAP(loop_search_gap), LOOP_SEARCH_TIME(loop_search_time), store_(store) {}
+
+LoopDetector::~LoopDetector()
+{
+    if (voc_) lmono_brief_vocabulary_destroy(voc_);         // the store keeps the device tree for as long as it is attached
+}
+
+void LoopDetector::loadVocabulary(const std::string &voc_path)
+{
+    std::ifstream in(voc_path, std::ios::binary);
+    if (!in) throw std::runtime_error("loadVocabulary: cannot open " + voc_path);
+    int32_t head[6];
+    in.read((char *)head, sizeof(head));
+    if (!in || head[4] < 0 || head[4] > 16777215 || head[5] < 0 || head[5] > 16777215) throw std::runtime_error("loadVocabulary: " + voc_path + " has no vocabulary header");
+    const size_t n = (size_t)head[4], nw = (size_t)head[5];
+    std::vector<char> nodes(n * 48), words(nw * 8);
+    in.read(nodes.data(), (std::streamsize)nodes.size());
+    in.read(words.data(), (std::streamsize)words.size());
+    if ((size_t)in.gcount() != words.size() || !in) throw std::runtime_error("loadVocabulary: " + voc_path + " is shorter than its header says");
+    std::vector<int32_t> node_id(n), parent_id(n), word_node(nw), word_id(nw);
+    std::vector<double> weight(n);
+    std::vector<uint32_t> desc(n * 8);
+    for (size_t r = 0; r < n; r++) {
+        const char *p = nodes.data() + r * 48;
+        std::memcpy(&node_id[r], p, 4); std::memcpy(&parent_id[r], p + 4, 4); std::memcpy(&weight[r], p + 8, 8); std::memcpy(&desc[r * 8], p + 16, 32);
+    }
+    for (size_t r = 0; r < nw; r++) { std::memcpy(&word_node[r], words.data() + r * 8, 4); std::memcpy(&word_id[r], words.data() + r * 8 + 4, 4); }
+    lmono_ctx *c = store_.hip().get();
+    lmono_brief_vocabulary *voc = lmono_brief_vocabulary_create(c, head[0], head[1], head[2], head[3], head[4], node_id.data(), parent_id.data(), weight.data(), desc.data(),
+                                                                head[5], word_node.data(), word_id.data());
+    if (!voc) throw std::runtime_error(std::string("lmono_brief_vocabulary_create: ") + lmono_last_error(c));
+    const int rc = lmono_keyframes_set_vocabulary(c, store_.get(), voc);                     // db.setVocabulary(*voc, false, 0)
+    if (rc != LMONO_OK) { lmono_brief_vocabulary_destroy(voc); store_.hip().check(rc, "lmono_keyframes_set_vocabulary"); }
+    if (voc_) lmono_brief_vocabulary_destroy(voc_);
+    voc_ = voc;
+}
+
+int LoopDetector::detectLoop(KeyFrame *keyframe, int frame_index)
+{
+    (void)frame_index;                                   // the database entry of a keyframe is its slot in the store
+    int loop_slot = -1, n = 0;
+    int32_t id[4];
+    double score[4];
+    store_.hip().check(lmono_keyframes_detect_loop(store_.hip().get(), store_.get(), keyframe->store_index, LOOP_SEARCH_GAP, &loop_slot, &n, id, score), "lmono_keyframes_detect_loop");
+    ret_id.assign(id, id + n); ret_score.assign(score, score + n);
+    if (loop_slot == -1) return -1;
+    for (KeyFrame *kf : keyframelist) if (kf->store_index == loop_slot) return kf->index;
+    return -1;
+}
+
+int LoopDetector::addKeyFrame(KeyFrame *cur_kf, bool flag_detect_loop)
+{
+    int loop_index = -1;
+    if (flag_detect_loop) loop_index = detectLoop(cur_kf, cur_kf->index);
+    // else addKeyFrameIntoVoc: the keyframe is in the store already, its BoW vector is built when a query first needs it
+    if (loop_index != -1) {
+        KeyFrame *old_kf = getKeyFrame(loop_index);
+        if (old_kf && std::fabs(cur_kf->time_stamp - old_kf->time_stamp) > LOOP_SEARCH_TIME) {          // :73
+            if (cur_kf->findConnection(old_kf)) {
+                loop_index = old_kf->index;
+                double old_tq[7], cur_tq[7], R_old[9];
+                old_kf->getVioPose(old_tq);
+                const double *rel_t = cur_kf->loop_info;                                                 // getLoopRelativeT / Q (w x y z)
+                const double rel_q[4] = { cur_kf->loop_info[4], cur_kf->loop_info[5], cur_kf->loop_info[6], cur_kf->loop_info[3] };
+                lmono::pnp_rot(old_tq + 3, R_old);
+                lmono::pnp_apply(R_old, old_tq, rel_t, cur_tq);                                          // w_P_cur = w_R_old * relative_t + w_P_old
+                lmono::pnp_qmul(old_tq + 3, rel_q, cur_tq + 3);                                          // w_R_cur = w_R_old * relative_q
+                cur_kf->updateVioPose(cur_tq);
+            } else loop_index = -1;
+        }
+    }
+    keyframelist.push_back(cur_kf);
+    return loop_index;
+}
+
+KeyFrame *LoopDetector::getKeyFrame(int index)
+{
+    for (KeyFrame *kf : keyframelist) if (kf->index == index) return kf;
+    return nullptr;
 }
 
 } // namespace lmono_host

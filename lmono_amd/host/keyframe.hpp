@@ -2,9 +2,11 @@
 // keyframe store of the C ABI (lmono_keyframes_*).  A KeyFrame keeps the reference's members on the host (they are read
 // back once, when it is built) and its slot in the store; searchByBRIEFDes and findConnection run the search on the device.
 // PnPRANSAC and findConnection to its end (KeyFrame.cc:296-351, :551-688) run on the device too (lmono_pnp_ransac, lmono_keyframes_verify).
-// Not mirrored: the DBoW2 database, the USE_ORB branch, the thumbnail, DEBUG_IMAGE; the ROS message of :644-684 is the plain struct LoopMessage.
+// LoopDetector (below) mirrors LoopDetector.cc:26-260 over the store's BoW database (lmono_keyframes_detect_loop).
+// Not mirrored: the USE_ORB branch, the thumbnail, DEBUG_IMAGE; the ROS message of :644-684 is the plain struct LoopMessage.
 #pragma once
 #include <array>
+#include <list>
 #include <string>
 #include <vector>
 #include "lmono_host.hpp"
@@ -80,6 +82,10 @@ public:
     int sequence;
     bool has_loop;
     int loop_index;
+    // KeyFrame.cc:753-777; the mirror keeps one pose for vio_T_w_i / vio_R_w_i and T_w_i / R_w_i (updateVioPose sets the two alike)
+    void getVioPose(double *tq) const { for (int e = 0; e < 7; e++) tq[e] = T_w_i_tq[e]; }
+    void updateVioPose(const double *tq) { for (int e = 0; e < 7; e++) T_w_i_tq[e] = tq[e]; }
+
     // poses as t (x y z), q (x y z w): origin_vio_T / origin_vio_R, T_w_i / R_w_i, and the camera in the body (tlc, qlc); identity until set
     double origin_vio_tq[7] = { 0, 0, 0, 0, 0, 0, 1 }, T_w_i_tq[7] = { 0, 0, 0, 0, 0, 0, 1 }, ex_tq[7] = { 0, 0, 0, 0, 0, 0, 1 };
     lmono_pnp_params pnp_params = { 0.0, 0, 0u, 0, 0, 0.0, 0.0 };      // zeros: the defaults of kitti_loop_config_04.yaml
@@ -92,6 +98,35 @@ public:
 private:
     KeyFrameStore &store_;
     void readBack();
+};
+
+// LoopDetector (include/loop_detection/Loop_Detector.h, src/loop_detection/LoopDetector.cc:26-150, :167-260) over one KeyFrameStore: the
+// stored keyframes are the database (entry e is the keyframe in slot e, so db.add is the KeyFrame constructor's add), and db.query with
+// the score rules is lmono_keyframes_detect_loop.  With keyframes built in order their index is their slot, as the reference assumes;
+// detectLoop answers in keyframe indices either way.  Not mirrored: the drift members, the optimisation thread, the commented blocks,
+// the files loop_odometry.txt / loop_recorder.txt, DEBUG_IMAGE.
+class LoopDetector {
+public:
+    LoopDetector(KeyFrameStore &store, int loop_search_gap, double loop_search_time);      // LOOP_SEARCH_GAP, LOOP_SEARCH_TIME of the config
+    ~LoopDetector();
+    LoopDetector(const LoopDetector &) = delete;
+    LoopDetector &operator=(const LoopDetector &) = delete;
+    // :26-30: a file in the layout of VocabularyBinary.hpp; std::runtime_error with the library's reason for a malformed one
+    void loadVocabulary(const std::string &voc_path);
+    // :32-150: detectLoop, the LOOP_SEARCH_TIME gate, findConnection and the updateVioPose of :80-95 -> the loop's keyframe index or -1
+    int addKeyFrame(KeyFrame *cur_kf, bool flag_detect_loop);
+    // :167-260 -> the keyframe index of the loop candidate or -1; ret of db.query is left in ret_id (slots) / ret_score
+    int detectLoop(KeyFrame *keyframe, int frame_index);
+    KeyFrame *getKeyFrame(int index);                    // :152-165
+
+    int LOOP_SEARCH_GAP;
+    double LOOP_SEARCH_TIME;
+    std::list<KeyFrame *> keyframelist;
+    std::vector<int> ret_id;
+    std::vector<double> ret_score;
+private:
+    KeyFrameStore &store_;
+    lmono_brief_vocabulary *voc_ = nullptr;
 };
 
 } // namespace lmono_host

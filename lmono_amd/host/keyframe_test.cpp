@@ -3,6 +3,9 @@
 //   keyframe_test <frames.raw> <brief_pattern.yml> [k [delta [verify]]]
 // With `verify` the same lines are followed by findConnection to its end (PnPRANSAC, the gates, loop_info, the published message): the
 // scene is taken as a fronto-parallel plane at 10 m in front of each camera, the current camera shifted by (0.3, 0.1, 0) m in the world.
+//   keyframe_test <frames.raw> <brief_pattern.yml> detect <vocabulary.bin> [loop_search_gap [loop_search_time]]
+// Every frame becomes a KeyFrame (window points: the tracker's points) and goes through LoopDetector::addKeyFrame(kf, true) with a
+// vocabulary file in the layout of VocabularyBinary.hpp; one line per keyframe: its loop index and the results of db.query.
 // frames.raw: a text line "<width> <height> <frames>" followed by frames * height * width grey bytes.
 #include <cstdio>
 #include <cstdlib>
@@ -14,9 +17,53 @@
 
 using namespace lmono_host;
 
+static int detect(int argc, char **argv)
+{
+    if (argc < 5) { std::fprintf(stderr, "usage: keyframe_test <frames.raw> <brief_pattern.yml> detect <vocabulary.bin> [loop_search_gap [loop_search_time]]\n"); return 2; }
+    const int gap = argc > 5 ? std::atoi(argv[5]) : 100;
+    const double search_time = argc > 6 ? std::atof(argv[6]) : 1e9;
+    try {
+        std::ifstream in(argv[1], std::ios::binary);
+        int W = 0, H = 0, N = 0;
+        in >> W >> H >> N;
+        in.get();
+        if (!in || W < 32 || H < 32 || W > 8192 || H > 8192 || N < 1 || N > 4096) { std::fprintf(stderr, "keyframe_test: bad frames file\n"); return 2; }
+        std::vector<uint8_t> frames((size_t)W * H * N);
+        in.read((char *)frames.data(), (std::streamsize)frames.size());
+        if ((size_t)in.gcount() != frames.size()) { std::fprintf(stderr, "keyframe_test: frames file is short\n"); return 2; }
+        const lmono_brief_pattern pattern = loadBriefPattern(argv[2]);
+        HipContext hip(0);
+        lmono_camera cam = { W, H, 300.0, 300.0, 0.5 * W, 0.5 * H, -0.1, 0.02, 0.0005, -0.0005, 5, 0, 0 };
+        FeatureTracker tracker(hip, cam, 150, 15);
+        KeyFrameStore store(hip, cam, pattern, N, 16384);
+        LoopDetector detector(store, gap, search_time);
+        detector.loadVocabulary(argv[4]);
+        std::vector<KeyFrame> kfs;
+        kfs.reserve((size_t)N);
+        for (int f = 0; f < N; f++) {
+            const uint8_t *img = frames.data() + (size_t)f * W * H;
+            tracker.trackImage(0.1 * f, img, LMONO_TRACK_GREY8);
+            std::vector<Point3f> p3; std::vector<Point2f> uv, nm; std::vector<int> id;
+            for (const lmono_track_record &r : tracker.records) {
+                p3.push_back({ r.x_n, r.y_n, 1.f }); uv.push_back({ r.u, r.v }); nm.push_back({ r.x_n, r.y_n }); id.push_back(r.id);
+            }
+            kfs.emplace_back(store, 0.1 * f, f, img, LMONO_TRACK_GREY8, p3, uv, nm, id, 0);
+            const int loop = detector.addKeyFrame(&kfs.back(), true);
+            std::printf("DETECT %d keypoints %zu loop %d results %zu", f, kfs.back().brief_keypoints.size(), loop, detector.ret_id.size());
+            for (size_t i = 0; i < detector.ret_id.size(); i++) std::printf(" %d:%.17g", detector.ret_id[i], detector.ret_score[i]);
+            std::printf("\n");
+        }
+    } catch (const std::exception &e) {
+        std::fprintf(stderr, "keyframe_test: %s\n", e.what());
+        return 1;
+    }
+    return 0;
+}
+
 int main(int argc, char **argv)
 {
-    if (argc < 3) { std::fprintf(stderr, "usage: keyframe_test <frames.raw> <brief_pattern.yml> [k [delta [verify]]]\n"); return 2; }
+    if (argc < 3) { std::fprintf(stderr, "usage: keyframe_test <frames.raw> <brief_pattern.yml> [k [delta [verify]]] | detect <vocabulary.bin> [gap [time]]\n"); return 2; }
+    if (argc > 3 && std::string(argv[3]) == "detect") return detect(argc, argv);
     const int k = argc > 3 ? std::atoi(argv[3]) : 2, delta = argc > 4 ? std::atoi(argv[4]) : 6;
     const bool verify = argc > 5 && std::string(argv[5]) == "verify";
     try {

@@ -2,11 +2,13 @@
 lmono_keyframes_add_batch for 1, 8, 64 streams at 1241 x 376 with 150 window points, images resident on the device; matches/s of
 lmono_keyframes_match for one current keyframe against 4 and against 1024 stored keyframes; per-kernel times of one 64-stream add and
 of one 1024-keyframe match from the torch profiler's device events; verifies/s of lmono_keyframes_verify (match, PnP RANSAC,
-gates) for the same current keyframe against 4 and 1024 candidates, with the device time of k_pnp_ransac.  Prints one JSON line.  One process; run it under `timeout`;
+gates) for the same current keyframe against 4 and 1024 candidates, with the device time of k_pnp_ransac; with --vocabulary FILE (a BRIEF
+vocabulary in the reference's binary layout, e.g. one of train_brief_vocabulary) also BoW builds/s and queries/s of one store
+at 64 / 1024 / 4096 stored keyframes and of 64 stores per call (detect_loop_batch).  Prints one JSON line.  One process; run it under `timeout`;
 exits non-zero on any HIP error.
 
   timeout 300 python scripts/keyframe_bench.py [--pattern tests/golden/brief_pattern.yml] [--streams 1,8,64] [--old 4,1024]
-                                               [--calls 12] [--warmup 3] [--no-kernels]"""
+                                               [--calls 12] [--warmup 3] [--no-kernels] [--vocabulary FILE] [--stored 64,1024,4096]"""
 import argparse
 import json
 import os
@@ -22,7 +24,7 @@ sys.path.insert(0, ROOT)
 def _kernel_times(prof):
     kern = {}
     for e in prof.key_averages():
-        tag = "k_kf_" if "k_kf_" in e.key else ("k_pnp_" if "k_pnp_" in e.key else None)
+        tag = next((t for t in ("k_kf_", "k_pnp_", "k_bow_") if t in e.key), None)
         if tag:
             name = e.key[e.key.index(tag):].split("(")[0]
             name = name.split("E")[0] if e.key.startswith("_Z") else name
@@ -31,6 +33,62 @@ def _kernel_times(prof):
                 us = getattr(e, "cuda_time_total", 0.0)
             kern[name] = kern.get(name, 0.0) + float(us)
     return kern
+
+
+def _timed(fn, calls, warmup):
+    ms = []
+    for f in range(calls + warmup):
+        t0 = time.perf_counter()
+        fn()                                                                             # every entry point synchronises before it returns
+        if f >= warmup:
+            ms.append((time.perf_counter() - t0) * 1e3)
+    return np.array(ms)
+
+
+def _bow(a, ctx, cam, pat, seeds, lmono_amd, torch):
+    """BoW builds/s (every vector of the store, after the watermark is reset) and queries/s (the last keyframe against all before it)."""
+    voc = lmono_amd.BriefVocabulary(ctx, lmono_amd.load_brief_vocabulary(a.vocabulary))
+    runs = []
+
+    def fill(store, n):
+        for o in range(n):
+            g = seeds[o % 4]
+            store.load(g["keypoints"], g["norm"], g["descriptors"])
+
+    def build(store, n):
+        store.set_vocabulary(voc)                                                        # resets the watermark
+        store.bow(n - 1)
+
+    for n in [int(x) for x in a.stored.split(",")]:
+        store = lmono_amd.KeyFrames(ctx, cam, pat, n, a.max_keypoints)
+        fill(store, n)
+        b = _timed(lambda: build(store, n), a.calls, a.warmup)
+        q = _timed(lambda: store.query(n - 1, 4, -1), a.calls, a.warmup)
+        d = _timed(lambda: store.detect_loop(n - 1, 100), a.calls, a.warmup)
+        run = {"stored": n, "build_ms_median": float(np.median(b)), "bow_builds_per_s": float(n * 1e3 / np.median(b)), "query_ms_median": float(np.median(q)),
+               "query_ms_min": float(q.min()), "queries_per_s": float(1e3 / np.median(q)), "detect_loop_ms_median": float(np.median(d)),
+               "words_mean": float(np.mean([len(store.bow(i)[0]) for i in range(4)]))}
+        if n == max(int(x) for x in a.stored.split(",")) and not a.no_kernels:
+            from torch.profiler import ProfilerActivity, profile
+            with profile(activities=[ProfilerActivity.CUDA, ProfilerActivity.CPU]) as prof:
+                build(store, n)
+                store.query(n - 1, 4, -1)
+                torch.cuda.synchronize()
+            run["kernels_us"] = _kernel_times(prof)
+        runs.append(run)
+        store.close()
+    stores = [lmono_amd.KeyFrames(ctx, cam, pat, 64, a.max_keypoints) for _ in range(64)]
+    for s in stores:
+        s.set_vocabulary(voc)
+        fill(s, 64)
+    curs = [63] * 64
+    lmono_amd.KeyFrames.detect_loop_batch(stores, curs, 20)                              # builds the vectors
+    q = _timed(lambda: lmono_amd.KeyFrames.detect_loop_batch(stores, curs, 20), a.calls, a.warmup)
+    batch = {"streams": 64, "stored": 64, "ms_per_call_median": float(np.median(q)), "queries_per_s": float(64 * 1e3 / np.median(q))}
+    for s in stores:
+        s.close()
+    voc.close()
+    return {"vocabulary": {"file": os.path.basename(a.vocabulary)}, "one_store": runs, "batch": batch}
 
 
 def main():
@@ -45,6 +103,8 @@ def main():
     ap.add_argument("--window", type=int, default=150)
     ap.add_argument("--max-keypoints", type=int, default=8192)
     ap.add_argument("--no-kernels", action="store_true")
+    ap.add_argument("--vocabulary", default=None, help="BRIEF vocabulary file: also measure BoW builds/s and queries/s")
+    ap.add_argument("--stored", default="64,1024,4096")
     a = ap.parse_args()
     import torch
     import lmono_amd
@@ -145,6 +205,8 @@ def main():
             run["kernels_us"] = _kernel_times(prof)
         out["verify"].append(run)
     store.close()
+    if a.vocabulary:
+        out["bow"] = _bow(a, ctx, cam, pat, seeds, lmono_amd, torch)
     print(json.dumps(out))
 
 

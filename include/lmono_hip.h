@@ -629,6 +629,31 @@ int   lmono_pose_graph_optimize(lmono_ctx *, lmono_pose_graph *, int max_iter); 
  * (blocks), accepted steps, rejected steps */
 int   lmono_pose_graph_result(lmono_ctx *, lmono_pose_graph *, double *poses_tq_h, double *stats);
 
+/* ---- camera-LiDAR rotation calibration, ESTIMATE_LASER == 2 ---------------------------------------------------------
+ * Estimator.cc:403-430 and src/initial/AxxbSolver.cc.  Per stream and frame: (1) the essential matrix of the frame's pairs of normalised
+ * points, the Hartley-normalised 8-point fit over all of them (pairs with a non-finite coordinate are dropped; fewer than 9 left: the
+ * identity); (2) R1 = U W V^T, R2 = U W^T V^T, t = +-u3; (3) the cheirality vote of testTriangulation over (R1, t), (R1, -t), (R2, t),
+ * (R2, -t), R1 on a strict majority, the winner transposed; (4) one step of CalibrationExRotation on a running 4 x 4 sum of the
+ * Huber-weighted blocks L(q_cam) - R(q_lidar): rlc = the transposed rotation of the smallest eigenvector, sv = the square roots of the
+ * eigenvalues, descending, ok = frame_count >= count && sv[2] > 0.25.  All fp64, one written order; parity with OpenCV and Eigen is unpinned.
+ * Quaternions are x y z w.  pairs [sum m][4] = prev x, prev y, cur x, cur y, concatenated in call order; m [n] in 0..512.
+ * stats [n][6] = pairs used, the four front counts, the winner (0: R1, 1: R2, -1: the identity by rule).  Refused before any launch, with
+ * no state changed: m > 512 (LMONO_ECAPACITY); a negative m, a stream index out of range or named twice in one call, count < 1, a
+ * non-finite quaternion (LMONO_EINVAL).  Outputs may be NULL.  A stream's bytes do not depend on the batch it travels in. */
+typedef struct lmono_excalib lmono_excalib;
+int  lmono_excalib_create(lmono_ctx *, int n_streams, lmono_excalib **out);
+void lmono_excalib_destroy(lmono_excalib *);
+int  lmono_excalib_reset(lmono_excalib *, int stream);          /* stream -1: all.  frame_count 0, a zero sum, rlc = I */
+/* stages 1-3 alone, stateless: R_out [n][9] = the camera's rotation increment R_{c,k-1}^T R_{c,k} */
+int  lmono_relative_rotation(lmono_ctx *, int n, const int32_t *m, const double *pairs, double *R_out, int32_t *stats);
+/* stage 4 alone on given rotation pairs: q_cam [n][4], q_lidar [n][4] -> rlc [n][9], sv [n][4], huber [n], ok [n] */
+int  lmono_excalib_push(lmono_excalib *, int n, const int32_t *streams, const double *q_cam, const double *q_lidar, int count, double *rlc, double *sv,
+                        double *huber, int32_t *ok);
+/* stages 1-4 of n distinct streams in one launch: q_cam is Quaterniond(R_cam) */
+int  lmono_excalib_step(lmono_excalib *, int n, const int32_t *streams, const int32_t *m, const double *pairs, const double *q_lidar, int count,
+                        double *R_cam, int32_t *stats, double *rlc, double *sv, double *huber, int32_t *ok);
+int  lmono_excalib_state(lmono_excalib *, int stream, int *frame_count, double *M, double *rlc);   /* M [16], rlc [9] */
+
 /* ---- pose composition (laserOdometry: t_w_curr += q_w_curr * t_last_curr; q_w_curr *= q_last_curr) ------- *
  * lmono_pose_prefix_d: poses_d[k - first] = incr[first] (+) ... (+) incr[k] for k in [first, n) (incr[0] is the
  * identity: first = 0 gives poses relative to scan 0, first > 0 poses relative to scan first-1).  lmono_pose_rebase_d: poses[k] <- bases[0] (+) ... (+) bases[n_bases-1] (+) poses[k]; with scans

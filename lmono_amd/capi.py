@@ -22,6 +22,7 @@ SYMBOLS = [
     "lmono_keyframes_load", "lmono_keyframes_match", "lmono_keyframes_images", "lmono_keyframes_get", "lmono_keyframes_verify", "lmono_pnp_ransac",
     "lmono_brief_vocabulary_create", "lmono_brief_vocabulary_destroy", "lmono_brief_vocabulary_transform", "lmono_keyframes_set_vocabulary", "lmono_keyframes_bow",
     "lmono_keyframes_query", "lmono_keyframes_detect_loop", "lmono_keyframes_detect_loop_batch",
+    "lmono_excalib_create", "lmono_excalib_destroy", "lmono_excalib_reset", "lmono_relative_rotation", "lmono_excalib_push", "lmono_excalib_step", "lmono_excalib_state",
     "lmono_pose_graph_create", "lmono_pose_graph_destroy", "lmono_pose_graph_reset", "lmono_pose_graph_info", "lmono_pose_graph_order", "lmono_pose_graph_reduce_buffer", "lmono_pose_graph_set_reduce_buffer", "lmono_pose_graph_linearise",
     "lmono_pose_graph_step", "lmono_pose_graph_optimize", "lmono_pose_graph_result", "lmono_factor_eval", "lmono_factor_eval_d", "lmono_factor_eval_blocks", "lmono_factor_eval_blocks_d",
     "lmono_triangulate", "lmono_outlier_scores", "lmono_shift_depth", "lmono_shift_depth_batch", "lmono_marginalize", "lmono_marg_evaluate", "lmono_marg_second_new", "lmono_ba_batch_create", "lmono_ba_batch_update", "lmono_ba_batch_destroy", "lmono_ba_solve", "lmono_ba_batch_reset", "lmono_ba_batch_read", "lmono_debug_bounds",
@@ -1296,6 +1297,106 @@ def pnp_ransac(ctx, points_3d, points_2d, guess_tq, keys=None, params=None):
                                  ky.ctypes.data, st.ctypes.data, pose.ctypes.data, stats.ctypes.data))
     off = np.concatenate([[0], np.cumsum(cnt)])
     return [st[off[i]:off[i + 1]].copy() for i in range(n)], pose, stats
+
+
+def _excalib_prototypes(L):
+    if getattr(L, "_excalib_ready", False):
+        return
+    L.lmono_excalib_create.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+    L.lmono_excalib_destroy.argtypes = [C.c_void_p]
+    L.lmono_excalib_destroy.restype = None
+    L.lmono_excalib_reset.argtypes = [C.c_void_p, C.c_int]
+    L.lmono_relative_rotation.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 4
+    L.lmono_excalib_push.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 3 + [C.c_int] + [C.c_void_p] * 4
+    L.lmono_excalib_step.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 6
+    L.lmono_excalib_state.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 3
+    L._excalib_ready = True
+
+
+def _pairs_arrays(pairs_list):
+    """A list of [m, 4] arrays -> (m int32 [n], the rows concatenated, with one spare row so that the pointer is never null)."""
+    ps = [np.ascontiguousarray(a, np.float64).reshape(-1, 4) for a in pairs_list]
+    m = np.array([len(a) for a in ps], np.int32)
+    return m, np.concatenate(ps + [np.zeros((1, 4))])
+
+
+def relative_rotation(ctx, pairs_list):
+    """The camera's rotation increment of each problem from its pairs of normalised image points (lmono_relative_rotation, DESIGN.md 6i:
+    essential matrix over all pairs, decomposition, cheirality vote), all problems in one launch.  pairs_list: a list of [m, 4] arrays
+    (prev x, prev y, cur x, cur y; m <= 512) -> (R [n, 3, 3], stats [n, 6] = pairs used, the four front counts, the winner)."""
+    _excalib_prototypes(ctx.L)
+    m, flat = _pairs_arrays(pairs_list)
+    n = len(m)
+    R = np.zeros((n, 3, 3)); stats = np.zeros((n, 6), np.int32)
+    ctx.check(ctx.L.lmono_relative_rotation(ctx.h, n, m.ctypes.data, flat.ctypes.data, R.ctypes.data, stats.ctypes.data))
+    return R, stats
+
+
+class ExtrinsicCalibrator:
+    """The camera-LiDAR rotation calibration of ESTIMATE_LASER == 2 for n_streams independent streams (lmono_excalib_*).
+    Quaternions are x y z w.  `streams`: the stream index of each entry of a call (default 0 .. n-1); a stream may be named once per call."""
+
+    def __init__(self, ctx, n_streams=1, count=10):
+        self.ctx = ctx
+        ctx._children.add(self)
+        _excalib_prototypes(ctx.L)
+        self.n_streams, self.count = int(n_streams), int(count)
+        h = C.c_void_p()
+        self.h = None
+        ctx.check(ctx.L.lmono_excalib_create(ctx.h, self.n_streams, C.byref(h)))
+        self.h = h.value
+
+    def _streams(self, streams, n):
+        st = np.arange(n, dtype=np.int32) if streams is None else np.ascontiguousarray(streams, np.int32).reshape(-1)
+        if len(st) != n:
+            raise LmonoError("ExtrinsicCalibrator: streams and the other arguments differ in length")
+        return st
+
+    def step(self, pairs_list, q_lidar, streams=None):
+        """One frame of each named stream, stages 1-4 in one launch.  q_lidar [n, 4]: the LiDAR's rotation increment over the same frame
+        -> dict(R_cam [n, 3, 3], stats [n, 6], rlc [n, 3, 3], sv [n, 4], huber [n], ok [n] bool)."""
+        m, flat = _pairs_arrays(pairs_list)
+        n = len(m)
+        ql = np.ascontiguousarray(q_lidar, np.float64).reshape(-1, 4)
+        st = self._streams(streams, n)
+        if len(ql) != n:
+            raise LmonoError("ExtrinsicCalibrator.step: pairs_list and q_lidar differ in length")
+        R = np.zeros((n, 3, 3)); stats = np.zeros((n, 6), np.int32); rlc = np.zeros((n, 3, 3)); sv = np.zeros((n, 4)); hub = np.zeros(n); ok = np.zeros(n, np.int32)
+        self.ctx.check(self.ctx.L.lmono_excalib_step(self.h, n, st.ctypes.data, m.ctypes.data, flat.ctypes.data, ql.ctypes.data, self.count, R.ctypes.data,
+                                                     stats.ctypes.data, rlc.ctypes.data, sv.ctypes.data, hub.ctypes.data, ok.ctypes.data))
+        return dict(R_cam=R, stats=stats, rlc=rlc, sv=sv, huber=hub, ok=ok.astype(bool))
+
+    def push(self, q_cam, q_lidar, streams=None):
+        """Stage 4 alone on given rotation pairs q_cam, q_lidar [n, 4] -> dict(rlc, sv, huber, ok)."""
+        qc = np.ascontiguousarray(q_cam, np.float64).reshape(-1, 4); ql = np.ascontiguousarray(q_lidar, np.float64).reshape(-1, 4)
+        n = len(qc)
+        st = self._streams(streams, n)
+        if len(ql) != n:
+            raise LmonoError("ExtrinsicCalibrator.push: q_cam and q_lidar differ in length")
+        rlc = np.zeros((n, 3, 3)); sv = np.zeros((n, 4)); hub = np.zeros(n); ok = np.zeros(n, np.int32)
+        self.ctx.check(self.ctx.L.lmono_excalib_push(self.h, n, st.ctypes.data, qc.ctypes.data, ql.ctypes.data, self.count, rlc.ctypes.data, sv.ctypes.data,
+                                                     hub.ctypes.data, ok.ctypes.data))
+        return dict(rlc=rlc, sv=sv, huber=hub, ok=ok.astype(bool))
+
+    def state(self, s=0):
+        """-> (frame_count, M [4, 4]: the running sum, rlc [3, 3]) of stream s."""
+        fc = C.c_int(0); M = np.zeros((4, 4)); rlc = np.zeros((3, 3))
+        self.ctx.check(self.ctx.L.lmono_excalib_state(self.h, int(s), C.byref(fc), M.ctypes.data, rlc.ctypes.data))
+        return fc.value, M, rlc
+
+    def reset(self, s=None):
+        self.ctx.check(self.ctx.L.lmono_excalib_reset(self.h, -1 if s is None else int(s)))
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.ctx.L.lmono_excalib_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class KeyFrames:

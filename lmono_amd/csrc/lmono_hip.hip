@@ -352,3 +352,4 @@ template <typename H> static int batch_handle_fault(const lmono_ctx *c, int s, H
 #include "pnp_abi.hip"
 #include "bow_abi.hip"
 #include "posegraph_abi.hip"
+#include "excalib_abi.hip"

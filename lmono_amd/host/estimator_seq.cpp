@@ -4,7 +4,9 @@
 //
 // Stream file (doubles): n_frames, TLC[16], then per frame: header, L0_Pos[16], n_loop (0/1) [loop_time_stamp, old_T[3],
 // old_Q[4] w x y z, correct_T[3], correct_Q[4] w x y z], n_features, n_features x (id, x_n, y_n, u, v).
-// Usage: estimator_seq <stream.bin> [new_odometry.txt | -] [sync | async] [streams=N [groups=G] [digest] [more stream files ...]]
+// Usage: estimator_seq <stream.bin> [new_odometry.txt | -] [sync | async] [estimate_laser=K] [streams=N [groups=G] [digest] [more stream files ...]]
+// "estimate_laser=K": Params::ESTIMATE_LASER (default 1).  With 2 the single-stream run finds the camera-LiDAR rotation by hand-eye calibration
+// (Estimator.cc:403-430) and prints one "CAL <frame> <rlc, 9 numbers row-major>" line behind the FRM line of the frame it succeeds on.
 // "async": marginalisation overlapped with the next frame (Estimator::setAsyncMargin); the PRI line (digest of the last prior) and
 // everything else must come out the same bytes as without it.
 // "streams=N": N independent Estimators stepped in lock-step by EstimatorBatch (one batched C-ABI call per numeric step); stream s replays
@@ -110,12 +112,13 @@ int main(int argc, char **argv)
 {
     if (argc < 2) return 2;
     try {
-        int n_streams = 0, n_groups = 1; bool digest_only = false, async = false;
+        int n_streams = 0, n_groups = 1, estimate_laser = -1; bool digest_only = false, async = false;
         std::vector<const char *> files{ argv[1] };
         for (int a = 3; a < argc; a++) {
             const std::string s = argv[a];
             if (s == "async") async = true;
             else if (s == "sync") async = false;
+            else if (s.rfind("estimate_laser=", 0) == 0) estimate_laser = std::atoi(s.c_str() + 15);
             else if (s.rfind("streams=", 0) == 0) n_streams = std::atoi(s.c_str() + 8);
             else if (s.rfind("groups=", 0) == 0) n_groups = std::max(1, std::atoi(s.c_str() + 7));
             else if (s == "digest") digest_only = true;
@@ -123,6 +126,10 @@ int main(int argc, char **argv)
         }
         HipContext hip(0);
         Params p;
+        if (estimate_laser >= 0) {
+            if (estimate_laser > 2) { std::fprintf(stderr, "estimator_seq: estimate_laser is 0, 1 or 2\n"); return 2; }
+            p.ESTIMATE_LASER = estimate_laser;
+        }
         if (n_streams <= 0) {
             const Stream st = parse_stream(argv[1]);
             Estimator est(hip, p);
@@ -133,12 +140,19 @@ int main(int argc, char **argv)
             for (size_t f = 0; f < st.frames.size(); f++) {
                 const Frame &fr = st.frames[f];
                 if (fr.has_loop) est.setLoopFrame(fr.loop);
-                const bool was_inited = est.stage_flag == Estimator::INITED;
+                const bool was_inited = est.stage_flag == Estimator::INITED, was_calibrated = est.extrinsic_calibrated;
                 const auto t0 = std::chrono::steady_clock::now();
                 const bool keyframe = est.processImage(fr.header, fr.image, fr.L0);
                 const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
                 if (was_inited) { solve_ms += ms; solves++; }
                 frm_line(out, (int)f, keyframe, est);
+                if (est.extrinsic_calibrated && !was_calibrated) {
+                    std::string c = "CAL " + std::to_string(f);
+                    char buf[64];
+                    for (int j = 0; j < 9; j++) { std::snprintf(buf, sizeof buf, " %.17g", est.calib_rlc[j]); c += buf; }
+                    c += "\n";
+                    out.add(c.c_str());
+                }
             }
             est.marginWait();
             tail_lines(out, est);

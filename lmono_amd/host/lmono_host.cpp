@@ -67,6 +67,42 @@ int FeatureManager::getFeatureCount()
     for (auto &it : feature) { it.used_num = (int)it.feature_per_frame.size(); if (it.used_num >= params->TRACK_CNT) cnt++; }
     return cnt;
 }
+std::vector<std::array<double, 4>> FeatureManager::getCorresponding(int frame_count_l, int frame_count_r) const
+{
+    std::vector<std::array<double, 4>> corres;
+    for (const auto &it : feature) {
+        if (it.start_frame <= frame_count_l && it.endFrame() >= frame_count_r) {
+            const FeaturePerFrame &a = it.feature_per_frame[(size_t)(frame_count_l - it.start_frame)], &b = it.feature_per_frame[(size_t)(frame_count_r - it.start_frame)];
+            corres.push_back({ a.pt[0], a.pt[1], b.pt[0], b.pt[1] });
+        }
+    }
+    return corres;
+}
+
+// ---- AXXBSolver ---------------------------------------------------------------------------------------------------
+// Weak references: this file is also linked against implementations of the C ABI that stop at the frame loop's numeric steps and have no
+// calibration (a CPU baseline of the loop); there ESTIMATE_LASER == 2 is refused when the first frame asks for it, everything else links as before.
+#pragma weak lmono_excalib_create
+#pragma weak lmono_excalib_destroy
+#pragma weak lmono_excalib_step
+AXXBSolver::AXXBSolver(HipContext &hip) : hip_(hip)
+{
+    if (!lmono_excalib_create || !lmono_excalib_destroy || !lmono_excalib_step)
+        throw std::runtime_error("AXXBSolver: the C ABI this program is linked against has no lmono_excalib_* (ESTIMATE_LASER == 2 needs the HIP library)");
+    hip_.check(lmono_excalib_create(hip_.get(), 1, &h_), "lmono_excalib_create");
+}
+AXXBSolver::~AXXBSolver() { if (h_) lmono_excalib_destroy(h_); }
+bool AXXBSolver::CalibrationExRotation(const std::vector<std::array<double, 4>> &corres, const double delta_q_lidar[4], double calib_rlc_result[9], int count)
+{
+    const int32_t stream = 0, m = (int32_t)std::min<size_t>(corres.size(), LMONO_TRACK_MAX_POINTS);
+    double rlc[9];
+    int32_t ok = 0;
+    hip_.check(lmono_excalib_step(h_, 1, &stream, &m, corres.empty() ? nullptr : corres[0].data(), delta_q_lidar, count, nullptr, nullptr, rlc, nullptr, nullptr, &ok),
+               "lmono_excalib_step");
+    if (!ok) return false;
+    std::memcpy(calib_rlc_result, rlc, sizeof(rlc));
+    return true;
+}
 std::vector<double> FeatureManager::getDepthVector()
 {
     std::vector<double> dep;
@@ -625,11 +661,30 @@ void Estimator::pushOdometryRow()
     R_to_q(Rs[WINDOW_SIZE].m, &row[4]);
     new_odometry.push_back(row);
 }
+// Estimator.cc:403-430.  laser_delta_q: the rotation of prev_laser_pose^-1 transform_to_init, R_prev^T R_cur
+void Estimator::calibrateExtrinsicRotation(const double transform_to_init[16])
+{
+    if (frame_count == 0) return;
+    double Rp_T[9], Rc[9], dR[9], laser_delta_q[4];
+    for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) { Rp_T[i * 3 + j] = prev_laser_pose[j * 4 + i]; Rc[i * 3 + j] = transform_to_init[i * 4 + j]; }
+    mat_mul(Rp_T, Rc, dR);
+    R_to_q(dR, laser_delta_q);
+    if (!axxbsolver_) axxbsolver_.reset(new AXXBSolver(hip_));
+    const std::vector<std::array<double, 4>> corres = feature_manager.getCorresponding(frame_count - 1, frame_count);
+    double calib_rlc_result[9];
+    if (axxbsolver_->CalibrationExRotation(corres, laser_delta_q, calib_rlc_result, 10)) {
+        for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) TLC[i * 4 + j] = calib_rlc_result[i * 3 + j];
+        std::memcpy(calib_rlc, calib_rlc_result, sizeof(calib_rlc));
+        extrinsic_calibrated = true;
+        p_.ESTIMATE_LASER = 1;
+    }
+}
 bool Estimator::processImage(double header, const FeatureManager::Image &image, const double transform_to_init[16])
 {
     g_clock.start();
     bool keyframe = false;
     preFrame(header, image, transform_to_init, &keyframe);
+    if (p_.ESTIMATE_LASER == 2) calibrateExtrinsicRotation(transform_to_init);
     if (stage_flag == NOT_INITED) {
         if (frame_count == WINDOW_SIZE) {
             if (p_.ESTIMATE_LASER != 2 && runInitialization()) {
@@ -660,6 +715,7 @@ bool Estimator::processImage(double header, const FeatureManager::Image &image, 
         g_clock.frames++;
     }
     if (stage_flag == INITED) pushOdometryRow();             // new_odometry.txt row, :634-645
+    std::memcpy(prev_laser_pose, transform_to_init, sizeof(prev_laser_pose));      // :651
     return keyframe;
 }
 

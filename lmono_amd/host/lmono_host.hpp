@@ -90,6 +90,8 @@ public:
     double computeParallax(const FeaturePerId &it_per_id, int frame_count) const;   // :279-313
     void clearDepth();                                       // :29-36
     void clearState() { feature.clear(); }
+    // :592-618: the normalised points (x, y; z = 1) of every track that spans both frames, in list order -> rows prev x, prev y, cur x, cur y
+    std::vector<std::array<double, 4>> getCorresponding(int frame_count_l, int frame_count_r) const;
     int last_track_num = 0, long_track_num = 0, new_feature_num = 0;
     // packs tracks with used_num >= TRACK_CNT for the kernels: start, offsets, points (anchor first)
     void pack(std::vector<int> &start, std::vector<int> &off, std::vector<double> &pts, std::vector<double> &depth, bool all_tracks);
@@ -118,6 +120,23 @@ struct ShiftPack { std::vector<double> pt, dep; double frames[40]; };     // lmo
 
 class EstimatorBatch;
 class MarginWorker;
+
+// ---- AXXBSolver (src/initial/AxxbSolver.cc) over the C ABI: a one-stream lmono_excalib handle.  The Rc / Rlidar / Rc_g lists of the reference are
+// the handle's 4 x 4 running sum (observation A).
+class AXXBSolver {
+public:
+    explicit AXXBSolver(HipContext &hip);
+    ~AXXBSolver();
+    AXXBSolver(const AXXBSolver &) = delete;
+    AXXBSolver &operator=(const AXXBSolver &) = delete;
+    // solveRelativeR(corres) and CalibrationExRotation(Quaterniond(that), delta_q_lidar, calib_rlc_result, count) as ONE lmono_excalib_step;
+    // delta_q_lidar x y z w.  true: calib_rlc_result [9] holds rlc.  The device step holds LMONO_TRACK_MAX_POINTS (512) pairs, the tracker's own
+    // limit: of a longer list (the reference has no limit) the first 512 in list order are used
+    bool CalibrationExRotation(const std::vector<std::array<double, 4>> &corres, const double delta_q_lidar[4], double calib_rlc_result[9], int count);
+private:
+    HipContext &hip_;
+    lmono_excalib *h_ = nullptr;
+};
 
 // ---- Estimator ------------------------------------------------------------------------------------------------------
 class Estimator {
@@ -148,6 +167,12 @@ public:
     StageFlag stage_flag = NOT_INITED;
     double Header[WINDOW_SIZE + 1] = { 0 };
     Vec3 last_laser_t = { { 0, 0, 0 } };
+    double prev_laser_pose[16] = { 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1 };   // the previous frame's LiDAR pose (Estimator.cc:78, :651)
+    // ESTIMATE_LASER == 2 (:403-430): the camera-LiDAR rotation is found by hand-eye calibration before the estimator initialises; on success
+    // TLC's rotation is replaced, this estimator's ESTIMATE_LASER becomes 1 and calib_rlc keeps the result
+    bool extrinsic_calibrated = false;
+    double calib_rlc[9] = { 1, 0, 0, 0, 1, 0, 0, 0, 1 };
+    void calibrateExtrinsicRotation(const double transform_to_init[16]);
     bool loop_closure = false;
     struct LoopFrame { double loop_time_stamp; double old_T[3], old_Q[4], correct_T[3], correct_Q[4]; };   // quaternions w x y z (Estimator.h:60-104)
     std::vector<LoopFrame> loop_buf;
@@ -209,6 +234,7 @@ public:
 private:
     HipContext &hip_;
     lmono_ba_batch *ba_batch_ = nullptr;       // the window problem's device arrays, kept from frame to frame
+    std::unique_ptr<AXXBSolver> axxbsolver_;   // created by the first frame that runs with ESTIMATE_LASER == 2
     std::unique_ptr<HipContext> margin_hip_;   // setAsyncMargin: the context marginalisation runs on
     // the overlapped marginalisation's worker: ONE host thread for the Estimator's lifetime takes the jobs (a thread per frame -- std::async -- cost the
     // frame loop ~70 us per frame); at most one job is pending
@@ -225,6 +251,8 @@ private:
 // n_windows), the host halves around the calls run on a small thread pool.  Every stream's output is the bytes of its own single-stream run: the kernels
 // own one window per workgroup (or one track per thread) and form their sums in an order fixed by the window alone.
 // The streams must be at the same frame of their sequences (same frame_count / stage_flag): they are created together and fed one frame each per call.
+// ESTIMATE_LASER == 2 is not run here: streams finish calibrating on different frames and would leave the lock-step; such streams stay
+// NOT_INITED as before.  A single Estimator calibrates.
 class HostPool;
 class EstimatorBatch {
 public:

@@ -85,10 +85,15 @@ std::vector<std::array<double, 4>> FeatureManager::getCorresponding(int frame_co
 #pragma weak lmono_excalib_create
 #pragma weak lmono_excalib_destroy
 #pragma weak lmono_excalib_step
+#pragma weak lmono_excalib_reset
+static void require_excalib()
+{
+    if (!lmono_excalib_create || !lmono_excalib_destroy || !lmono_excalib_step || !lmono_excalib_reset)
+        throw std::runtime_error("AXXBSolver: the C ABI this program is linked against has no lmono_excalib_* (ESTIMATE_LASER == 2 needs the HIP library)");
+}
 AXXBSolver::AXXBSolver(HipContext &hip) : hip_(hip)
 {
-    if (!lmono_excalib_create || !lmono_excalib_destroy || !lmono_excalib_step)
-        throw std::runtime_error("AXXBSolver: the C ABI this program is linked against has no lmono_excalib_* (ESTIMATE_LASER == 2 needs the HIP library)");
+    require_excalib();
     hip_.check(lmono_excalib_create(hip_.get(), 1, &h_), "lmono_excalib_create");
 }
 AXXBSolver::~AXXBSolver() { if (h_) lmono_excalib_destroy(h_); }
@@ -662,13 +667,18 @@ void Estimator::pushOdometryRow()
     new_odometry.push_back(row);
 }
 // Estimator.cc:403-430.  laser_delta_q: the rotation of prev_laser_pose^-1 transform_to_init, R_prev^T R_cur
-void Estimator::calibrateExtrinsicRotation(const double transform_to_init[16])
+static void laser_increment(const double prev_laser_pose[16], const double transform_to_init[16], double laser_delta_q[4])
 {
-    if (frame_count == 0) return;
-    double Rp_T[9], Rc[9], dR[9], laser_delta_q[4];
+    double Rp_T[9], Rc[9], dR[9];
     for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) { Rp_T[i * 3 + j] = prev_laser_pose[j * 4 + i]; Rc[i * 3 + j] = transform_to_init[i * 4 + j]; }
     mat_mul(Rp_T, Rc, dR);
     R_to_q(dR, laser_delta_q);
+}
+void Estimator::calibrateExtrinsicRotation(const double transform_to_init[16])
+{
+    if (frame_count == 0) return;
+    double laser_delta_q[4];
+    laser_increment(prev_laser_pose, transform_to_init, laser_delta_q);
     if (!axxbsolver_) axxbsolver_.reset(new AXXBSolver(hip_));
     const std::vector<std::array<double, 4>> corres = feature_manager.getCorresponding(frame_count - 1, frame_count);
     double calib_rlc_result[9];
@@ -864,20 +874,32 @@ struct EstimatorBatch::Work {
     std::vector<TrackPack> tp;
     std::vector<SolvePack> sp;
     std::vector<ShiftPack> shp;
-    std::vector<char> due;
+    std::vector<char> due, kf, cls;
+    bool launched = false;          // a solve is in flight: Begin has returned, Finish has not run
+    // the streams of this frame, each list in ascending stream order (the vectors keep their capacity): given a frame | still calibrating | the classes |
+    // init + run = the windows of the triangulation, the solve and what follows it
+    std::vector<int> present, cal, init, run, solve;
+    // the calibration step: per stream the frame's pairs and LiDAR increment, then the call's concatenated arrays
+    std::vector<std::vector<std::array<double, 4>>> corres;
+    std::vector<int32_t> cal_ids, cal_m, cal_ok;
+    std::vector<double> cal_q, cal_pairs, cal_rlc;
     // concatenated arrays of the calls
     std::vector<int> foff, ooff, start, off, flag, flags, obs_feat, obs_i, obs_j, shoff;
     std::vector<double> R, P, tlc, pts, depth, score, poses, ex, invd, obs_pts, laser, prior_T, summary, frames, shpt, shdep, shout;
 };
 
-EstimatorBatch::EstimatorBatch(HipContext &hip, const Params &p, int n_streams, int host_threads) : hip_(hip), p_(p)
+EstimatorBatch::EstimatorBatch(HipContext &hip, const Params &p, int n_streams, int host_threads, int capacity) : hip_(hip), p_(p)
 {
     if (n_streams < 1) throw std::invalid_argument("EstimatorBatch: n_streams must be >= 1");
+    if (capacity != 0 && capacity < n_streams) throw std::invalid_argument("EstimatorBatch: the capacity is below n_streams");
+    capacity_ = capacity ? capacity : n_streams;
+    est_.reserve((size_t)capacity_);
     for (int s = 0; s < n_streams; s++) est_.emplace_back(new Estimator(hip, p));
+    pending_.assign((size_t)capacity_, (char)ABSENT);
     int nt = host_threads;
     if (nt <= 0) { if (const char *e = std::getenv("LMONO_HOST_THREADS")) nt = std::atoi(e); }
     if (nt <= 0) nt = (int)std::min(16u, std::max(1u, std::thread::hardware_concurrency()));
-    pool_ = shared_host_pool(std::min(nt, n_streams));
+    pool_ = shared_host_pool(std::min(nt, capacity_));
     work_.reset(new Work());
 }
 EstimatorBatch::~EstimatorBatch()
@@ -885,7 +907,25 @@ EstimatorBatch::~EstimatorBatch()
     try { marginWait(); } catch (...) {}
     margin_worker_.reset();
     if (ba_batch_) lmono_ba_batch_destroy(ba_batch_);
+    if (excalib_) lmono_excalib_destroy(excalib_);
     g_bclock.print(size());
+}
+int EstimatorBatch::addStream()
+{
+    if (open_) throw std::logic_error("EstimatorBatch::addStream: a frame is between processImageBegin and processImageFinish");
+    if (size() >= capacity_) throw std::length_error("EstimatorBatch::addStream: the batch is at its capacity of " + std::to_string(capacity_) + " streams");
+    marginWait();                                    // (the worker walks est_)
+    est_.emplace_back(new Estimator(hip_, p_));
+    return size() - 1;
+}
+Estimator &EstimatorBatch::resetStream(int s)
+{
+    if (open_) throw std::logic_error("EstimatorBatch::resetStream: a frame is between processImageBegin and processImageFinish");
+    if (s < 0 || s >= size()) throw std::out_of_range("EstimatorBatch::resetStream: no stream " + std::to_string(s));
+    marginWait();                                    // the worker writes est_[s]->last_marginalization_info
+    est_[(size_t)s].reset(new Estimator(hip_, p_));
+    if (excalib_) hip_.check(lmono_excalib_reset(excalib_, s), "lmono_excalib_reset");
+    return *est_[(size_t)s];
 }
 void EstimatorBatch::marginWait() { if (margin_worker_) margin_worker_->wait(); }
 void EstimatorBatch::setAsyncMargin(bool on)
@@ -899,78 +939,86 @@ namespace {
 template <typename T> void fit(std::vector<T> &v, size_t n) { if (v.size() < n) v.resize(n); }
 }
 
-// the tracks of every stream (w.tp, packed by the pass before) as one set of windows: w.foff / w.ooff and the concatenated arrays
-void EstimatorBatch::concatTracks()
+// the tracks of the streams ids (w.tp, packed by the pass before) as one set of windows, window k = stream ids[k]: w.foff / w.ooff and the concatenated arrays
+void EstimatorBatch::concatTracks(const std::vector<int> &ids)
 {
     Work &w = *work_;
-    const int N = size();
+    const int N = (int)ids.size();
     w.foff.assign((size_t)N + 1, 0); w.ooff.assign((size_t)N + 1, 0);
-    for (int s = 0; s < N; s++) { w.foff[(size_t)s + 1] = w.foff[(size_t)s] + (int)w.tp[(size_t)s].start.size(); w.ooff[(size_t)s + 1] = w.ooff[(size_t)s] + (int)w.tp[(size_t)s].pts.size() / 2; }
+    for (int k = 0; k < N; k++) {
+        const TrackPack &t = w.tp[(size_t)ids[(size_t)k]];
+        w.foff[(size_t)k + 1] = w.foff[(size_t)k] + (int)t.start.size(); w.ooff[(size_t)k + 1] = w.ooff[(size_t)k] + (int)t.pts.size() / 2;
+    }
     const int TF = w.foff[(size_t)N], TO = w.ooff[(size_t)N];
     fit(w.R, (size_t)N * 99); fit(w.P, (size_t)N * 33); fit(w.tlc, (size_t)N * 16); fit(w.pts, (size_t)TO * 2 + 2); fit(w.depth, (size_t)TF + 1);
     fit(w.start, (size_t)TF + 1); fit(w.off, (size_t)TF + 1); fit(w.flag, (size_t)TF + 1); fit(w.score, (size_t)TF + 1);
-    pool_->run(N, [&](int s) {
+    pool_->run(N, [&](int k) {
+        const int s = ids[(size_t)k];
         const TrackPack &t = w.tp[(size_t)s];
-        std::memcpy(&w.R[(size_t)s * 99], t.R, sizeof(t.R)); std::memcpy(&w.P[(size_t)s * 33], t.P, sizeof(t.P)); std::memcpy(&w.tlc[(size_t)s * 16], est_[(size_t)s]->TLC, 128);
-        const int f0 = w.foff[(size_t)s], o0 = w.ooff[(size_t)s];
-        for (size_t k = 0; k < t.start.size(); k++) { w.start[(size_t)f0 + k] = t.start[k]; w.off[(size_t)f0 + k] = o0 + t.off[k]; w.depth[(size_t)f0 + k] = t.depth[k]; }
+        std::memcpy(&w.R[(size_t)k * 99], t.R, sizeof(t.R)); std::memcpy(&w.P[(size_t)k * 33], t.P, sizeof(t.P)); std::memcpy(&w.tlc[(size_t)k * 16], est_[(size_t)s]->TLC, 128);
+        const int f0 = w.foff[(size_t)k], o0 = w.ooff[(size_t)k];
+        for (size_t i = 0; i < t.start.size(); i++) { w.start[(size_t)f0 + i] = t.start[i]; w.off[(size_t)f0 + i] = o0 + t.off[i]; w.depth[(size_t)f0 + i] = t.depth[i]; }
         if (!t.pts.empty()) std::memcpy(&w.pts[(size_t)o0 * 2], t.pts.data(), t.pts.size() * sizeof(double));
     });
     w.off[(size_t)TF] = TO;
 }
-// FeatureManager::triangulate of every stream: one lmono_triangulate over N windows (results: w.depth, w.flag by w.foff)
-void EstimatorBatch::callTriangulate()
+// FeatureManager::triangulate of the streams ids: one lmono_triangulate over their windows (results: w.depth, w.flag by w.foff)
+void EstimatorBatch::callTriangulate(const std::vector<int> &ids)
 {
     Work &w = *work_;
-    concatTracks();
-    const int N = size();
+    concatTracks(ids);
+    const int N = (int)ids.size();
     if (w.foff[(size_t)N] == 0) return;
     std::fill(w.flag.begin(), w.flag.begin() + w.foff[(size_t)N], 0);
     hip_.check(lmono_triangulate(hip_.get(), N, w.foff.data(), w.R.data(), w.P.data(), w.tlc.data(), w.start.data(), w.off.data(), w.pts.data(), w.depth.data(), w.flag.data(),
                                  p_.TRACK_CNT, WINDOW_SIZE, p_.FACTOR_WEIGHT, 50), "lmono_triangulate");
 }
-void EstimatorBatch::applyTriangulate(int s)
+void EstimatorBatch::applyTriangulate(int k, int s)
 {
     Work &w = *work_;
-    if (w.foff[(size_t)s + 1] > w.foff[(size_t)s]) est_[(size_t)s]->feature_manager.triangulateApply(&w.depth[(size_t)w.foff[(size_t)s]], &w.flag[(size_t)w.foff[(size_t)s]]);
+    if (w.foff[(size_t)k + 1] > w.foff[(size_t)k]) est_[(size_t)s]->feature_manager.triangulateApply(&w.depth[(size_t)w.foff[(size_t)k]], &w.flag[(size_t)w.foff[(size_t)k]]);
 }
-// Estimator::outliersRejection's statistic for every stream: one lmono_outlier_scores over N windows (results: w.score by w.foff)
-void EstimatorBatch::callOutliers()
+// Estimator::outliersRejection's statistic for the streams ids: one lmono_outlier_scores over their windows (results: w.score by w.foff)
+void EstimatorBatch::callOutliers(const std::vector<int> &ids)
 {
     Work &w = *work_;
-    concatTracks();
-    const int N = size();
+    concatTracks(ids);
+    const int N = (int)ids.size();
     if (w.foff[(size_t)N] == 0) return;
     hip_.check(lmono_outlier_scores(hip_.get(), N, w.foff.data(), w.R.data(), w.P.data(), w.tlc.data(), w.start.data(), w.off.data(), w.pts.data(), w.depth.data(),
                                     p_.TRACK_CNT, p_.FACTOR_WEIGHT, w.score.data()), "lmono_outlier_scores");
 }
-void EstimatorBatch::applyOutliers(int s, double error)
+void EstimatorBatch::applyOutliers(int k, int s, double error)
 {
     Work &w = *work_;
-    if (w.foff[(size_t)s + 1] == w.foff[(size_t)s]) return;
+    if (w.foff[(size_t)k + 1] == w.foff[(size_t)k]) return;
     std::set<int> removeIndex;
-    est_[(size_t)s]->applyOutlierScores(&w.score[(size_t)w.foff[(size_t)s]], error, removeIndex);
+    est_[(size_t)s]->applyOutlierScores(&w.score[(size_t)w.foff[(size_t)k]], error, removeIndex);
     est_[(size_t)s]->feature_manager.removeOutlier(removeIndex);
 }
-// Estimator::optimization's solve for every stream (w.sp, packed by the pass before): N windows in one lmono_ba_batch_update + lmono_ba_solve + lmono_ba_batch_read
-void EstimatorBatch::callSolve()
+// Estimator::optimization's solve for the streams ids (w.sp, packed by the pass before): their windows in one lmono_ba_batch_update + lmono_ba_solve + lmono_ba_batch_read
+void EstimatorBatch::callSolve(const std::vector<int> &ids)
 {
     Work &w = *work_;
-    const int N = size();
+    const int N = (int)ids.size();
     w.foff.assign((size_t)N + 1, 0); w.ooff.assign((size_t)N + 1, 0);
-    for (int s = 0; s < N; s++) { w.foff[(size_t)s + 1] = w.foff[(size_t)s] + w.sp[(size_t)s].F; w.ooff[(size_t)s + 1] = w.ooff[(size_t)s] + (int)w.sp[(size_t)s].obs_feat.size(); }
+    for (int k = 0; k < N; k++) {
+        const SolvePack &q = w.sp[(size_t)ids[(size_t)k]];
+        w.foff[(size_t)k + 1] = w.foff[(size_t)k] + q.F; w.ooff[(size_t)k + 1] = w.ooff[(size_t)k] + (int)q.obs_feat.size();
+    }
     const int TF = w.foff[(size_t)N], TO = w.ooff[(size_t)N];
     fit(w.flags, (size_t)N * 4); fit(w.obs_feat, (size_t)TO + 1); fit(w.obs_i, (size_t)TO + 1); fit(w.obs_j, (size_t)TO + 1);
     fit(w.poses, (size_t)N * 77); fit(w.ex, (size_t)N * 7); fit(w.invd, (size_t)TF + 1); fit(w.obs_pts, (size_t)TO * 4 + 4); fit(w.laser, (size_t)N * 240); fit(w.prior_T, (size_t)N * 16);
     fit(w.summary, (size_t)N * 6);
-    pool_->run(N, [&](int s) {
+    pool_->run(N, [&](int k) {
+        const int s = ids[(size_t)k];
         const SolvePack &q = w.sp[(size_t)s];
         Estimator &e = *est_[(size_t)s];
-        std::memcpy(&w.flags[(size_t)s * 4], q.flags, sizeof(q.flags));
-        std::memcpy(&w.poses[(size_t)s * 77], q.poses, sizeof(q.poses)); std::memcpy(&w.ex[(size_t)s * 7], e.para_ex[0], 56);
-        std::memcpy(&w.laser[(size_t)s * 240], q.laser, sizeof(q.laser)); std::memcpy(&w.prior_T[(size_t)s * 16], e.TLC, 128);
-        if (q.F > 0) std::memcpy(&w.invd[(size_t)w.foff[(size_t)s]], e.para_depth_inv.data(), (size_t)q.F * sizeof(double));
-        const size_t o0 = (size_t)w.ooff[(size_t)s], no = q.obs_feat.size();
+        std::memcpy(&w.flags[(size_t)k * 4], q.flags, sizeof(q.flags));
+        std::memcpy(&w.poses[(size_t)k * 77], q.poses, sizeof(q.poses)); std::memcpy(&w.ex[(size_t)k * 7], e.para_ex[0], 56);
+        std::memcpy(&w.laser[(size_t)k * 240], q.laser, sizeof(q.laser)); std::memcpy(&w.prior_T[(size_t)k * 16], e.TLC, 128);
+        if (q.F > 0) std::memcpy(&w.invd[(size_t)w.foff[(size_t)k]], e.para_depth_inv.data(), (size_t)q.F * sizeof(double));
+        const size_t o0 = (size_t)w.ooff[(size_t)k], no = q.obs_feat.size();
         if (no) {
             std::memcpy(&w.obs_feat[o0], q.obs_feat.data(), no * sizeof(int)); std::memcpy(&w.obs_i[o0], q.obs_i.data(), no * sizeof(int));
             std::memcpy(&w.obs_j[o0], q.obs_j.data(), no * sizeof(int)); std::memcpy(&w.obs_pts[o0 * 4], q.obs_pts.data(), no * 4 * sizeof(double));
@@ -987,7 +1035,7 @@ void EstimatorBatch::callSolve()
         ba_batch_ = lmono_ba_batch_create(hip_.get(), &d);
         if (!ba_batch_) throw std::runtime_error(std::string("lmono_ba_batch_create: ") + lmono_last_error(hip_.get()));
     } else
-        hip_.check(lmono_ba_batch_update(hip_.get(), ba_batch_, &d), "lmono_ba_batch_update");
+        hip_.check(lmono_ba_batch_update(hip_.get(), ba_batch_, &d), "lmono_ba_batch_update");      // (the number of windows may differ from call to call)
     g_bclock.lap(5);
     hip_.check(lmono_ba_solve(hip_.get(), ba_batch_, p_.NUM_ITERATIONS), "lmono_ba_solve");       // asynchronous on the context stream
 }
@@ -997,17 +1045,18 @@ void EstimatorBatch::readSolve()
     hip_.check(lmono_ba_batch_read(hip_.get(), ba_batch_, w.poses.data(), w.ex.data(), w.invd.data(), w.summary.data()), "lmono_ba_batch_read");
     g_bclock.lap(6);
 }
-void EstimatorBatch::applySolve(int s)
+void EstimatorBatch::applySolve(int k, int s)
 {
     Work &w = *work_;
-    est_[(size_t)s]->unpackSolve(w.sp[(size_t)s], &w.poses[(size_t)s * 77], &w.ex[(size_t)s * 7], &w.invd[(size_t)w.foff[(size_t)s]], &w.summary[(size_t)s * 6]);
+    est_[(size_t)s]->unpackSolve(w.sp[(size_t)s], &w.poses[(size_t)k * 77], &w.ex[(size_t)k * 7], &w.invd[(size_t)w.foff[(size_t)k]], &w.summary[(size_t)k * 6]);
 }
 
-// Estimator::margin of every stream (packs filled by the pass before): the MARGIN_OLD streams in one lmono_marginalize, the MARGIN_SECOND_NEW ones in one
-// lmono_marg_second_new -- on the marginalisation context and its worker thread when overlapped (the concatenation happens there too)
+// Estimator::margin of every stream that solved (packs indexed by stream, filled by the pass before; kind 0: not this frame): the MARGIN_OLD streams in one
+// lmono_marginalize, the MARGIN_SECOND_NEW ones in one lmono_marg_second_new -- on the marginalisation context and its worker thread when overlapped (the
+// concatenation happens there too)
 void EstimatorBatch::submitMargin(std::shared_ptr<std::vector<MargPack>> packs)
 {
-    const int N = size();
+    const int N = (int)packs->size();
     HipContext *h = async_margin_ ? margin_hip_.get() : &hip_;
     auto job = [this, h, packs, N]() {
         std::vector<int> olds, seconds;
@@ -1062,22 +1111,80 @@ void EstimatorBatch::submitMargin(std::shared_ptr<std::vector<MargPack>> packs)
     margin_worker_->submit(std::move(job));
 }
 
-// the depth shifts of every stream whose slide is removeBackShiftDepth (w.due / w.shp, filled by the pass before): one lmono_shift_depth_batch
-void EstimatorBatch::callShift()
+// the depth shifts of the streams ids whose slide is removeBackShiftDepth (w.due / w.shp, filled by the pass before): one lmono_shift_depth_batch
+void EstimatorBatch::callShift(const std::vector<int> &ids)
 {
     Work &w = *work_;
-    const int N = size();
+    const int N = (int)ids.size();
     w.shoff.assign((size_t)N + 1, 0);
-    for (int s = 0; s < N; s++) w.shoff[(size_t)s + 1] = w.shoff[(size_t)s] + (w.due[(size_t)s] ? (int)w.shp[(size_t)s].dep.size() : 0);
+    for (int k = 0; k < N; k++) { const int s = ids[(size_t)k]; w.shoff[(size_t)k + 1] = w.shoff[(size_t)k] + (w.due[(size_t)s] ? (int)w.shp[(size_t)s].dep.size() : 0); }
     const int T = w.shoff[(size_t)N];
     fit(w.frames, (size_t)N * 40); fit(w.shpt, (size_t)T * 2 + 2); fit(w.shdep, (size_t)T + 1); fit(w.shout, (size_t)T + 1);
-    for (int s = 0; s < N; s++) {
-        if (!w.due[(size_t)s]) { std::memset(&w.frames[(size_t)s * 40], 0, 40 * sizeof(double)); continue; }
-        std::memcpy(&w.frames[(size_t)s * 40], w.shp[(size_t)s].frames, sizeof(w.shp[(size_t)s].frames));
+    for (int k = 0; k < N; k++) {
+        const int s = ids[(size_t)k];
+        if (!w.due[(size_t)s]) { std::memset(&w.frames[(size_t)k * 40], 0, 40 * sizeof(double)); continue; }
+        std::memcpy(&w.frames[(size_t)k * 40], w.shp[(size_t)s].frames, sizeof(w.shp[(size_t)s].frames));
         const size_t n = w.shp[(size_t)s].dep.size();
-        if (n) { std::memcpy(&w.shpt[(size_t)w.shoff[(size_t)s] * 2], w.shp[(size_t)s].pt.data(), n * 2 * sizeof(double)); std::memcpy(&w.shdep[(size_t)w.shoff[(size_t)s]], w.shp[(size_t)s].dep.data(), n * sizeof(double)); }
+        if (n) { std::memcpy(&w.shpt[(size_t)w.shoff[(size_t)k] * 2], w.shp[(size_t)s].pt.data(), n * 2 * sizeof(double)); std::memcpy(&w.shdep[(size_t)w.shoff[(size_t)k]], w.shp[(size_t)s].dep.data(), n * sizeof(double)); }
     }
     if (T > 0) hip_.check(lmono_shift_depth_batch(hip_.get(), N, w.frames.data(), w.shoff.data(), w.shpt.data(), w.shdep.data(), w.shout.data()), "lmono_shift_depth_batch");
+}
+
+// Estimator::calibrateExtrinsicRotation for the streams w.cal (their pairs and LiDAR increments formed by the pass before): ONE lmono_excalib_step, then what
+// follows a success, stream by stream
+void EstimatorBatch::callCalibrate()
+{
+    Work &w = *work_;
+    const int n = (int)w.cal.size();
+    if (!excalib_) {
+        require_excalib();
+        hip_.check(lmono_excalib_create(hip_.get(), capacity_, &excalib_), "lmono_excalib_create");
+    }
+    w.cal_ids.resize((size_t)n); w.cal_m.resize((size_t)n); w.cal_ok.assign((size_t)n, 0);
+    fit(w.cal_rlc, (size_t)n * 9);
+    size_t total = 0;
+    for (int k = 0; k < n; k++) {
+        const int s = w.cal[(size_t)k];
+        w.cal_ids[(size_t)k] = s;
+        w.cal_m[(size_t)k] = (int32_t)std::min<size_t>(w.corres[(size_t)s].size(), LMONO_TRACK_MAX_POINTS);      // as AXXBSolver: the first 512 in list order
+        total += (size_t)w.cal_m[(size_t)k];
+    }
+    fit(w.cal_pairs, total * 4 + 4);
+    total = 0;
+    for (int k = 0; k < n; k++) {
+        const size_t m = (size_t)w.cal_m[(size_t)k];
+        if (m) std::memcpy(&w.cal_pairs[total * 4], w.corres[(size_t)w.cal[(size_t)k]][0].data(), m * 4 * sizeof(double));
+        total += m;
+    }
+    hip_.check(lmono_excalib_step(excalib_, n, w.cal_ids.data(), w.cal_m.data(), w.cal_pairs.data(), w.cal_q.data(), 10, nullptr, nullptr, w.cal_rlc.data(), nullptr, nullptr,
+                                  w.cal_ok.data()), "lmono_excalib_step");
+}
+
+// what a present stream does in the frame's first pass once it is known whether it still calibrates: its class, and the class's work up to the first
+// numeric call.  A fill stream's frame ends here
+char EstimatorBatch::beginStream(int s, const double transform_to_init[16], bool *keyframe)
+{
+    Work &w = *work_;
+    Estimator &e = *est_[(size_t)s];
+    char c;
+    if (e.stage_flag == Estimator::INITED) c = RUN;
+    else c = (e.frame_count == WINDOW_SIZE && e.p_.ESTIMATE_LASER != 2) ? INIT : FILL;
+    if (c == RUN) { e.loopCorrection(); e.packTracks(w.tp[(size_t)s]); }
+    else if (c == INIT) { e.initialPoses(); e.packTracks(w.tp[(size_t)s]); }                   // runInitialization :986-1012, then optimization
+    else {
+        if (e.frame_count == WINDOW_SIZE) e.slideWindow();              // (ESTIMATE_LASER == 2: NOT_INITED slides are list surgery only, removeBack)
+        if (e.frame_count < WINDOW_SIZE) {
+            e.frame_count++;
+            e.Ps[e.frame_count] = e.Ps[e.frame_count - 1]; e.Rs[e.frame_count] = e.Rs[e.frame_count - 1]; e.Header[e.frame_count] = e.Header[e.frame_count - 1];
+        }
+    }
+    std::memcpy(e.prev_laser_pose, transform_to_init, sizeof(e.prev_laser_pose));      // :651 (nothing reads it before the stream's next frame)
+    if (c == FILL) {
+        // (a frame without a solve ends here: the caller's keyframe flag first, then the hook)
+        if (keyframe) keyframe[s] = w.kf[(size_t)s] != 0;
+        if (frame_hook_) frame_hook_(s, e);
+    }
+    return c;
 }
 
 // Estimator::processImage (Estimator.cc:367-499) for every stream, the numeric steps batched
@@ -1096,71 +1203,102 @@ void EstimatorBatch::processImage(const double *headers, const FeatureManager::I
 // returns; Finish waits for the solve and runs the rest.  A caller that drives several EstimatorBatches (each on its own context / stream) from ONE thread
 // interleaves them -- finish(A), begin(A, next frame), finish(B), begin(B, next frame) ... -- so that one batch's host passes run under another's solve
 // (estimator_seq groups=G); processImage = Begin + Finish.
+// Per frame the batch is the streams that are given one (w.present).  Each is classified by its own state -- after the calibration step, which can move a
+// stream from fill to init in the very frame that fills its window (Estimator::processImage :687-697) -- and the passes and calls below run over the
+// lists of the classes.  With every stream present and in one class these are the passes and calls of the lock-step frame.
 void EstimatorBatch::processImageBegin(const double *headers, const FeatureManager::Image *const *images, const double (*transform_to_init)[16], bool *keyframe)
 {
-    if (pending_ != 0) throw std::logic_error("EstimatorBatch::processImageBegin: the previous frame was not finished");
-    const int N = size();
     Work &w = *work_;
-    if ((int)w.tp.size() != N) { w.tp.resize((size_t)N); w.sp.resize((size_t)N); w.shp.resize((size_t)N); w.due.assign((size_t)N, 0); }
-    std::vector<char> kf((size_t)N, 0);
-    g_bclock.start();
-    const Estimator &e0 = *est_[0];
-    for (int s = 1; s < N; s++)
-        if (est_[(size_t)s]->stage_flag != e0.stage_flag || est_[(size_t)s]->frame_count != e0.frame_count)
-            throw std::logic_error("EstimatorBatch: the streams are not at the same frame of their sequences");
-    auto pre = [&](int s) { bool k = false; est_[(size_t)s]->preFrame(headers[s], *images[s], transform_to_init[s], &k); kf[(size_t)s] = k ? 1 : 0; };
-    if (e0.stage_flag == Estimator::NOT_INITED) {
-        if (e0.frame_count == WINDOW_SIZE && p_.ESTIMATE_LASER != 2) {
-            // runInitialization :986-1012, then optimization
-            pool_->run(N, [&](int s) { pre(s); est_[(size_t)s]->initialPoses(); est_[(size_t)s]->packTracks(w.tp[(size_t)s]); });
-            callTriangulate();
-            pool_->run(N, [&](int s) { applyTriangulate(s); est_[(size_t)s]->packTracks(w.tp[(size_t)s]); });
-            callOutliers();
-            pool_->run(N, [&](int s) { applyOutliers(s, 100.0); est_[(size_t)s]->packSolve(w.sp[(size_t)s]); });
-            callSolve();
-            pending_ = 2;
-        } else {
-            pool_->run(N, [&](int s) {
-                pre(s);
-                Estimator &e = *est_[(size_t)s];
-                if (e.frame_count == WINDOW_SIZE) e.slideWindow();              // (ESTIMATE_LASER == 2: NOT_INITED slides are list surgery only, removeBack)
-                if (e.frame_count < WINDOW_SIZE) {
-                    e.frame_count++;
-                    e.Ps[e.frame_count] = e.Ps[e.frame_count - 1]; e.Rs[e.frame_count] = e.Rs[e.frame_count - 1]; e.Header[e.frame_count] = e.Header[e.frame_count - 1];
-                }
-                // (a frame without a solve ends here: the caller's keyframe flag first, then the hook)
-                if (keyframe) keyframe[s] = kf[(size_t)s] != 0;
-                if (frame_hook_) frame_hook_(s, e);
-            });
-        }
-    } else {
-        pool_->run(N, [&](int s) { pre(s); est_[(size_t)s]->loopCorrection(); est_[(size_t)s]->packTracks(w.tp[(size_t)s]); });
-        g_bclock.lap(0);
-        callTriangulate();
-        g_bclock.lap(2);
-        pool_->run(N, [&](int s) { applyTriangulate(s); est_[(size_t)s]->packSolve(w.sp[(size_t)s]); });
-        g_bclock.lap(3);
-        callSolve();
-        pending_ = 1;
+    if (w.launched) throw std::logic_error("EstimatorBatch::processImageBegin: the previous frame was not finished");
+    const int N = size();
+    if ((int)w.tp.size() != N) { w.tp.resize((size_t)N); w.sp.resize((size_t)N); w.shp.resize((size_t)N); w.due.assign((size_t)N, 0); w.kf.assign((size_t)N, 0); w.cls.assign((size_t)N, (char)ABSENT); }
+    w.present.clear(); w.cal.clear();
+    for (int s = 0; s < N; s++) {
+        if (!images[s]) { if (keyframe) keyframe[s] = false; continue; }
+        w.present.push_back(s);
+        if (est_[(size_t)s]->p_.ESTIMATE_LASER == 2 && est_[(size_t)s]->frame_count > 0) w.cal.push_back(s);       // (preFrame does not change frame_count)
     }
-    if (keyframe) for (int s = 0; s < N; s++) keyframe[s] = kf[(size_t)s] != 0;
+    if (w.present.empty()) return;
+    g_bclock.start();
+    const int NP = (int)w.present.size();
+    if (!w.cal.empty()) {
+        if ((int)w.corres.size() < N) w.corres.resize((size_t)N);
+        fit(w.cal_q, w.cal.size() * 4);
+    }
+    // first pass: preFrame; a stream that still calibrates forms its pairs and its LiDAR increment and waits for the step, every other stream goes on
+    pool_->run(NP, [&](int i) {
+        const int s = w.present[(size_t)i];
+        Estimator &e = *est_[(size_t)s];
+        bool k = false;
+        e.preFrame(headers[s], *images[s], transform_to_init[s], &k);
+        w.kf[(size_t)s] = k ? 1 : 0;
+        if (e.p_.ESTIMATE_LASER == 2 && e.frame_count > 0) {
+            const size_t c = (size_t)(std::lower_bound(w.cal.begin(), w.cal.end(), s) - w.cal.begin());
+            laser_increment(e.prev_laser_pose, transform_to_init[s], &w.cal_q[c * 4]);
+            w.corres[(size_t)s] = e.feature_manager.getCorresponding(e.frame_count - 1, e.frame_count);
+            return;
+        }
+        w.cls[(size_t)s] = beginStream(s, transform_to_init[s], keyframe);
+    });
+    if (!w.cal.empty()) {
+        callCalibrate();
+        pool_->run((int)w.cal.size(), [&](int c) {
+            const int s = w.cal[(size_t)c];
+            Estimator &e = *est_[(size_t)s];
+            if (w.cal_ok[(size_t)c]) {
+                const double *rlc = &w.cal_rlc[(size_t)c * 9];
+                for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) e.TLC[i * 4 + j] = rlc[i * 3 + j];
+                std::memcpy(e.calib_rlc, rlc, sizeof(e.calib_rlc));
+                e.extrinsic_calibrated = true;
+                e.p_.ESTIMATE_LASER = 1;
+            }
+            w.cls[(size_t)s] = beginStream(s, transform_to_init[s], keyframe);
+        });
+    }
+    w.init.clear(); w.run.clear(); w.solve.clear();
+    for (int s : w.present) {
+        const char c = w.cls[(size_t)s];
+        if (c == INIT) w.init.push_back(s); else if (c == RUN) w.run.push_back(s);
+        if (c == INIT || c == RUN) { w.solve.push_back(s); pending_[(size_t)s] = c; }
+    }
+    g_bclock.lap(0);
+    if (w.solve.empty()) { open_ = true; return; }
+    callTriangulate(w.solve);
+    g_bclock.lap(2);
+    pool_->run((int)w.solve.size(), [&](int k) {
+        const int s = w.solve[(size_t)k];
+        applyTriangulate(k, s);
+        if (pending_[(size_t)s] == INIT) est_[(size_t)s]->packTracks(w.tp[(size_t)s]); else est_[(size_t)s]->packSolve(w.sp[(size_t)s]);
+    });
+    if (!w.init.empty()) {
+        callOutliers(w.init);
+        pool_->run((int)w.init.size(), [&](int k) { const int s = w.init[(size_t)k]; applyOutliers(k, s, 100.0); est_[(size_t)s]->packSolve(w.sp[(size_t)s]); });
+    }
+    g_bclock.lap(3);
+    callSolve(w.solve);
+    w.launched = open_ = true;      // (set where Begin succeeds: a call that threw leaves no frame open)
+    if (keyframe) for (int s : w.solve) keyframe[s] = w.kf[(size_t)s] != 0;
 }
 void EstimatorBatch::processImageFinish()
 {
-    if (pending_ == 0) return;
-    const int N = size();
     Work &w = *work_;
-    const bool init_frame = pending_ == 2;
-    pending_ = 0;
+    open_ = false;
+    if (!w.launched) return;
+    w.launched = false;
+    const int N = size(), NS = (int)w.solve.size();
+    const bool init_frame = !w.init.empty();
     g_bclock.start();
     readSolve();
-    // Estimator::optimization behind the solve: double2Matrix, then margin() (frame_count == WINDOW_SIZE here) -- and the tracks for the outlier scores
+    // Estimator::optimization behind the solve: double2Matrix, then margin() (frame_count == WINDOW_SIZE here) for the streams whose own ESTIMATE_LASER is not 0
+    // (a stream's changes when it calibrates; the batch's copy does not) -- and the tracks for the outlier scores
     std::shared_ptr<std::vector<MargPack>> packs;
-    const bool do_margin = p_.ESTIMATE_LASER != 0;
+    bool do_margin = false;
+    for (int s : w.solve) if (est_[(size_t)s]->p_.ESTIMATE_LASER != 0) { do_margin = true; break; }
     if (do_margin) { marginWait(); packs = std::make_shared<std::vector<MargPack>>((size_t)N); }
-    pool_->run(N, [&](int s) {
-        applySolve(s);
-        if (do_margin) est_[(size_t)s]->packMargin((*packs)[(size_t)s]);
+    pool_->run(NS, [&](int k) {
+        const int s = w.solve[(size_t)k];
+        applySolve(k, s);
+        if (do_margin && est_[(size_t)s]->p_.ESTIMATE_LASER != 0) est_[(size_t)s]->packMargin((*packs)[(size_t)s]);
         est_[(size_t)s]->packTracks(w.tp[(size_t)s]);
     });
     g_bclock.lap(7);
@@ -1172,20 +1310,26 @@ void EstimatorBatch::processImageFinish()
     const bool early = force_early || N < 64;
     if (do_margin && (!async_margin_ || early)) { submitMargin(packs); packs.reset(); }
     g_bclock.lap(8);
-    if (init_frame) for (auto &e : est_) e->stage_flag = Estimator::INITED;
-    const double outlier_error = init_frame ? 3.0 : p_.OUTLIER_T;
-    callOutliers();
-    pool_->run(N, [&](int s) { applyOutliers(s, outlier_error); w.due[(size_t)s] = est_[(size_t)s]->slideWindowBegin(w.shp[(size_t)s]) ? 1 : 0; });
+    for (int s : w.init) est_[(size_t)s]->stage_flag = Estimator::INITED;
+    callOutliers(w.solve);
+    pool_->run(NS, [&](int k) {
+        const int s = w.solve[(size_t)k];
+        applyOutliers(k, s, pending_[(size_t)s] == INIT ? 3.0 : p_.OUTLIER_T);
+        w.due[(size_t)s] = est_[(size_t)s]->slideWindowBegin(w.shp[(size_t)s]) ? 1 : 0;
+    });
     g_bclock.lap(9);
-    callShift();
-    pool_->run(N, [&](int s) {
-        if (w.due[(size_t)s]) est_[(size_t)s]->slideWindowFinish(&w.shout[(size_t)w.shoff[(size_t)s]]);
+    callShift(w.solve);
+    pool_->run(NS, [&](int k) {
+        const int s = w.solve[(size_t)k];
+        if (w.due[(size_t)s]) est_[(size_t)s]->slideWindowFinish(&w.shout[(size_t)w.shoff[(size_t)k]]);
         est_[(size_t)s]->pushOdometryRow();
+        pending_[(size_t)s] = ABSENT;
         if (frame_hook_) frame_hook_(s, *est_[(size_t)s]);
     });
     g_bclock.lap(10);
     if (packs && async_margin_) submitMargin(packs);
     if (!init_frame) g_bclock.frames++;
+    w.solve.clear();
 }
 
 // ---- A-LOAM nodes ---------------------------------------------------------------------------------------------------

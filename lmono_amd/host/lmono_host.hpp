@@ -250,53 +250,79 @@ private:
 // solve, marginalisation, outlier scores, the depth shift of the slide -- is ONE C-ABI call over the N windows of the N streams (the entry points take
 // n_windows), the host halves around the calls run on a small thread pool.  Every stream's output is the bytes of its own single-stream run: the kernels
 // own one window per workgroup (or one track per thread) and form their sums in an order fixed by the window alone.
-// The streams must be at the same frame of their sequences (same frame_count / stage_flag): they are created together and fed one frame each per call.
-// ESTIMATE_LASER == 2 is not run here: streams finish calibrating on different frames and would leave the lock-step; such streams stay
-// NOT_INITED as before.  A single Estimator calibrates.
+// The streams need not be at the same frame of their sequences: per call the batch is the streams that are given a frame (images[s] != nullptr), and every
+// one of them is, by its OWN state, in one of three classes -- fill (NOT_INITED and the window not full, or still calibrating: host work only), init (the
+// frame that fills the window: runInitialization, then the solve) or run (INITED) -- so a stream may start late, miss frames, be added (addStream) or start
+// over (resetStream) while the others go on.  A numeric step is still ONE call per frame, over the windows of the streams that need it in ascending stream
+// order; a step that no stream needs makes no call.  A window's bytes do not depend on the batch it travels in, so every stream still prints its single run.
+// ESTIMATE_LASER == 2: the batch owns one lmono_excalib with a slot per stream (capacity); the streams that are still calibrating take ONE
+// lmono_excalib_step per frame, and a stream that succeeds goes on with its own ESTIMATE_LASER = 1, exactly as Estimator::calibrateExtrinsicRotation does
+// (a stream that calibrates on the frame that fills its window initialises in that frame).
 class HostPool;
 class EstimatorBatch {
 public:
-    EstimatorBatch(HipContext &hip, const Params &p, int n_streams, int host_threads = 0);     // host_threads 0: min(hardware threads, 16) (LMONO_HOST_THREADS)
+    // host_threads 0: min(hardware threads, 16) (LMONO_HOST_THREADS).  capacity: the most streams the batch will ever hold (addStream), 0 = n_streams; the
+    // thread pool (min(host_threads, capacity) threads) and the calibration handle are sized for it and do not grow
+    EstimatorBatch(HipContext &hip, const Params &p, int n_streams, int host_threads = 0, int capacity = 0);
     ~EstimatorBatch();
     EstimatorBatch(const EstimatorBatch &) = delete;
     EstimatorBatch &operator=(const EstimatorBatch &) = delete;
     int size() const { return (int)est_.size(); }
+    int capacity() const { return capacity_; }
     Estimator &stream(int s) { return *est_[(size_t)s]; }
     // one frame of every stream: headers[n], images[n], transform_to_init[n] (4 x 4 row-major LiDAR poses); keyframe[n] (optional) as processImage returns it
     void processImage(const double *headers, const FeatureManager::Image *images, const double (*transform_to_init)[16], bool *keyframe = nullptr);
-    void processImage(const double *headers, const FeatureManager::Image *const *images, const double (*transform_to_init)[16], bool *keyframe = nullptr);   // images by pointer
-    // the same frame in two halves around the (asynchronous) window solve: Begin returns with the solve in flight, Finish waits for it and runs the rest of the frame.
-    // One thread can interleave several batches (own contexts) that way: a batch's host passes under another batch's solve
+    // images by pointer.  images[s] == nullptr: stream s has no frame in this call -- nothing of it changes, it takes part in no numeric call, its hook is
+    // not called, keyframe[s] is false and headers[s] / transform_to_init[s] are not read.  A call in which no stream has a frame does nothing
+    void processImage(const double *headers, const FeatureManager::Image *const *images, const double (*transform_to_init)[16], bool *keyframe = nullptr);
+    // the same frame in two halves around the (asynchronous) window solve: Begin returns with the solve in flight, Finish waits for it and runs the rest of the frame
+    // (nothing, when no stream of the frame had a solve).  One thread can interleave several batches (own contexts) that way: a batch's host passes under
+    // another batch's solve
     void processImageBegin(const double *headers, const FeatureManager::Image *const *images, const double (*transform_to_init)[16], bool *keyframe = nullptr);
     void processImageFinish();
+    // Appends a fresh NOT_INITED Estimator and returns its index; std::length_error beyond the capacity.
+    int addStream();
+    // Stream s starts over: waits for a pending marginalisation (its worker writes the stream's last_marginalization_info), replaces the Estimator by a fresh
+    // one and clears the stream's calibration sums.  Returns the fresh Estimator (set its TLC as on a new stream).
+    // Both throw std::logic_error between processImageBegin and processImageFinish.
+    Estimator &resetStream(int s);
     void setAsyncMargin(bool on);          // marginalisation of frame k beside frame k + 1 (second context, own stream, one worker thread), as Estimator::setAsyncMargin
     void marginWait();
-    // called once per stream at the end of every frame, inside the frame's last per-stream pass (on a pool thread: it may touch stream s's own data only) --
-    // what a node does with a stream's result (publishing, logging) without a serial loop over the streams behind the frame
+    // called once per stream that had a frame, at the end of that frame, inside the frame's last per-stream pass (on a pool thread: it may touch stream s's own
+    // data only) -- what a node does with a stream's result (publishing, logging) without a serial loop over the streams behind the frame.
+    // With overlapped marginalisation (setAsyncMargin) the stream's last_marginalization_info is off limits in the hook: the worker may be writing it until
+    // marginWait() has returned, and marginWait() must not be called from the hook
     void setFrameHook(std::function<void(int stream, const Estimator &)> hook) { frame_hook_ = std::move(hook); }
 private:
     std::function<void(int, const Estimator &)> frame_hook_;
     struct Work;
-    void concatTracks();
-    void callTriangulate();
-    void applyTriangulate(int s);
-    void callOutliers();
-    void applyOutliers(int s, double error);
-    void callSolve();
+    enum StreamClass : char { ABSENT = 0, FILL = 1, INIT = 2, RUN = 3 };
+    // (ids: the streams of a call in ascending order -- window k of the call is stream ids[k])
+    void concatTracks(const std::vector<int> &ids);
+    void callTriangulate(const std::vector<int> &ids);
+    void applyTriangulate(int k, int s);
+    void callOutliers(const std::vector<int> &ids);
+    void applyOutliers(int k, int s, double error);
+    void callSolve(const std::vector<int> &ids);
     void readSolve();
-    void applySolve(int s);
+    void applySolve(int k, int s);
     void submitMargin(std::shared_ptr<std::vector<MargPack>> packs);
-    void callShift();
+    void callShift(const std::vector<int> &ids);
+    void callCalibrate();
+    char beginStream(int s, const double transform_to_init[16], bool *keyframe);
     HipContext &hip_;
     Params p_;
     std::vector<std::unique_ptr<Estimator>> est_;
+    int capacity_ = 0;
     lmono_ba_batch *ba_batch_ = nullptr;
+    lmono_excalib *excalib_ = nullptr;     // ESTIMATE_LASER == 2: one slot per stream (capacity), created by the first frame that calibrates
     std::shared_ptr<HostPool> pool_;       // shared by the EstimatorBatches of a process that ask for the same number of threads (groups driven by one thread)
     std::unique_ptr<Work> work_;
     std::unique_ptr<HipContext> margin_hip_;
     std::unique_ptr<MarginWorker> margin_worker_;
     bool async_margin_ = false;
-    int pending_ = 0;                      // a frame between Begin and Finish: 1 = an INITED frame, 2 = the initialisation frame
+    bool open_ = false;                    // between a Begin that was given a frame and its Finish
+    std::vector<char> pending_;            // per stream, between Begin and Finish: the class it solves as (INIT or RUN), else ABSENT
 };
 
 // ---- A-LOAM nodes ---------------------------------------------------------------------------------------------------

@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """Diagnostic: where a k_corr_flat workgroup spends its cycles.  Run on the GPU box through scripts/prof_flat.sh, which builds a
 -DLMONO_TILE_PROF library into gpurun_out/ and points LMONO_HIP_LIB at it (s_memtime ticks of thread 0 of every workgroup, 100 MHz)."""
+# Every stamp charges the ticks since the previous stamp to its own counter, so the counters partition the kernel's time between the
+# first and the last stamp: stage 2 is the sum of its sub-stamps plus the wait at the barrier behind it, and the total is the sum of all.
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 assert os.environ.get("LMONO_HIP_LIB"), "run through scripts/prof_flat.sh"
@@ -22,16 +24,19 @@ batch.odometry_d(chains, lead, incr.data_ptr(), None)
 groups, _, _ = ctx.timing()
 d = ctx.diag
 wgs = max(d[0], 1)
-names = ["1a requests", "1b resolve + prefix", "2 candidates", "3 decide + vote", "setup"]
-tot = sum(d[1:6])
+# d[1 + i] = stamp i: 0 1a, 1 1b, 2 barrier behind stage 2, 3 decide + vote, 4 set-up, 10 .. 14 the sub-stamps of stage 2
+fine = [("2: chunk search", d[11]), ("2: issuing the gathers", d[12]), ("2: descriptor walk + gathers in flight", d[13]),
+        ("2: arithmetic + flushes", d[14]), ("2: last flush", d[15]), ("2: wait at the barrier behind it", d[3])]
+stage2 = sum(v for _, v in fine)
+stages = [("1a requests", d[1]), ("1b resolve + prefix", d[2]), ("2 candidates", stage2), ("3 decide + vote", d[4]), ("setup", d[5])]
+tot = sum(v for _, v in stages)
 print("workgroups %d: NN rounds %.2f, walk rounds %.2f per workgroup; 4-point chunks per NN round %.0f, per walk round %.0f" %
       (wgs, d[7] / wgs, d[8] / wgs, d[9] / max(d[7], 1), d[10] / max(d[8], 1)))
-for i, nm in enumerate(names):
-    print("  %-22s %9.0f cycles / workgroup (%4.1f %%)" % (nm, d[1 + i] / wgs, 100 * d[1 + i] / tot))
+for nm, v in stages:
+    print("  %-22s %9.0f cycles / workgroup (%4.1f %%)" % (nm, v / wgs, 100 * v / tot))
 print("  total %.0f cycles / workgroup" % (tot / wgs))
-fine = ["2: chunk search", "2: addresses (LDS)", "2: gathers in flight", "2: arithmetic + flushes", "2: last flush"]
-for i, nm in enumerate(fine):
-    print("    %-24s %9.0f" % (nm, d[11 + i] / wgs))
+for nm, v in fine:
+    print("    %-40s %9.0f (%4.1f %%)" % (nm, v / wgs, 100 * v / tot))
 print("    gather batches per workgroup (thread 0) %.1f, owner switches %.1f" % (d[16] / wgs, d[17] / wgs))
 print("    rounds per workgroup as run (max nearest + max walk) %.2f; max over its features of (nearest + walk) %.2f; mean per feature %.2f" %
       ((d[7] + d[8]) / wgs, d[18] / wgs, d[19] / wgs / 128.0))

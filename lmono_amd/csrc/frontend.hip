@@ -1064,13 +1064,27 @@ __device__ __forceinline__ void voxel_ring(BatchView &b, int r, int s)
 #ifndef LMONO_COMPACT_T
 #define LMONO_COMPACT_T 256
 #endif
-constexpr int kCompT = LMONO_COMPACT_T;      // threads per scan of the stand-alone kernel; 256 / 512 / 1024 measured the same 2.0 ms per pass (profiles/r4: bound by its traffic)
+constexpr int kCompT = LMONO_COMPACT_T;      // threads per scan of the stand-alone kernel; 256 / 512 / 1024 measured the same 2.0 ms per pass (profiles/r4).
+// Not "bound by its traffic", as this line said until round 8: the fused kernel moved 12.7 GB per pass (5.7 fetched + 7.0 written) in 3.97 ms,
+// 3.2 TB/s, with ONE workgroup per CU; at two per CU, one read of the "last" clouds fewer and the start tables written in rows it moves 10.9 GB
+// in about 3.1 ms, 3.5 TB/s (profiles/r8/NOTES.md).  Residency and its own chain of phases bound it first, bytes second.
 static_assert(kCompT >= 256 && kCompT % 64 == 0, "the four prefixes take one wave each");
 
-// one scan's feature clouds compacted by kT threads (k_compact: kCompT; k_compact_index, odometry.hip: the line index's 1024); returns the sizes of the
-// two "last" clouds (less sharp, less flat) to every thread
-template <int kT>
-__device__ __forceinline__ void compact_scan(const BatchView &b, int s, int &n_ls_out, int &n_lf_out)
+// What compact_scan tells about the two "last" clouds (cld 0: less sharp, 1: less flat) while their points pass through its copy loops.  kOn = false:
+// nothing (k_compact).  k_compact_index (odometry.hip) counts the points per (line, azimuth bin) there instead of reading the cloud once more.
+//   reset(cld, n)   before the cloud's copy loop, by every thread; a barrier of compact_scan follows before the first point()
+//   point(ok, p)    every point the loop writes, called by WHOLE waves (ok = false: a lane without a point)
+//   finish(cld, n)  behind the loop, by every thread; holds barriers
+struct CompactNoFeed {
+    static constexpr bool kOn = false;
+    __device__ __forceinline__ void reset(int, int) {}
+    __device__ __forceinline__ void point(bool, const float4 &) {}
+    __device__ __forceinline__ void finish(int, int) {}
+};
+
+// one scan's feature clouds compacted by kT threads (k_compact: kCompT; k_compact_index, odometry.hip: the line index's 1024)
+template <int kT, class Feed>
+__device__ __forceinline__ void compact_scan(const BatchView &b, int s, Feed &feed)
 {
     const int tid = threadIdx.x;
     const int64_t off = b.off[s];
@@ -1124,9 +1138,13 @@ __device__ __forceinline__ void compact_scan(const BatchView &b, int s, int &n_l
     if (tid < 66) { s_first[0][tid] = INT_MAX; s_last[0][tid] = -1; s_first[1][tid] = INT_MAX; s_last[1][tid] = -1; }
     if (tid < 2) s_flag[tid] = 0;
     if (tid >= 128 && tid < 128 + kMaxRings + 1) s_rb[tid - 128] = b.ring_begin[s * 65 + tid - 128];
+    const int n_ls = pre_ls[NE], n_lf = pre_lf[kMaxRings];
+    feed.reset(0, n_ls);
     __syncthreads();
     // four selection slots per thread and turn: the counts come from the LDS prefixes, the index loads and then the point gathers are issued
     // together (behind per-slot guards the compiler waits for every load in turn: three dependent round trips per slot, 30 slots per thread)
+    // (NE * 20 is a multiple of 64: the lanes of a wave make the same trips)
+    static_assert(NE * 20 % 64 == 0, "feed.point() needs whole waves");
     for (int x0 = tid; x0 < NE * 20; x0 += 4 * kT) {
         int pos[4], idx[4];
 #pragma unroll
@@ -1141,15 +1159,17 @@ __device__ __forceinline__ void compact_scan(const BatchView &b, int s, int &n_l
         for (int q = 0; q < 4; q++) { const float4 *src = pos[q] >= 0 ? cl + idx[q] : b.cloud; p4[q] = *src; }      // (an unused slot reads the batch's first point)
 #pragma unroll
         for (int q = 0; q < 4; q++) {
-            if (pos[q] < 0) continue;
-            const int x = x0 + kT * q, e = x / 20, k = x % 20;
             const float4 p = p4[q];
-            ls[pos[q]] = p;
-            if (k < 2) sharp[pre_sh[e] + k] = p;
-            int v = (int)p.w;
-            v = v < 0 ? 0 : (v > 65 ? 65 : v);
-            atomicMin(&s_first[0][v], pos[q]);
-            atomicMax(&s_last[0][v], pos[q]);
+            if (pos[q] >= 0) {
+                const int x = x0 + kT * q, e = x / 20, k = x % 20;
+                ls[pos[q]] = p;
+                if (k < 2) sharp[pre_sh[e] + k] = p;
+                int v = (int)p.w;
+                v = v < 0 ? 0 : (v > 65 ? 65 : v);
+                atomicMin(&s_first[0][v], pos[q]);
+                atomicMax(&s_last[0][v], pos[q]);
+            }
+            feed.point(pos[q] >= 0, p);
         }
     }
     for (int x0 = tid; x0 < NE * 4; x0 += 2 * kT) {
@@ -1167,10 +1187,17 @@ __device__ __forceinline__ void compact_scan(const BatchView &b, int s, int &n_l
 #pragma unroll
         for (int q = 0; q < 2; q++) if (pos[q] >= 0) flat[pos[q]] = p2[q];
     }
+    // the feed's state serves one cloud after the other
+    if (Feed::kOn) {
+        feed.finish(0, n_ls);
+        __syncthreads();
+        feed.reset(1, n_lf);
+        __syncthreads();
+    }
     // less-flat cloud = the rings' voxel outputs back to back: every thread finds the ring of its output index by a binary
     // search over the ring prefix (all loads independent, four per thread in flight)
-    const int n_lf = pre_lf[kMaxRings];
-    for (int j0 = tid; j0 < n_lf; j0 += 4 * kT) {
+    for (int base = 0; base < n_lf; base += 4 * kT) {      // uniform trip count: feed.point() needs whole waves
+        const int j0 = base + tid;
         float4 v4[4];
 #pragma unroll
         for (int q = 0; q < 4; q++) {
@@ -1192,10 +1219,12 @@ __device__ __forceinline__ void compact_scan(const BatchView &b, int s, int &n_l
                 atomicMin(&s_first[1][v], j);
                 atomicMax(&s_last[1][v], j);
             }
+            feed.point(j < n_lf, v4[q]);
         }
     }
+    feed.finish(1, n_lf);
     if (tid == 0) {
-        b.feat_n[s * 4 + 0] = pre_sh[NE]; b.feat_n[s * 4 + 1] = pre_ls[NE];
+        b.feat_n[s * 4 + 0] = pre_sh[NE]; b.feat_n[s * 4 + 1] = n_ls;
         b.feat_n[s * 4 + 2] = pre_fl[NE]; b.feat_n[s * 4 + 3] = n_lf;
     }
     __syncthreads();
@@ -1207,7 +1236,7 @@ __device__ __forceinline__ void compact_scan(const BatchView &b, int s, int &n_l
     __syncthreads();
     if (tid == 0 || tid == 64) {
         const int cld = tid >> 6;
-        const int n = cld ? n_lf : pre_ls[NE];
+        const int n = cld ? n_lf : n_ls;
         int *first_ge = b.line_first_ge + (size_t)(s * 2 + cld) * 66, *last_le = b.line_last_le + (size_t)(s * 2 + cld) * 66;
         int m = n;
         for (int t = 65; t >= 0; t--) { m = min(m, s_first[cld][t] == INT_MAX ? n : s_first[cld][t]); first_ge[t] = m; }
@@ -1215,13 +1244,12 @@ __device__ __forceinline__ void compact_scan(const BatchView &b, int s, int &n_l
         for (int t = 0; t <= 65; t++) { M = max(M, s_last[cld][t]); last_le[t] = M; }
         if (s_flag[cld]) atomicOr(b.status + s, kStatusIrregularLines);
     }
-    n_ls_out = pre_ls[NE]; n_lf_out = n_lf;
 }
 
 __global__ __launch_bounds__(kCompT) void k_compact(BatchView b)
 {
-    int n_ls, n_lf;
-    compact_scan<kCompT>(b, b.scan0 + blockIdx.x, n_ls, n_lf);
+    CompactNoFeed feed;
+    compact_scan<kCompT>(b, b.scan0 + blockIdx.x, feed);
 }
 
 } // namespace lmono

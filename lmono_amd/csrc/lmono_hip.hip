@@ -243,6 +243,8 @@ extern "C" lmono_ctx *lmono_create(int device)
         int nb = 0;
         (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void *)k_corr_flat, kCfT, 0);
         std::fprintf(stderr, "[lmono diag] k_corr_flat: %d workgroups of %d threads per CU by the occupancy query, static LDS %zu B\n", nb, kCfT, sizeof(CfLds));
+        (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, (const void *)k_compact_index, kLiT, kLiLdsHalf);
+        std::fprintf(stderr, "[lmono diag] k_compact_index: %d workgroups of %d threads per CU by the occupancy query, dynamic LDS %d B\n", nb, kLiT, kLiLdsHalf);
     }
 #endif
     return c;

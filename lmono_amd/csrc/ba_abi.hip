@@ -174,9 +174,8 @@ static int ba_fill(lmono_ctx *c, lmono_ba_batch *b, const lmono_ba_desc *d)
         for (int f = f0; f < f1; f++) if (fo[f + 1] > fo[f]) anchor[f] = d->obs_i[fo[f]];
         if (d->flags[4 * w + 3]) {   // use_mono == 0: the projection factors are not part of the problem
             // counting sort of the window's observations by frame pair (ascending observation index inside a pair), pairs by (observer j, anchor i) ascending
-            // (round 6: the order in which a one-workgroup solve can add a pair's tile into H_pp as soon as it is formed -- see ba_linearise_lds; rounds 4-5
-            // sorted by descending size for the waves' work counter, which the 16-slot segments made pointless) -- no per-window allocations: a lock-step
-            // batch of Estimators fills hundreds of windows per frame
+            // (since round 6; the order of the sums, so part of the result's bits.  Rounds 4-5 sorted by descending size for the waves' work counter, which
+            // the 16-slot segments made pointless) -- no per-window allocations: a lock-step batch of Estimators fills hundreds of windows per frame
             constexpr int kKeys = kBaMaxPoses * kBaMaxPoses;
             int cnt[kKeys], base[kKeys], order[kKeys], local_of[kKeys], n_keys = 0;
             for (int key = 0; key < kKeys; key++) cnt[key] = 0;
@@ -261,8 +260,6 @@ static int ba_fill(lmono_ctx *c, lmono_ba_batch *b, const lmono_ba_desc *d)
     pk.add(v.pairdat, (const double *)nullptr, (size_t)b->cluster * pair_ij.size() * kBaPairRec);
     pk.add(v.mbox, (const double *)nullptr, (size_t)W * kBaMbox);
     pk.add(v.bar, (const unsigned int *)nullptr, (size_t)W * kBaBar);
-    pk.add(v.hred, (const double *)nullptr, b->cluster > 1 ? (size_t)W * kBaHred : (size_t)1);
-    pk.add(v.fdg, (const double *)nullptr, b->cluster > 1 ? (size_t)W * 2 * v.feat_cap : (size_t)1);
     v.n_pairs_total = (int)pair_ij.size();
     pk.add(v.pairH, (const double *)nullptr, (seg_tab.size() + pair_ij.size() + (size_t)W) * kBaPairTile);
     pk.add(v.gprog, (const int *)nullptr, (size_t)W * kBaGprog);
@@ -280,8 +277,6 @@ static int ba_fill(lmono_ctx *c, lmono_ba_batch *b, const lmono_ba_desc *d)
     v.laser_consts = laser; v.prior_T = prior; v.info = infod;
     v.feat_obs_off = fobs_d; v.slot_obs = oslot_d;
     v.seg_off = segoff_d; v.seg_tab = segtab_d; v.pair_seg = pseg_d; v.n_multi = nmulti_d;
-    v.lds_ok = 1;
-    for (int o = 0; o < TO && v.lds_ok; o++) if (d->obs_i[o] >= d->obs_j[o]) v.lds_ok = 0;
     v.blob_lo = b->blob; v.blob_hi = b->blob + pk.up + pk.zero;      // (the arrays of THIS fill: what lies behind them in a larger, re-used allocation is out of bounds too)
     return LMONO_OK;
 }
@@ -331,9 +326,7 @@ extern "C" int lmono_ba_solve(lmono_ctx *c, lmono_ba_batch *b, int max_iteration
             HIP_TRY(c, hipMemcpyAsync(b->pre, b->v.poses, (size_t)((const char *)(b->v.inv_depth + b->total_feat) - (const char *)b->v.poses), hipMemcpyDeviceToDevice, c->stream));
         static const int test_fail = [] { const char *e = getenv("LMONO_BA_TEST_FAIL"); return e ? atoi(e) : 0; }();   // test hook: the cluster gives up at its first poll
         if (test_fail) HIP_TRY(c, hipMemsetAsync(b->v.fail, 1, 1, c->stream));
-        // bit 0 LMONO_BA_SPREAD (test hook: a window's workgroups on different XCDs), bit 1 LMONO_BA_SHARE_SUMS (measurement switch: the cluster shares the
-        // leader's ordered sums -- byte-identical, measured slower, off)
-        static const int spread = [] { const char *e = getenv("LMONO_BA_SPREAD"); const char *h = getenv("LMONO_BA_SHARE_SUMS"); return ((e && atoi(e)) ? 1 : 0) | ((h && atoi(h)) ? 2 : 0); }();
+        static const int spread = [] { const char *e = getenv("LMONO_BA_SPREAD"); return (e && atoi(e)) ? 1 : 0; }();      // test hook: a window's workgroups on different XCDs
         const dim3 grid(((b->n_windows + 7) / 8) * 8 * b->cluster);
         if (b->big) hipLaunchKernelGGL((k_ba_solve<true, true>), grid, dim3(kBaT), 0, c->stream, b->v, b->cluster, spread);
         else hipLaunchKernelGGL((k_ba_solve<true, false>), grid, dim3(kBaT), 0, c->stream, b->v, b->cluster, spread);

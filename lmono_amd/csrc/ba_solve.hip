@@ -45,9 +45,9 @@ constexpr int kBaPairRec = 52;                   // Tres(9) tres(3) Cm(9) A(9) B
 constexpr int kBaPairTile = 320;                 // 16 x 16 tile + 16 x 4 side tile of a SEGMENT of a frame pair (column 3 of the side tile: the segment's scalar sums)
 constexpr int kBaSeg = 16;                       // observations of a segment: a frame pair's slots in runs of 16 (two lanes each: half a wave)
 constexpr int kBaMaxSeg = kBaMaxPairs + kBaLdsFeat * (kBaMaxPoses - 1) / kBaSeg;      // 110 + 280 (segments whose table lives in LDS; kBig reads the table from HBM)
-constexpr int kBaMbox = 96 + kBaMaxFeat;         // leader -> followers: [0] command, [1] re-use the records, [8..84] poses, [88..94] extrinsic, [96..] inverse depths
+constexpr int kBaMbox = 96 + kBaMaxFeat;         // leader -> followers: [0] command, [1] re-use the records, [2] the leader's XCD, [8..84] poses, [88..94] extrinsic, [96..] inverse depths
 constexpr int kBaMaxK = 8;                       // workgroups per window
-constexpr int kBaBar = 32;                       // flag words per window: [0] go, [r] follower r's "segments done", [8] the leader's, [8 + r] follower r's "sums done", [16 + r] its XCD + 1
+constexpr int kBaBar = 32;                       // flag words per window (one 128-B line): [0] the leader's go, [r] follower r's "segments done"; the rest unused
 // ba_reduce_pairs' gather program (built once per solve: which tile cells an entry of H_pp / g_p is the sum of does not change between iterations):
 // part A = the 36 entries of every lower frame-block pair (two sources, written twice: the tiles are symmetric), part B = per frame the 21 lower
 // entries of its diagonal block, its 36 entries against the extrinsic and its 6 gradient entries (22 sources: the pairs (f, k), then the pairs (k, f))
@@ -56,9 +56,6 @@ constexpr int kBaGbN = 704;                      // part B items (11 frames x 63
 constexpr int kBaGprog = 4 * kBaGaN + 24 * kBaGbN;
 constexpr int kBaObsRec = 24;                    // per-observation record: hdd, gd, hx[6], hi[6], hj[6], oj
 constexpr int kBaT = 512;                        // threads per workgroup (2 waves per SIMD)
-#ifndef LMONO_BA_HS_FUSED
-#define LMONO_BA_HS_FUSED 1                      // the H s product reads the coupling rows once (1) or once for the camera rows and once for the depth rows (0: rounds 1-5)
-#endif
 constexpr int kBaW = kBaT / 64;
 
 typedef double ba_d4 __attribute__((ext_vector_type(4)));
@@ -95,11 +92,9 @@ struct BaBatch {
     double *pairH;              // scratch [total segments + total pairs + W][kBaPairTile], per window [its segments | its pairs | one tile of zeros]: every segment's J^T [J r] tile
                                 // (16 x 16 + 16 x 4) and scalar sums; a pair of several segments has their sum (segment order) in its own tile (ba_reduce_pairs)
     double *cpart;              // scratch [total segments]: every segment's share of a candidate's cost
-    // several workgroups per window (k_ba_solve<true>): the leader's mail box [W][kBaMbox] (command, state to evaluate), flag words [W][16]
+    // several workgroups per window (k_ba_solve<true>): the leader's mail box [W][kBaMbox] (command, state to evaluate), flag words [W][kBaBar]
     // (go, done of every follower; zeroed before every launch), a failure flag; pairdat then holds one copy per workgroup of a window
     int *gprog;                 // scratch [W][kBaGprog]: every window's gather program (see kBaGaN)
-    double *hred;               // scratch [W][kBaHred]: H_pp | g_p of a linearisation whose ordered sums the cluster's workgroups share (ba_reduce_pairs)
-    double *fdg;                // scratch [W][2][feat_cap]: H_ff | g_f likewise (LDS-resident windows; a kBig window's live in bigv anyway)
     int feat_cap;               // stride of the per-window feature arrays hpd / cand / mbox: kBaLdsFeat, or kBaMaxFeat when a window of the batch is larger
     double *bigv;               // scratch [W][8][kBaMaxFeat] (kBig only): H_ff, g_f and the feature part of scale, D, gs, gn, va, vb
     double *mbox;
@@ -108,8 +103,6 @@ struct BaBatch {
     int n_pairs_total;          // stride of the per-rank copies of pairdat
     double *cand;               // scratch [W][kBaMaxFeat]
     double *summary;            // [W][6] initial_cost, final_cost, iterations, termination, successful, unsuccessful
-    int lds_ok;                 // every observation's anchor frame precedes its observer (i < j: what the Estimator produces): the one-workgroup solve may add a
-                                // pair's tiles into H_pp in pair order straight from LDS (ba_linearise_lds); 0: it goes through the scratch like a cluster
     const char *blob_lo, *blob_hi;  // the batch's one device allocation (every pointer above points into it): the bounds-checked build's limits
 };
 
@@ -150,7 +143,6 @@ struct BaLds {
     signed char fanchor[kBaLdsFeat];             // the frame a feature is anchored in (-1: no observation)
     int ok;
     int eval_no, failed;        // several workgroups per window: evaluations handed out so far; a workgroup did not arrive
-    int coloc;                  // the leader's: -1 unknown, 1 every workgroup of the cluster runs on the leader's XCD (then they share the ordered sums), 0 not
 #ifdef LMONO_BA_PROF
     unsigned long long prof[24];
 #endif
@@ -370,7 +362,7 @@ template <bool kBig> __device__ __forceinline__ double &ba_vref(double *lds, dou
 
 // Hand-offs between the workgroups of a window are FLAG WORDS with one writer each (device-coherent stores, polled with device-coherent loads; no
 // read-modify-write: an agent-scope atomic add is resolved beyond the XCD's L2 and costs a microsecond before anybody can see it): the leader's "go"
-// word holds the number of evaluations it has published, follower r's "done" word the number it has answered.  B.bar: [W][16] words, [0] = go,
+// word holds the number of evaluations it has published, follower r's "done" word the number it has answered.  B.bar: [W][kBaBar] words, [0] = go,
 // [r] = done of follower r (rank r >= 1).  Zeroed before every launch.
 __device__ __forceinline__ unsigned int ba_flag_load(const unsigned int *p) { return __hip_atomic_load(BA_P(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ void ba_flag_store(unsigned int *p, unsigned int v) { __hip_atomic_store(BA_P(p), v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
@@ -500,26 +492,13 @@ __device__ __forceinline__ void ba_prior_accumulate_wave(const BaCtx &c, BaLds &
 // by one thread, which adds the tiles that touch it in a fixed order -- a pair's segments in segment order, then the pairs (f, j) by ascending j and
 // the pairs (i, f) by ascending i for an entry of frame f's rows / columns; all segments by index for the extrinsic block -- so the sums are the same
 // bits in every run whatever the waves' timing was and whoever computed a segment.  Entries nothing touches become zero: the pass replaces clearing H_pp.
-// Round 6: WHO forms an entry does not change it either, so the entries CAN be dealt to the workgroups of a window's cluster (part of nparts: the gather
-// program's items in turn, the extrinsic block to the last part; VERDICT r5 #2a) instead of the leader forming all of them while the followers wait.
-// Out: where an entry goes -- the leader's LDS when one workgroup forms them all, the window's row of B.hred (72 x 72 + 72 doubles, L2) when the cluster
-// shares them; the leader then loads the row in one sweep.  Built, byte-identical (the K = 1 / 2 / 4 / 8 tests ran on it), and MEASURED SLOWER: single
-// window 3.44 -> 3.51 ms, Estimator loop 393 -> 372 frames/s.  The pass is a chain of three dependent L2 round trips (program words -> tile cells -> the
-// other segments of a pair) whatever the share is, so a smaller share does not end sooner, and sharing adds two flag hand-offs and the leader's read-back
-// of 5.3 k doubles per linearisation.  Kept behind LMONO_BA_SHARE_SUMS=1 (default off: the leader forms every entry).
-struct BaOutLds {
-    BaLds &L;
-    __device__ __forceinline__ void put(int dst, double v) const { if (dst >= kBaP * kBaP) L.gp[dst - kBaP * kBaP] = v; else L.Hpp[dst] = v; }
-};
-template <bool kSc> struct BaOutGlob {
-    double *h;
-    __device__ __forceinline__ void put(int dst, double v) const { st_sh<kSc>(h + dst, v); }
-};
-constexpr int kBaHred = kBaP * kBaP + kBaP;
-template <bool kCl, class Out>
-__device__ __forceinline__ void ba_reduce_pairs(const BaBatch &B, const BaCtx c, BaLds &L, const Out out, int part, int nparts)
+// The leader forms every entry (round 6 dealt the entries to the cluster's workgroups instead: byte-identical and slower, removed in round 9 -- DESIGN.md
+// section 6, profiles/r6).
+template <bool kCl>
+__device__ __forceinline__ void ba_reduce_pairs(const BaBatch &B, const BaCtx c, BaLds &L)
 {
     const int tid = threadIdx.x;
+    auto put = [&](int dst, double v) { if (dst >= kBaP * kBaP) L.gp[dst - kBaP * kBaP] = v; else L.Hpp[dst] = v; };      // destinations: H_pp, then g_p
     // the window's tiles: one per segment
     double *tiles = B.pairH + (size_t)(c.sg0 + c.pp0 + c.win) * kBaPairTile;
     // (A), (B): the entries of H_pp and g_p that are sums over frame pairs, by the window's gather program (ba_setup: the cells an entry is the sum of are
@@ -537,7 +516,7 @@ __device__ __forceinline__ void ba_reduce_pairs(const BaBatch &B, const BaCtx c,
         for (int sgi = 1; sgi < cnt; sgi++) first += ld_sh<kCl>(t0 + (size_t)sgi * kBaPairTile);
         return first;
     };
-    for (int a0 = part * kBaT * 4; a0 < kBaGaN; a0 += nparts * kBaT * 4) {
+    for (int a0 = 0; a0 < kBaGaN; a0 += kBaT * 4) {
         int o1[4], o2[4], d1[4], d2[4];
         double v1[4], v2[4];
 #pragma unroll
@@ -549,10 +528,10 @@ __device__ __forceinline__ void ba_reduce_pairs(const BaBatch &B, const BaCtx c,
 #pragma unroll
         for (int u = 0; u < 4; u++) { v1[u] = (o1[u] >> 20) ? ld_sh<kCl>(tiles + (o1[u] & 0xfffff)) : 0.0; v2[u] = (o2[u] >> 20) ? ld_sh<kCl>(tiles + (o2[u] & 0xfffff)) : 0.0; }
 #pragma unroll
-        for (int u = 0; u < 4; u++) if (d1[u] >= 0) { const double sum = pair_value(o1[u], v1[u]) + pair_value(o2[u], v2[u]); out.put(d1[u], sum); out.put(d2[u], sum); }
+        for (int u = 0; u < 4; u++) if (d1[u] >= 0) { const double sum = pair_value(o1[u], v1[u]) + pair_value(o2[u], v2[u]); put(d1[u], sum); put(d2[u], sum); }
     }
     const int *gb = gp + 4 * kBaGaN;
-    for (int t = part * kBaT + tid; t < kBaGbN; t += nparts * kBaT) {
+    for (int t = tid; t < kBaGbN; t += kBaT) {
         int off[22];
         double v[22];
 #pragma unroll
@@ -563,12 +542,12 @@ __device__ __forceinline__ void ba_reduce_pairs(const BaBatch &B, const BaCtx c,
         double acc = 0.0;
 #pragma unroll
         for (int k = 0; k < 22; k++) acc += pair_value(off[k], v[k]);
-        if (dst >= 0) { out.put(dst, acc); if (dst2 >= 0) out.put(dst2, acc); }
+        if (dst >= 0) { put(dst, acc); if (dst2 >= 0) put(dst2, acc); }
     }
     // (C) the extrinsic block and gradient get a share from EVERY segment: 33 values per segment (rows 12..15 of the tile and of the side tile, and
     //     the five scalar sums of the (4..5, 4..5) corner); 15 threads per value add the segments s = g (mod 15) in ascending order into L.D (dead during
-    //     a linearisation; every workgroup of a cluster has its own), one thread per value then adds the 15 in order.  The last part's.
-    if (x0 >= 0 && part == nparts - 1) {
+    //     a linearisation), one thread per value then adds the 15 in order.
+    if (x0 >= 0) {
         constexpr int kG = 15;
         if (tid < 33 * kG) {
             const int e = tid % 33, g = tid / 33;
@@ -592,17 +571,17 @@ __device__ __forceinline__ void ba_reduce_pairs(const BaBatch &B, const BaCtx c,
 #pragma unroll
             for (int g = 0; g < kG; g++) tot += L.D[g * 33 + tid];
             const int e = tid, x4 = x0 + 4, x5 = x0 + 5, G0 = kBaP * kBaP;
-            if (e < 16) out.put((x0 + e / 4) * kBaP + x0 + e % 4, tot);
+            if (e < 16) put((x0 + e / 4) * kBaP + x0 + e % 4, tot);
             else if (e < 28) {
                 const int om = (e - 16) / 3, cc = (e - 16) % 3;
-                if (cc < 2) { out.put((x0 + om) * kBaP + x4 + cc, tot); out.put((x4 + cc) * kBaP + x0 + om, tot); }
-                else out.put(G0 + x0 + om, tot);
+                if (cc < 2) { put((x0 + om) * kBaP + x4 + cc, tot); put((x4 + cc) * kBaP + x0 + om, tot); }
+                else put(G0 + x0 + om, tot);
             }
-            else if (e == 28) out.put(x4 * kBaP + x4, tot);
-            else if (e == 29) { out.put(x4 * kBaP + x5, tot); out.put(x5 * kBaP + x4, tot); }
-            else if (e == 30) out.put(x5 * kBaP + x5, tot);
-            else if (e == 31) out.put(G0 + x4, tot);
-            else out.put(G0 + x5, tot);
+            else if (e == 28) put(x4 * kBaP + x4, tot);
+            else if (e == 29) { put(x4 * kBaP + x5, tot); put(x5 * kBaP + x4, tot); }
+            else if (e == 30) put(x5 * kBaP + x5, tot);
+            else if (e == 31) put(G0 + x4, tot);
+            else put(G0 + x5, tot);
         }
     }
     __syncthreads();
@@ -689,7 +668,7 @@ __device__ __forceinline__ void ba_publish(const BaBatch &B, const BaCtx &c, BaL
     if (tid < 64 && L.eval_no > 0 && !L.failed) { if (!ba_wait_flags(flags + 1, c.K - 1, (unsigned int)L.eval_no, B.fail) && tid == 0) L.failed = 1; }
     __syncthreads();
     double *mb = B.mbox + (size_t)c.win * kBaMbox;
-    if (tid == 0) { st_sh<true>(mb, (double)cmd); st_sh<true>(mb + 1, reuse ? 1.0 : 0.0); st_sh<true>(mb + 2, (double)ba_xcc_id()); st_sh<true>(mb + 3, (cmd == 1 && L.coloc == 1) ? 1.0 : 0.0); }
+    if (tid == 0) { st_sh<true>(mb, (double)cmd); st_sh<true>(mb + 1, reuse ? 1.0 : 0.0); st_sh<true>(mb + 2, (double)ba_xcc_id()); }
     if (!reuse && cmd != 3) {
         for (int k = tid; k < 7 * c.n_poses; k += kBaT) st_sh<true>(mb + 8 + k, poses[k]);
         if (tid < 7) st_sh<true>(mb + 88 + tid, ex[tid]);
@@ -714,17 +693,13 @@ __device__ __forceinline__ void ba_done(const BaBatch &B, const BaCtx &c, BaLds 
 
 // one workgroup's share of an evaluation: the segments gw, gw + GW, ... of the window (a linearisation takes two per round and wave, a cost evaluation
 // four).  Every result goes to the segment's / the observation's own record.
-// kLds (one workgroup per window, linearisation): ONE round -- the segments 16 round + wave and 16 round + 8 + wave -- and the two tiles stay in the wave's own
-// slice of the LDS stage (ba_linearise_lds adds them into H_pp from there) instead of going to the L2 scratch
-template <bool kJac, bool kCl, bool kBig, bool kFol = false, bool kLds = false>      // kFol: a follower workgroup (its inverse depths are the leader's mail box)
-__device__ __forceinline__ void ba_segments(const BaBatch &B, const BaCtx &c, BaLds &L, const BaBig &G, const double *ex, const double *pairdat, int round = 0,
-                                            const double *minfo = nullptr)
+template <bool kJac, bool kCl, bool kBig, bool kFol = false>      // kFol: a follower workgroup (its inverse depths are the leader's mail box)
+__device__ __forceinline__ void ba_segments(const BaBatch &B, const BaCtx &c, BaLds &L, const BaBig &G, const double *ex, const double *pairdat)
 {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const double *Rlc = L.Rp + 9 * c.n_poses;
     const double *mono_info = B.info + 36;
-    // (sqrt_info of the projection factor: from the caller's registers when it calls once per round -- four L2 round trips per call otherwise)
-    const double m00 = minfo ? minfo[0] : gld(mono_info), m01 = minfo ? minfo[1] : gld(mono_info + 1), m10 = minfo ? minfo[2] : gld(mono_info + 2), m11 = minfo ? minfo[3] : gld(mono_info + 3);
+    const double m00 = gld(mono_info), m01 = gld(mono_info + 1), m10 = gld(mono_info + 2), m11 = gld(mono_info + 3);
     const int *sinfo = B.slot_info + c.ps0;
     const double *spts = B.slot_pts + (size_t)c.ps0 * 4;
     const int gw = ba_worker(c, wave), GW = c.GW;        // this wave among the waves that share the window's segments
@@ -771,8 +746,7 @@ __device__ __forceinline__ void ba_segments(const BaBatch &B, const BaCtx &c, Ba
     double *tiles = B.pairH + (size_t)(c.sg0 + c.pp0 + c.win) * kBaPairTile;
     const int q = lane & 1, half = lane >> 5, lo = (lane & 31) >> 1, col = lane & 15, kq = lane >> 4;
     const double *Mx = L.Mq + 18 * c.n_poses, *Mxi = L.Mq + 18 * (kBaMaxPoses + 1);
-    const int s_lo = kLds ? 2 * kBaW * round + gw : gw, s_hi = kLds ? min(c.n_seg, 2 * kBaW * round + kBaW) : c.n_seg;
-    for (int sA = s_lo; sA < s_hi; sA += 2 * GW) {
+    for (int sA = gw; sA < c.n_seg; sA += 2 * GW) {
         const int sB = sA + GW;
         const int sg = half ? sB : sA;                       // this lane's segment
         const bool seg_ok = sg < c.n_seg;
@@ -881,7 +855,6 @@ __device__ __forceinline__ void ba_segments(const BaBatch &B, const BaCtx &c, Ba
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
         const int nA = __builtin_amdgcn_readlane(s_end - s_begin, 0), nB = sB < c.n_seg ? __builtin_amdgcn_readlane(s_end - s_begin, 32) : 0;
-        ba_d4 keep_a[2], keep_b[2];              // kLds: both tiles wait in registers until both products have read the staged rows (the tiles take the rows' place)
 #pragma unroll
         for (int h = 0; h < 2; h++) {
             const int n = h ? nB : nA;
@@ -894,7 +867,6 @@ __device__ __forceinline__ void ba_segments(const BaBatch &B, const BaCtx &c, Ba
                     aa = __builtin_amdgcn_mfma_f64_16x16x4f64(a, a, aa, 0, 0, 0);
                     ab = __builtin_amdgcn_mfma_f64_16x16x4f64(a, bq, ab, 0, 0, 0);
                 }
-                if (kLds) { keep_a[h] = aa; keep_b[h] = ab; continue; }
                 // the segment's tile [J_i J_j J_x0..3]^T [J_i J_j J_x0..3 | J_x4 J_x5 r] and its scalar sums go to the segment's own record in the
                 // L2 scratch (plain stores, nobody else touches it); ba_reduce_pairs adds the records in a fixed order afterwards
                 double *tile = tiles + (size_t)(h ? sB : sA) * kBaPairTile;
@@ -909,41 +881,20 @@ __device__ __forceinline__ void ba_segments(const BaBatch &B, const BaCtx &c, Ba
                 }
             }
         }
-        if (kLds) {
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();                     // every lane's products have read their rows
-#pragma unroll
-            for (int h = 0; h < 2; h++) {
-                const int n = h ? nB : nA;
-                if (n > 0) {
-                    double *tile = wstage + h * kBaPairTile;
-#pragma unroll
-                    for (int v = 0; v < 4; v++) {
-                        tile[(kq + 4 * v) * 16 + col] = keep_a[h][v];
-                        if (col < 3) tile[256 + (kq + 4 * v) * 4 + col] = keep_b[h][v];
-                    }
-                    if (lane == 32 * h) {
-                        tile[256 + 3] = cst; tile[260 + 3] = xx44; tile[264 + 3] = xx45; tile[268 + 3] = xx55; tile[272 + 3] = gx4; tile[276 + 3] = gx5;
-                    }
-                }
-            }
-        }
         __builtin_amdgcn_wave_barrier();   // the slice is rewritten by the next round
     }
 }
 
-// H_ff, g_f and the coupling rows from the observations' records, the features / observations f = part (mod nparts) of them: 16 lanes per feature, lane k
+// H_ff, g_f and the coupling rows from the observations' records: 16 lanes per feature, lane k
 // sums entry k of the feature's observation records (contiguous, at most 10: one per other frame of the window) in observation order; the loads are
-// independent and requested together.  kGlob: H_ff / g_f of an LDS-resident window go to the window's row of B.fdg (the cluster shares the pass; the leader
-// loads them), else to the leader's LDS (kBig: the L2 scratch either way).
-template <bool kCl, bool kBig, bool kGlob>
-__device__ __forceinline__ void ba_feature_pass(const BaBatch &B, const BaCtx &c, BaLds &L, const BaBig &G, double *hpd, int part, int nparts)
+// independent and requested together.  H_ff / g_f go to the leader's LDS (kBig: the L2 scratch).
+template <bool kCl, bool kBig>
+__device__ __forceinline__ void ba_feature_pass(const BaBatch &B, const BaCtx &c, BaLds &L, const BaBig &G, double *hpd)
 {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    double *fd = B.fdg + (size_t)c.win * 2 * B.feat_cap;
     {
         const int k = lane & 15, t8 = wave * 4 + (lane >> 4);
-        for (int f = part * 4 * kBaW + t8; f < c.F; f += nparts * 4 * kBaW) {
+        for (int f = t8; f < c.F; f += 4 * kBaW) {
             const int o0 = c.o0 + BA_FOBS(f), o1 = c.o0 + BA_FOBS(f + 1);
             double acc = 0.0;
             for (int ob = o0; ob < o1; ob += 10) {
@@ -953,8 +904,8 @@ __device__ __forceinline__ void ba_feature_pass(const BaBatch &B, const BaCtx &c
 #pragma unroll
                 for (int u = 0; u < 10; u++) acc += v[u];
             }
-            if (k == 0) { if (kGlob && !kBig) st_sh<true>(fd + f, acc); else BA_F(Hdd, f) = acc; }
-            else if (k == 1) { if (kGlob && !kBig) st_sh<true>(fd + B.feat_cap + f, acc); else BA_F(gdd, f) = acc; }
+            if (k == 0) BA_F(Hdd, f) = acc;
+            else if (k == 1) BA_F(gdd, f) = acc;
             else if (k < 14) {
                 double *hrow = hpd + (size_t)f * kBaPS;
                 if (k < 8) { if (c.ex_off >= 0) gst(hrow + c.ex_off + k - 2, acc); }
@@ -965,7 +916,7 @@ __device__ __forceinline__ void ba_feature_pass(const BaBatch &B, const BaCtx &c
         // observations of a lane in flight
         const int n_obs = c.use_mono ? BA_FOBS(c.F) : 0;
         const int kk = tid & 7;
-        for (int ob0 = part * 4 * (kBaT / 8) + (tid >> 3); ob0 < n_obs; ob0 += nparts * 4 * (kBaT / 8)) {
+        for (int ob0 = tid >> 3; ob0 < n_obs; ob0 += 4 * (kBaT / 8)) {
             double vj[4], vo[4], vf[4];
 #pragma unroll
             for (int u = 0; u < 4; u++) {
@@ -981,183 +932,6 @@ __device__ __forceinline__ void ba_feature_pass(const BaBatch &B, const BaCtx &c
             }
         }
     }
-}
-
-// Linearisation of a window that has ONE workgroup (round 6; VERDICT r5 #1a: the batched solve moved 27 x its algorithmic bytes through HBM, a third of it
-// the segments' tiles -- written to the L2 scratch by ba_segments and gathered back by ba_reduce_pairs).  Alone in its workgroup a window needs neither trip:
-// the eight waves evaluate the segments in ROUNDS of sixteen (wave w: segments 16 r + w and 16 r + 8 + w, as before), leave the sixteen tiles in their slices of
-// the LDS stage, and every entry of H_pp / g_p -- owned by one thread, as in the gather -- adds the round's tiles that touch it, straight from LDS, carrying its
-// running sums in registers.  THE SAME SUMS IN THE SAME ORDER as ba_reduce_pairs forms from the scratch, so the bytes equal the cluster's:
-//   * an entry of frame f adds the window's pairs that touch f in ascending pair order (the gather program's source order: ba_setup), a pair's value being
-//     the sum of its segments in segment order, started from zero -- the pairs are sorted by (observer, anchor), segments follow pairs, so a round delivers
-//     an entry's sources in exactly that order and a cursor over the frame's pair list (flist, built once per solve) replaces the gather program;
-//   * an entry between two frames adds the two pairs that can hold it (either order: a sum of two);
-//   * the extrinsic block's 33 values: 15 partial sums over the segments s = g (mod 15), then the 15 in order;
-//   * the cost: lane t of wave 0 adds the segments s = t (mod 64) in ascending order, then the wave's butterfly.
-// The per-observation records (depth blocks, coupling rows) still go through the scratch: their sums follow the observation order, not the pair order.
-// MEASURED (scripts/r6_ba_ab.sh, one box, A / B): byte-identical to the scratch path (the K = 1 vs K = 2 / 4 / 8 tests ran on it) and SLOWER -- 1024 windows
-// 33.0 k instead of 41.5 k windows/s, one window with one workgroup 5.7 instead of 4.2 ms.  A round ends in a workgroup barrier, so every round pays the
-// full latency of its segments' loads (pair record, slot tables, points, inverse depths: ~3 us) with nothing to overlap it; the scratch path lets each wave
-// run through its segments on its own, eight waves' latencies overlapping, and pays the L2 once in the gather.  The tiles' trip through the scratch is
-// traffic (a third of the solve's), not time.  Default OFF; kept as a compile-time variant (-DLMONO_BA_LDS_TILES=1, tests/test_bounds_gpu.py builds and
-// checks it) because it is the form a solve with a second stage buffer (rounds overlapped two deep) would start from.
-#ifndef LMONO_BA_LDS_TILES
-#define LMONO_BA_LDS_TILES 0
-#endif
-template <bool kBig>
-__device__ __forceinline__ void ba_linearise_lds(const BaBatch &B, const BaCtx &c, BaLds &L, const BaBig &G, const double *ex, const double *pairdat)
-{
-    const int tid = threadIdx.x, np_ = c.n_poses, x0 = c.ex_off;
-    constexpr int kWS = 2 * kBaRound * kBaRow;                   // doubles of a wave's stage slice
-    auto tile_of = [&](int q) { return L.u.stage + (size_t)(q % kBaW) * kWS + (q / kBaW) * kBaPairTile; };      // segment q of the round
-    auto pos = [](int r, int q) { return q < 16 ? (r < 16 ? r * 16 + q : 256 + q * 4 + (r - 16)) : 256 + r * 4 + (q - 16); };
-    // ---- this thread's entries
-    // part A: items a = tid + 512 u of the 55 x 36 frame-block entries (as the gather program numbers them)
-    int a_p1[4], a_p2[4], a_o1[4], a_o2[4], a_d1[4], a_d2[4], a_s1[4][2], a_s2[4][2];      // a_s*: the pair's segments [first, end) (none: an empty range)
-    double a_v1[4], a_v2[4];
-#pragma unroll
-    for (int u = 0; u < 4; u++) {
-        const int a = tid + u * kBaT;
-        a_p1[u] = a_p2[u] = -1; a_o1[u] = a_o2[u] = 0; a_d1[u] = a_d2[u] = -1; a_v1[u] = a_v2[u] = 0.0;
-        a_s1[u][0] = a_s1[u][1] = a_s2[u][0] = a_s2[u][1] = 0;
-        if (a < 55 * 36) {
-            const int pb = a / 36, e = a % 36, om = e / 6, on = e % 6;
-            int bm = 1;
-            while (bm * (bm + 1) / 2 <= pb) bm++;
-            const int bn = pb - bm * (bm - 1) / 2;
-            if (bm < np_ && bm < kBaMaxPoses) {
-                a_p1[u] = L.pair_of[bn * kBaMaxPoses + bm]; a_p2[u] = L.pair_of[bm * kBaMaxPoses + bn];
-                a_o1[u] = pos(6 + om, on); a_o2[u] = pos(om, 6 + on);
-                a_d1[u] = (ba_pose_off(c, bm) + om) * kBaP + ba_pose_off(c, bn) + on;
-                a_d2[u] = (ba_pose_off(c, bn) + on) * kBaP + ba_pose_off(c, bm) + om;
-                if (a_p1[u] >= 0) { a_s1[u][0] = L.pair_seg[a_p1[u]]; a_s1[u][1] = L.pair_seg[a_p1[u] + 1]; }
-                if (a_p2[u] >= 0) { a_s2[u][0] = L.pair_seg[a_p2[u]]; a_s2[u][1] = L.pair_seg[a_p2[u] + 1]; }
-            }
-        }
-    }
-    // part B: items t = tid, tid + 512 of the 11 x 63 entries of one frame (diagonal block, frame x extrinsic, gradient)
-    int b_f[2], b_oi[2], b_oj[2], b_dst[2], b_dst2[2], b_cur[2];
-    double b_acc[2], b_pacc[2];
-#pragma unroll
-    for (int u = 0; u < 2; u++) {
-        const int t = tid + u * kBaT;
-        b_f[u] = -1; b_oi[u] = b_oj[u] = 0; b_dst[u] = b_dst2[u] = -1; b_cur[u] = 0; b_acc[u] = 0.0; b_pacc[u] = 0.0;
-        if (t < kBaMaxPoses * 63) {
-            const int f = t / 63, r = t % 63;
-            bool on_ = f < np_;
-            int oi_, oj_, dst, dst2 = -1;
-            if (r < 21) {
-                int om = 0;
-                while ((om + 1) * (om + 2) / 2 <= r) om++;
-                const int on = r - om * (om + 1) / 2;
-                oi_ = pos(om, on); oj_ = pos(6 + om, 6 + on);
-                dst = (ba_pose_off(c, f) + om) * kBaP + ba_pose_off(c, f) + on; dst2 = om != on ? (ba_pose_off(c, f) + on) * kBaP + ba_pose_off(c, f) + om : -1;
-            } else if (r < 57) {
-                const int q = r - 21, om = q / 6, ox = q % 6;
-                oi_ = pos(om, 12 + ox); oj_ = pos(6 + om, 12 + ox);
-                dst = (ba_pose_off(c, f) + om) * kBaP + x0 + ox; dst2 = (x0 + ox) * kBaP + ba_pose_off(c, f) + om;
-                if (x0 < 0) on_ = false;
-            } else {
-                const int om = r - 57;
-                oi_ = pos(om, 18); oj_ = pos(6 + om, 18);
-                dst = kBaP * kBaP + ba_pose_off(c, f) + om;
-            }
-            if (on_) { b_f[u] = f; b_oi[u] = oi_; b_oj[u] = oj_; b_dst[u] = dst; b_dst2[u] = dst2; }
-        }
-    }
-    // part C: value e of the extrinsic block, partial sum g
-    constexpr int kG = 15;
-    const int c_e = tid % 33, c_g = tid / 33;
-    int c_off = 0;
-    if (c_e < 16) c_off = (12 + c_e / 4) * 16 + 12 + c_e % 4;
-    else if (c_e < 28) c_off = 256 + (12 + (c_e - 16) / 3) * 4 + (c_e - 16) % 3;
-    else c_off = 256 + (c_e - 27) * 4 + 3;
-    double c_acc = 0.0, cost_acc = 0.0;
-    int c_rb15 = 0;                                              // (first segment of the round) mod 15
-    // ---- every frame's pairs in pair order: flist[f] = pair | (1 << 7 when f is the pair's observer), in L.gs (dead during a linearisation)
-    int *flist = (int *)L.gs;                                    // [kBaMaxPoses][24]: [0] count, [1 ..] entries
-    static_assert(sizeof(double) * kBaN >= sizeof(int) * kBaMaxPoses * 24, "flist fits gs");
-    __syncthreads();
-    if (tid < kBaMaxPoses) {
-        int n = 0;
-        for (int p = 0; p < c.n_pairs; p++) {
-            const int ij = L.pair_ij[p], i = ij & 255, j = ij >> 8;
-            if (i == tid) flist[tid * 24 + 1 + n++] = p;
-            else if (j == tid) flist[tid * 24 + 1 + n++] = p | 128;
-        }
-        flist[tid * 24] = n;
-    }
-    __syncthreads();
-    const int n_rounds = (c.n_seg + 2 * kBaW - 1) / (2 * kBaW);
-    const double minfo[4] = { gld(B.info + 36), gld(B.info + 37), gld(B.info + 38), gld(B.info + 39) };
-    for (int round = 0; round < n_rounds; round++) {
-        ba_segments<true, false, kBig, false, true>(B, c, L, G, ex, pairdat, round, minfo);
-        __syncthreads();
-        const int rb = 2 * kBaW * round, re = min(rb + 2 * kBaW, c.n_seg);      // the round's segments [rb, re)
-        // the value a pair adds to an entry: its segments' cells in order, from zero
-        auto take = [&](int p, int at, double &pacc) -> bool {              // adds the pair's segments of this round; true = the pair is complete
-            const int s0 = L.pair_seg[p], s1 = L.pair_seg[p + 1];
-            for (int sg = max(s0, rb); sg < min(s1, re); sg++) { const double v = tile_of(sg - rb)[at]; pacc = sg == s0 ? v : pacc + v; }
-            return s1 <= re;
-        };
-#pragma unroll
-        for (int u = 0; u < 4; u++) {
-            for (int sg = max(a_s1[u][0], rb); sg < min(a_s1[u][1], re); sg++) { const double v = tile_of(sg - rb)[a_o1[u]]; a_v1[u] = sg == a_s1[u][0] ? v : a_v1[u] + v; }
-            for (int sg = max(a_s2[u][0], rb); sg < min(a_s2[u][1], re); sg++) { const double v = tile_of(sg - rb)[a_o2[u]]; a_v2[u] = sg == a_s2[u][0] ? v : a_v2[u] + v; }
-        }
-#pragma unroll
-        for (int u = 0; u < 2; u++) {
-            if (b_f[u] < 0) continue;
-            const int *fl = flist + b_f[u] * 24;
-            const int n = fl[0];
-            while (b_cur[u] < n) {
-                const int e = fl[1 + b_cur[u]], p = e & 127;
-                if (L.pair_seg[p] >= re) break;                             // the next source comes in a later round
-                if (take(p, (e & 128) ? b_oj[u] : b_oi[u], b_pacc[u])) { b_acc[u] += b_pacc[u]; b_cur[u]++; }
-                else break;                                                 // the pair goes on in the next round
-            }
-        }
-        if (x0 >= 0 && tid < 33 * kG) {
-            // the round's segments s = g (mod 15): at most two of sixteen
-            int sg = rb + (c_g - c_rb15 + kG) % kG;
-            if (sg < re) { c_acc += tile_of(sg - rb)[c_off]; sg += kG; if (sg < re) c_acc += tile_of(sg - rb)[c_off]; }
-        }
-        c_rb15 = (c_rb15 + 2 * kBaW) % kG;
-        if (tid < 64) { const int sg = rb + ((tid - rb) & 63); if (sg < re) cost_acc += tile_of(sg - rb)[256 + 3]; }
-        __syncthreads();                                                    // the stage is rewritten by the next round
-    }
-    // ---- the sums go to their places (entries nothing touches: zero)
-#pragma unroll
-    for (int u = 0; u < 4; u++) if (a_d1[u] >= 0) { const double sum = a_v1[u] + a_v2[u]; L.Hpp[a_d1[u]] = sum; L.Hpp[a_d2[u]] = sum; }
-#pragma unroll
-    for (int u = 0; u < 2; u++)
-        if (b_dst[u] >= 0) {
-            if (b_dst[u] >= kBaP * kBaP) L.gp[b_dst[u] - kBaP * kBaP] = b_acc[u];
-            else { L.Hpp[b_dst[u]] = b_acc[u]; if (b_dst2[u] >= 0) L.Hpp[b_dst2[u]] = b_acc[u]; }
-        }
-    if (x0 >= 0) {
-        if (tid < 33 * kG) L.D[c_g * 33 + c_e] = c_acc;
-        __syncthreads();
-        if (tid < 33) {
-            double tot = 0.0;
-#pragma unroll
-            for (int g = 0; g < kG; g++) tot += L.D[g * 33 + tid];
-            const int e = tid, x4 = x0 + 4, x5 = x0 + 5;
-            if (e < 16) L.Hpp[(x0 + e / 4) * kBaP + x0 + e % 4] = tot;
-            else if (e < 28) {
-                const int om = (e - 16) / 3, cc = (e - 16) % 3;
-                if (cc < 2) { L.Hpp[(x0 + om) * kBaP + x4 + cc] = tot; L.Hpp[(x4 + cc) * kBaP + x0 + om] = tot; }
-                else L.gp[x0 + om] = tot;
-            }
-            else if (e == 28) L.Hpp[x4 * kBaP + x4] = tot;
-            else if (e == 29) { L.Hpp[x4 * kBaP + x5] = tot; L.Hpp[x5 * kBaP + x4] = tot; }
-            else if (e == 30) L.Hpp[x5 * kBaP + x5] = tot;
-            else if (e == 31) L.gp[x4] = tot;
-            else L.gp[x5] = tot;
-        }
-    }
-    if (tid < 64) { cost_acc = wave_sum_d(cost_acc); if (tid == 0) L.red[3 * kBaW - 1] = cost_acc; }
-    __syncthreads();
 }
 
 // cost (returned to every thread) and, when kJac, the unscaled normal equations: Hpp, gp, Hdd, gdd in LDS, Hpd in HBM -- the LEADER's view of an
@@ -1213,66 +987,21 @@ __device__ __noinline__ double ba_evaluate(const BaBatch &B, const BaCtx c, BaLd
     BA_TOCK(0)
     BA_TICK(1)
     if (kJac && tid >= 64 && tid < 96) small_cost = ba_small_factors<kJac>(B, c, L.gn, poses, ex, tid - 64);
-    // one workgroup per window: the tiles never leave the CU (ba_linearise_lds); a cluster's leader: its share of the segments, records in the L2 scratch
-    const bool lds_path = LMONO_BA_LDS_TILES && !kCl && B.lds_ok;
-    if (lds_path) ba_linearise_lds<kBig>(B, c, L, G, ex, pairdat);
-    else ba_segments<true, false, kBig>(B, c, L, G, ex, pairdat);          // (the leader's own records: plain stores; it reads them back from the L2 like everybody's)
+    // this workgroup's share of the segments (all of them when it is alone), records in the L2 scratch
+    ba_segments<true, false, kBig>(B, c, L, G, ex, pairdat);               // (the leader's own records: plain stores; it reads them back from the L2 like everybody's)
     BA_TOCK(1)
     BA_TICK(11)
-    // the cluster shares the ordered sums of this linearisation when all its workgroups sit on the leader's XCD (known from the second linearisation on)
-    const bool shared = kCl && L.coloc == 1;
-    if (kCl) {
-        if (shared) {
-            // the leader's own records are out: its "segments done" word lets the followers start on their shares of the sums
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __syncthreads();
-            if (tid == 0) ba_flag_store(B.bar + (size_t)c.win * kBaBar + 8, (unsigned int)(L.eval_no + 1));
-        }
-        ba_done<true>(B, c, L);                                  // every workgroup's segment and observation records are written
-        if (L.coloc < 0) {
-            // where the followers run: each left its XCD + 1 in its word before it answered the first linearisation
-            __syncthreads();
-            if (tid == 0) {
-                const unsigned int *fl = B.bar + (size_t)c.win * kBaBar;
-                const unsigned int mine = (unsigned int)ba_xcc_id() + 1u;
-                int same = 1;
-                for (int r = 1; r < c.K; r++) if (ba_flag_load(fl + 16 + r) != mine) same = 0;
-                static_assert(kBaMaxK <= 8, "flag words 16 + r");
-                L.coloc = same;
-            }
-            __syncthreads();
-        }
-    }
+    if (kCl) ba_done<true>(B, c, L);                                 // every workgroup's segment and observation records are written
     else {
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");       // the segment and observation records are written
         __syncthreads();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");       // ... and read below by other waves: drop this CU's L1 copies
     }
     BA_TICK(12)
-    if (lds_path) { }                                                  // (H_pp, g_p and the segments' cost are in LDS already)
-    else if (shared) ba_reduce_pairs<true>(B, c, L, BaOutGlob<true>{ B.hred + (size_t)c.win * kBaHred }, 0, c.K);
-    else ba_reduce_pairs<kCl>(B, c, L, BaOutLds{ L }, 0, 1);
+    ba_reduce_pairs<kCl>(B, c, L);
     BA_TOCK(12)
     BA_TICK(13)
-    if (shared) {
-        ba_feature_pass<true, kBig, true>(B, c, L, G, hpd, 0, c.K);
-        // the other workgroups' shares: wait for their "sums done" words, drop this CU's L1 (their stores went through the shared L2; the coupling rows are
-        // read with plain loads from here on), load H_pp | g_p and H_ff | g_f
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        unsigned int *flags = B.bar + (size_t)c.win * kBaBar;
-        if (tid < 64 && !L.failed) { if (!ba_wait_flags(flags + 9, c.K - 1, (unsigned int)(L.eval_no + 1), B.fail) && tid == 0) L.failed = 1; }
-        __syncthreads();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-        const double *hr = B.hred + (size_t)c.win * kBaHred;
-        for (int k = tid; k < kBaHred; k += kBaT) { const double v = ld_sh<true>(hr + k); if (k >= kBaP * kBaP) L.gp[k - kBaP * kBaP] = v; else L.Hpp[k] = v; }
-        if (!kBig) {
-            const double *fd = B.fdg + (size_t)c.win * 2 * B.feat_cap;
-            for (int f = tid; f < c.F; f += kBaT) { L.Hdd[f] = ld_sh<true>(fd + f); L.gdd[f] = ld_sh<true>(fd + B.feat_cap + f); }
-        }
-        __syncthreads();
-    } else
-        ba_feature_pass<kCl, kBig, false>(B, c, L, G, hpd, 0, 1);
+    ba_feature_pass<kCl, kBig>(B, c, L, G, hpd);
     BA_TOCK(13)
     // every segment's block is in H_pp: the LASERFactor chain left in gn | va | vb is added by everybody, the prior by wave 1 -- after the pair
     // blocks in every run
@@ -1282,7 +1011,7 @@ __device__ __noinline__ double ba_evaluate(const BaBatch &B, const BaCtx c, BaLd
         small_cost = wave_sum_d(small_cost);
         if (lane == 0) L.red[3 * kBaW - 2] = small_cost;
     }
-    if (!lds_path) ba_segment_cost<kCl>(c, L, tiles + 256 + 3, kBaPairTile);
+    ba_segment_cost<kCl>(c, L, tiles + 256 + 3, kBaPairTile);
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
     __syncthreads();
     const double cost = L.red[3 * kBaW - 1] + L.red[3 * kBaW - 2];
@@ -1305,8 +1034,7 @@ __device__ __noinline__ void ba_hs_mul(const BaCtx c, BaLds &L_arg, const BaBig 
     BA_TICK(4)
     for (int k = tid; k < N; k += kBaT) BA_V(gn, k) = BA_V(scale, k) * BA_V(va, k);
     __syncthreads();
-#if LMONO_BA_HS_FUSED
-    // ONE pass over the coupling rows (round 6: the camera rows and the depth rows each read all of them -- 2 x 275 KB per product for a 430-feature
+    // ONE pass over the coupling rows (until round 6 the camera rows and the depth rows each read all of them -- 2 x 275 KB per product for a 430-feature
     // window, a quarter of what the batched solve moves through HBM): wave w takes the features f = w (mod 8), lanes own the parameter columns
     // (coalesced 640-B rows), eight rows in flight.  A row's share of the camera rows is row x (feature's entry of the vector); its own depth row is the
     // dot product of the row with the pose part of the vector, summed over the wave (DPP row steps; the eight sums of a round are independent chains).
@@ -1334,44 +1062,6 @@ __device__ __noinline__ void ba_hs_mul(const BaCtx c, BaLds &L_arg, const BaBig 
         L.u.hs_part[wave][lane] = a0;
         if (lane < kBaPS - 64) L.u.hs_part[wave][64 + lane] = a1;
     }
-#else
-    // camera rows: wave w sums the features f = w (mod 8); lanes own the parameter columns (coalesced 640-B rows),
-    // eight feature rows in flight
-    {
-        double a0 = 0, a1 = 0;
-        for (int f = wave; f < F; f += 8 * kBaW) {
-            double r0[8], r1[8];
-#pragma unroll
-            for (int u = 0; u < 8; u++) {
-                const int fu = f + kBaW * u;
-                const double *row = hpd + (size_t)fu * kBaPS;
-                r0[u] = fu < F ? gld(row + lane) : 0.0;
-                r1[u] = (fu < F && lane < kBaPS - 64) ? gld(row + 64 + lane) : 0.0;
-            }
-#pragma unroll
-            for (int u = 0; u < 8; u++) {
-                const int fu = f + kBaW * u;
-                const double w = fu < F ? BA_V(gn, P + fu) : 0.0;
-                a0 += r0[u] * w; a1 += r1[u] * w;
-            }
-        }
-        L.u.hs_part[wave][lane] = a0;
-        if (lane < kBaPS - 64) L.u.hs_part[wave][64 + lane] = a1;
-    }
-    // depth rows: four lanes per feature, the 18 entries of a lane requested together
-    for (int f = tid >> 2; f < F; f += kBaT / 4) {
-        const double *row = hpd + (size_t)f * kBaPS;
-        double rv[18];
-#pragma unroll
-        for (int k = 0; k < 18; k++) { const int a = (tid & 3) + 4 * k; rv[k] = a < P ? gld(row + a) : 0.0; }
-        double acc = 0;
-#pragma unroll
-        for (int k = 0; k < 18; k++) { const int a = (tid & 3) + 4 * k; acc += rv[k] * (a < P ? BA_V(gn, a) : 0.0); }
-        acc += __shfl_xor(acc, 1);
-        acc += __shfl_xor(acc, 2);
-        if ((tid & 3) == 0) BA_V(vb, P + f) = (acc + BA_F(Hdd, f) * BA_V(gn, P + f)) * BA_V(scale, P + f);
-    }
-#endif
     __syncthreads();
     if (tid < P) {
         double acc = 0;
@@ -1772,13 +1462,11 @@ __device__ __noinline__ void ba_follow(const BaBatch &B, const BaCtx c, BaLds &L
     const double *mb = B.mbox + (size_t)c.win * kBaMbox;
     unsigned int *flags = B.bar + (size_t)c.win * kBaBar;
     G.vinv = mb + 96;                                   // (kBig: a follower reads the inverse depths straight from the mail box)
-    if (tid == 0) ba_flag_store(flags + 16 + c.rank, (unsigned int)ba_xcc_id() + 1u);
-    double *hpd = B.hpd + (size_t)c.win * B.feat_cap * kBaPS;
     for (;;) {
         if (tid < 64) { if (!ba_wait_flags(flags, 1, (unsigned int)(L.eval_no + 1), B.fail) && tid == 0) L.failed = 1; }
         __syncthreads();
         if (L.failed) return;
-        const int cmd = (int)ld_sh<true>(mb), reuse = (int)ld_sh<true>(mb + 1), shared = (int)ld_sh<true>(mb + 3);
+        const int cmd = (int)ld_sh<true>(mb), reuse = (int)ld_sh<true>(mb + 1);
         if (cmd == 3) return;
         if (!reuse) {
             for (int k = tid; k < 7 * c.n_poses; k += kBaT) L.cposes[k] = ld_sh<true>(mb + 8 + k);
@@ -1795,22 +1483,6 @@ __device__ __noinline__ void ba_follow(const BaBatch &B, const BaCtx c, BaLds &L
             if ((int)ld_sh<true>(mb + 2) == ba_xcc_id()) ba_segments<true, false, kBig, true>(B, c, L, G, L.cex, pairdat);      // the leader's XCD: plain stores stay in the shared L2
             else ba_segments<true, true, kBig, true>(B, c, L, G, L.cex, pairdat);
             ba_done<false>(B, c, L);
-            if (shared) {
-                // every workgroup's records (the other followers' and the leader's): then this workgroup's share of the ordered sums and of the per-feature
-                // pass -- an entry is formed by one thread from the same records in the same order whoever that thread is
-                if (tid < 64) {
-                    bool ok = ba_wait_flags(flags + 1, c.K - 1, (unsigned int)(L.eval_no + 1), B.fail);
-                    ok = ok && ba_wait_flags(flags + 8, 1, (unsigned int)(L.eval_no + 1), B.fail);
-                    if (!ok && tid == 0) L.failed = 1;
-                }
-                __syncthreads();
-                if (L.failed) return;
-                ba_reduce_pairs<true>(B, c, L, BaOutGlob<true>{ B.hred + (size_t)c.win * kBaHred }, c.rank, c.K);
-                ba_feature_pass<true, kBig, true>(B, c, L, G, hpd, c.rank, c.K);
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                __syncthreads();
-                if (tid == 0) ba_flag_store(flags + 8 + c.rank, (unsigned int)(L.eval_no + 1));
-            }
         }
         if (tid == 0) L.eval_no++;
         __syncthreads();
@@ -1829,7 +1501,7 @@ __global__ __launch_bounds__(kBaT) void k_ba_solve(BaBatch B, int K, int spread)
     BaCtx c;
     c.K = kCl ? K : 1;
     c.rank = kCl ? ((int)blockIdx.x / 8) % K : 0;
-    const int w = kCl ? ((int)blockIdx.x / 8 / K) * 8 + (((int)blockIdx.x % 8) + ((spread & 1) ? 8 - c.rank : 0)) % 8 : (int)blockIdx.x;
+    const int w = kCl ? ((int)blockIdx.x / 8 / K) * 8 + (((int)blockIdx.x % 8) + (spread ? 8 - c.rank : 0)) % 8 : (int)blockIdx.x;
     c.GW = c.K == 1 ? kBaW : c.K * kBaW - 1;
     c.win = w;
     if (w >= B.n_windows) return;
@@ -1856,8 +1528,7 @@ __global__ __launch_bounds__(kBaT) void k_ba_solve(BaBatch B, int K, int spread)
         G.Hdd = gv; G.gdd = gv + kBaMaxFeat; G.scale = gv + 2 * kBaMaxFeat; G.D = gv + 3 * kBaMaxFeat; G.gs = gv + 4 * kBaMaxFeat; G.gn = gv + 5 * kBaMaxFeat;
         G.va = gv + 6 * kBaMaxFeat; G.vb = gv + 7 * kBaMaxFeat; G.vinv = ginvd; G.fobs = B.feat_obs_off + c.f0; G.fanchor = B.feat_anchor + c.f0; G.seg = B.seg_tab + c.sg0; G.o0 = c.o0;
     }
-    // (spread bit 1 = LMONO_BA_SHARE_SUMS: the cluster shares the ordered sums; off by default -- measured slower, see ba_reduce_pairs)
-    if (tid == 0) { L.eval_no = 0; L.failed = 0; L.coloc = (spread & 2) ? -1 : 0; }
+    if (tid == 0) { L.eval_no = 0; L.failed = 0; }
 #ifdef LMONO_BA_PROF
     if (tid < 24) L.prof[tid] = 0;
 #endif

@@ -90,9 +90,6 @@ static_assert(kCfC - 1 <= kLbPad, "a chunk's loads may run kCfC - 1 points past 
 #define LMONO_CF_WALK_ROUNDS 64
 #endif
 constexpr int kCfNnRounds = LMONO_CF_NN_ROUNDS, kCfWalkRounds = LMONO_CF_WALK_ROUNDS;
-#ifndef LMONO_WALK_TIGHT
-#define LMONO_WALK_TIGHT 1      // a walk pass that SAW its partners outside its ball continues with the ball that just holds them, not with the next rung
-#endif
 
 // run request, one word: line (7 bits) | first bin (9) << 7 | bins (9) << 16 | owner (7) << 25.  The cloud follows from the owner.
 __device__ __forceinline__ unsigned int cf_request_line(int line, int b0, int nb, int owner) { return (unsigned int)line | ((unsigned int)b0 << 7) | ((unsigned int)nb << 16) | ((unsigned int)owner << 25); }
@@ -567,7 +564,6 @@ __global__ __launch_bounds__(kCfT, LMONO_CF_WAVES) void k_corr_flat(BatchView b,
                 else {
                     wpass++;
                     while (wpass < 4 && rad[wpass] <= rad[wpass - 1]) wpass++;
-#if LMONO_WALK_TIGHT
                     // the pass SAW the partners it needs, but outside its ball (its arc's bins hold more than the ball): the ball that just holds
                     // them settles the walk exactly -- every point outside it is farther -- and is usually much smaller than the next rung's
                     if (other < thr && (edge || same < thr)) {
@@ -575,7 +571,6 @@ __global__ __launch_bounds__(kCfT, LMONO_CF_WAVES) void k_corr_flat(BatchView b,
                         const float rt = sqrtf(d) * 1.002f + 1e-3f;
                         if (wpass < 4 && rt < rad[wpass] && d < 24.0f) r_seed = rt;
                     }
-#endif
                 }
             }
         }

@@ -10,7 +10,8 @@
 //                rings longer than the small LDS slice go through a work list to a second launch
 //   k_voxel      one workgroup per (scan, ring): voxel-grid down-sampling of the less-flat points (run-length segments from
 //                ballots, bucket sort of the segment keys in LDS; <9 slots> / <16 slots> instantiations + work list)
-//   k_compact    one workgroup per scan: prefix sums over (ring, sector), compaction of the four clouds, line tables
+//   k_compact_index  one workgroup per scan: prefix sums over (ring, sector), compaction of the four clouds, line tables, and the (scan line,
+//                azimuth bin) index of the two "last" clouds (the steps of line_index.hip) built while their points pass through
 // Arithmetic is float/double exactly as the CPU restatement evaluates it (compiled with -ffp-contract=off).
 #include "batch.hpp"
 
@@ -343,7 +344,6 @@ __global__ __launch_bounds__(256) void k_curvature(BatchView b)
 // keeps its sector elements (curvature, suppressed flag) in registers and a pick is one 64-lane arg-max / arg-min
 // over the packed key (curvature bits, index), which also reproduces the (curvature, index) tie order of the sort.
 constexpr int kSelMaxPerLane = (kRingCap / 6 + 1 + 63) / 64;   // 11 elements per lane for the largest legal sector
-constexpr int kSelWaveLds = 2 * kRingCap;                      // picked, gap bytes of one ring (unfused flavour; sel_slice_bytes below)
 
 // key of a sector element: hi = curvature bits, lo = (index << 8 | suppression reach).  Ordering by (hi, lo) = ordering by
 // (curvature, index), so the arg-max / arg-min over keys reproduces the sort's tie order; the winner's reach rides along.
@@ -352,18 +352,12 @@ constexpr int kSelWaveLds = 2 * kRingCap;                      // picked, gap by
 __device__ __forceinline__ unsigned int select_lo(int idx, unsigned int reach) { return ((unsigned int)idx << 8) | reach; }
 
 // one sector of one ring, M register slots per lane (element m of a lane is ring-local index sp + lane + 64 m)
-#ifndef LMONO_SEL_COMPACT
-#define LMONO_SEL_COMPACT 1
-#endif
 constexpr int kSelScratch = 64 * 8;      // per wave: one (curvature bits, index | reach) pair per lane, the compacted candidates of a sector
 
-// kFused (LMONO_FUSE_CURV_SELECT, round 5): the curvature is computed here, from the sector's points staged in LDS (xs / ys / zs: staged index 0 =
-// ring point sp - 5), written to `curv` (the API returns it) instead of read from it, and `gap` is the SECTOR's bit mask (bit k = gap flag of ring
-// point sp - 5 + k) instead of the ring's.  Same expressions in the same order as k_curvature.
-template <int M, bool kFused>
-__device__ __forceinline__ void select_sector(int lane, int j, int sp, int slen, int rbeg, float *curv, unsigned char *picked,
+template <int M>
+__device__ __forceinline__ void select_sector(int lane, int j, int sp, int slen, int rbeg, const float *curv, unsigned char *picked,
                                               signed char *label, const unsigned long long *gap, int *sel_sh, int *sel_sh_n, int *sel_fl, int *sel_fl_n,
-                                              unsigned int *scratch, const float *sx = nullptr, const float *sy = nullptr, const float *sz = nullptr)
+                                              unsigned int *scratch)
 {
     unsigned int kh[M], kl[M];
     unsigned int dead = 0, big = 0, small = 0;     // bit m: suppressed / out of range; curvature > 0.1; < 0.1
@@ -375,19 +369,11 @@ __device__ __forceinline__ void select_sector(int lane, int j, int sp, int slen,
         bool cand = false;
         if (e < slen) {
             const int i = sp + e;
-            float c;
-            if (kFused) {
-                const int q = e + 5;
-                const float dx = sx[q - 5] + sx[q - 4] + sx[q - 3] + sx[q - 2] + sx[q - 1] - 10 * sx[q] + sx[q + 1] + sx[q + 2] + sx[q + 3] + sx[q + 4] + sx[q + 5];
-                const float dy = sy[q - 5] + sy[q - 4] + sy[q - 3] + sy[q - 2] + sy[q - 1] - 10 * sy[q] + sy[q + 1] + sy[q + 2] + sy[q + 3] + sy[q + 4] + sy[q + 5];
-                const float dz = sz[q - 5] + sz[q - 4] + sz[q - 3] + sz[q - 2] + sz[q - 1] - 10 * sz[q] + sz[q + 1] + sz[q + 2] + sz[q + 3] + sz[q + 4] + sz[q + 5];
-                c = dx * dx + dy * dy + dz * dz;
-                curv[i] = c;
-            } else c = curv[i];
+            const float c = curv[i];
             // suppression reach: the neighbour walk marks l = 1..5 forward while the gap before point i+l is short, and the same backward --
             // the zero runs above / below bit i of the ring's gap BIT mask (two independent 8-byte LDS reads; as bytes the two walks were up to
             // ten dependent single-byte reads per element, the latency that bound the kernel).  i >= 5 inside a sector.
-            const int jw = kFused ? e : i - 5;
+            const int jw = i - 5;
             const unsigned long long wa = gap[jw >> 6], wb = gap[(jw >> 6) + 1];
             const int sh = jw & 63;
             const unsigned int win = (unsigned int)((wa >> sh) | (sh ? wb << (64 - sh) : 0ull));      // bit k = gap flag of point i - 5 + k
@@ -399,18 +385,15 @@ __device__ __forceinline__ void select_sector(int lane, int j, int sp, int slen,
             if ((double)c > 0.1) { big |= 1u << m; cand = !pk; }
             if ((double)c < 0.1) small |= 1u << m;
         } else dead |= 1u << m;
-#if LMONO_SEL_COMPACT
         {
             const unsigned long long mk = __ballot(cand);
             const int pos = n_big + __popcll(mk & ((1ull << lane) - 1ull));
             if (cand && pos < 64) { scratch[2 * pos] = kh[m]; scratch[2 * pos + 1] = kl[m]; }
             n_big += __popcll(mk);
         }
-#endif
     }
     // ---- largest curvature first: <= 2 sharp, <= 20 less sharp
     int largest = 0;
-#if LMONO_SEL_COMPACT
     // Only the points with c > 0.1 that are not suppressed yet can be picked here -- a few dozen of a sector's ~300.  When they fit one per lane
     // they are compacted (ballot ranks, through 512 B of LDS): a pick then costs one comparison per lane + the wave reduction instead of a pass
     // over the lane's M slots.  Same live set, same (curvature, index) order: the same picks.  The slot bitmask `dead` is kept up to date for the
@@ -443,9 +426,6 @@ __device__ __forceinline__ void select_sector(int lane, int j, int sp, int slen,
         }
     }
     while (!compact) {
-#else
-    while (true) {
-#endif
         const unsigned int live = big & ~dead;
         // the lane's own best: slots ascend in index, so ">=" keeps the larger index among equal curvatures (live curvatures are > 0.1: 0 = none)
         unsigned int bh = 0u, bl = 0u;
@@ -521,40 +501,12 @@ template <typename T> __device__ __forceinline__ T *uni_ptr(T *p)
     return (T *)(GT *)uni64((long long)p);
 }
 
-#ifndef LMONO_FUSE_CURV_SELECT
-#define LMONO_FUSE_CURV_SELECT 0
-#endif
-// LDS slice of one wave for rings of up to `cap` points.  Unfused: picked bytes + the ring's gap bit mask (cap bytes reserved).  Fused with the
-// curvature: picked bytes + the staged x / y / z of one sector and its halo + the sector's gap words.
-__host__ __device__ constexpr int sel_sector_cap(int cap) { return cap / 6 + 2; }
-__host__ __device__ constexpr int sel_slice_bytes(int cap)
-{
-    return LMONO_FUSE_CURV_SELECT ? ((cap + 15) & ~15) + 3 * 4 * ((sel_sector_cap(cap) + 12 + 3) & ~3) + 8 * ((sel_sector_cap(cap) + 12) / 64 + 2) : 2 * cap;
-}
-// curvature of the cloud points first .. first + count - 1 of a scan straight from HBM (fused flavour: the points at a ring's ends, which no sector
-// holds, and rings that take no part in the selection) -- k_curvature's expressions
-__device__ __forceinline__ void curv_points_global(const float4 *c, float *curv, int n, int first, int count, int lane)
-{
-    for (int k = lane; k < count; k += 64) {
-        const int i = first + k;
-        float cv = 0.f;
-        if (i >= 5 && i < n - 5) {
-            float px[11], py[11], pz[11];
-#pragma unroll
-            for (int d = 0; d < 11; d++) { const float4 p = c[i - 5 + d]; px[d] = p.x; py[d] = p.y; pz[d] = p.z; }
-            const float dx = px[0] + px[1] + px[2] + px[3] + px[4] - 10 * px[5] + px[6] + px[7] + px[8] + px[9] + px[10];
-            const float dy = py[0] + py[1] + py[2] + py[3] + py[4] - 10 * py[5] + py[6] + py[7] + py[8] + py[9] + py[10];
-            const float dz = pz[0] + pz[1] + pz[2] + pz[3] + pz[4] - 10 * pz[5] + pz[6] + pz[7] + pz[8] + pz[9] + pz[10];
-            cv = dx * dx + dy * dy + dz * dz;
-        }
-        curv[i] = cv;
-    }
-}
+// LDS slice of one wave for rings of up to `cap` points: picked bytes + the ring's gap bit mask (cap bytes reserved)
+__host__ __device__ constexpr int sel_slice_bytes(int cap) { return 2 * cap; }
 
 // one ring by one wave; cap = ring points the wave's LDS slice (sel_slice_bytes(cap) at smem_w) can hold
 __device__ __forceinline__ void select_ring(BatchView &b, int r, int s, int lane, unsigned char *smem_w, int cap, bool may_defer, unsigned int *scratch)
 {
-    constexpr bool kFused = LMONO_FUSE_CURV_SELECT != 0;
     r = uni(r); s = uni(s);
     const int64_t off = uni64(b.off[s]);
     const int *rb = b.ring_begin + s * 65;
@@ -564,13 +516,10 @@ __device__ __forceinline__ void select_ring(BatchView &b, int r, int s, int lane
     int *sel_sh_n = uni_ptr(b.sel_sharp_n + (s * 64 + r) * kSectors);
     int *sel_fl = uni_ptr(b.sel_flat + (size_t)((s * 64 + r) * kSectors) * 4);
     int *sel_fl_n = uni_ptr(b.sel_flat_n + (s * 64 + r) * kSectors);
-    const float4 *cl = uni_ptr(b.cloud + off);
-    const int n_cloud = kFused ? uni(b.n_cloud[s]) : 0;
     if (E - S < 6 || len > kRingCap) {
         if (lane < kSectors) { sel_sh_n[lane] = 0; sel_fl_n[lane] = 0; }
         if (lane == 0 && len > kRingCap) atomicOr(&b.status[s], kStatusRingOverflow);
         for (int i = lane; i < len; i += 64) b.label[off + rbeg + i] = 0;
-        if (kFused) curv_points_global(cl, uni_ptr(b.curv + off), n_cloud, rbeg, len, lane);
         return;
     }
     if (len > cap) {
@@ -582,66 +531,26 @@ __device__ __forceinline__ void select_ring(BatchView &b, int r, int s, int lane
     // picked and gap bytes
     unsigned char *picked = smem_w;
     signed char *label = uni_ptr((signed char *)(b.label + off + rbeg));
-    float *curv = uni_ptr(b.curv + off + rbeg);
+    const float *curv = uni_ptr(b.curv + off + rbeg);
     const int span = E - S;
-    if (!kFused) {
-        // gap flags of the ring as a bit mask, one 64-bit word per 64 points (+ one word of padding read by the last elements' windows)
-        unsigned long long *gap = (unsigned long long *)(picked + cap);
-        for (int i0 = 0; i0 < len + 64; i0 += 64) {
-            const int i = i0 + lane;
-            unsigned char g = 0;
-            if (i < len) { picked[i] = 0; label[i] = 0; g = b.gap[off + rbeg + i]; }
-            const unsigned long long mk = __ballot(g != 0);
-            if (lane == 0) gap[i0 >> 6] = mk;
-        }
-        __builtin_amdgcn_wave_barrier();
-        for (int j = 0; j < kSectors; j++) {
-            const int sp = 5 + span * j / 6;
-            const int ep = 5 + span * (j + 1) / 6 - 1;
-            const int slen = ep - sp + 1;
-            // HDL-64-sized sectors (<= 320 / <= 384 points) take the 5- / 6-slot instantiations, longer rings the full one
-            if (slen <= 5 * 64) select_sector<5, false>(lane, j, sp, slen, rbeg, curv, picked, label, gap, sel_sh, sel_sh_n, sel_fl, sel_fl_n, scratch);
-            else if (slen <= 6 * 64) select_sector<6, false>(lane, j, sp, slen, rbeg, curv, picked, label, gap, sel_sh, sel_sh_n, sel_fl, sel_fl_n, scratch);
-            else select_sector<kSelMaxPerLane, false>(lane, j, sp, slen, rbeg, curv, picked, label, gap, sel_sh, sel_sh_n, sel_fl, sel_fl_n, scratch);
-        }
-        return;
+    // gap flags of the ring as a bit mask, one 64-bit word per 64 points (+ one word of padding read by the last elements' windows)
+    unsigned long long *gap = (unsigned long long *)(picked + cap);
+    for (int i0 = 0; i0 < len + 64; i0 += 64) {
+        const int i = i0 + lane;
+        unsigned char g = 0;
+        if (i < len) { picked[i] = 0; label[i] = 0; g = b.gap[off + rbeg + i]; }
+        const unsigned long long mk = __ballot(g != 0);
+        if (lane == 0) gap[i0 >> 6] = mk;
     }
-    // ---- fused with the curvature (VERDICT r4 #2b): no k_curvature launch; a sector's points and their halo are staged in LDS, the curvature of its
-    // elements and the gap flags around them are computed from the stage
-    const int scap = (sel_sector_cap(cap) + 12 + 3) & ~3;
-    float *sx = (float *)(smem_w + ((cap + 15) & ~15)), *sy = sx + scap, *sz = sy + scap;
-    unsigned long long *gap = (unsigned long long *)(sz + scap);
-    for (int i = lane; i < len; i += 64) { picked[i] = 0; label[i] = 0; }
-    // the ring's end points belong to no sector: their curvature comes straight from HBM
-    curv_points_global(cl, uni_ptr(b.curv + off), n_cloud, rbeg, 5, lane);
-    curv_points_global(cl, uni_ptr(b.curv + off), n_cloud, rend - 6, 6, lane);
+    __builtin_amdgcn_wave_barrier();
     for (int j = 0; j < kSectors; j++) {
         const int sp = 5 + span * j / 6;
         const int ep = 5 + span * (j + 1) / 6 - 1;
         const int slen = ep - sp + 1;
-        __builtin_amdgcn_wave_barrier();               // the previous sector is done with the stage
-        // ring points sp - 5 .. ep + 6 (a point past the cloud reads as the origin: only its gap flag could use it, and that is forced to 0)
-        for (int k = lane; k < slen + 12; k += 64) {
-            const int ci = rbeg + sp - 5 + k;
-            float4 p = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (ci < n_cloud) p = cl[ci];
-            sx[k] = p.x; sy[k] = p.y; sz[k] = p.z;
-        }
-        __builtin_amdgcn_wave_barrier();
-        for (int k0 = 0; k0 < slen + 11 + 64; k0 += 64) {
-            const int k = k0 + lane;
-            bool g = false;
-            if (k < slen + 11 && rbeg + sp - 5 + k + 1 < n_cloud) {
-                const float gx = sx[k + 1] - sx[k], gy = sy[k + 1] - sy[k], gz = sz[k + 1] - sz[k];
-                g = (double)(gx * gx + gy * gy + gz * gz) > 0.05;
-            }
-            const unsigned long long mk = __ballot(g);
-            if (lane == 0) gap[k0 >> 6] = mk;
-        }
-        __builtin_amdgcn_wave_barrier();
-        if (slen <= 5 * 64) select_sector<5, true>(lane, j, sp, slen, rbeg, curv, picked, label, gap, sel_sh, sel_sh_n, sel_fl, sel_fl_n, scratch, sx, sy, sz);
-        else if (slen <= 6 * 64) select_sector<6, true>(lane, j, sp, slen, rbeg, curv, picked, label, gap, sel_sh, sel_sh_n, sel_fl, sel_fl_n, scratch, sx, sy, sz);
-        else select_sector<kSelMaxPerLane, true>(lane, j, sp, slen, rbeg, curv, picked, label, gap, sel_sh, sel_sh_n, sel_fl, sel_fl_n, scratch, sx, sy, sz);
+        // HDL-64-sized sectors (<= 320 / <= 384 points) take the 5- / 6-slot instantiations, longer rings the full one
+        if (slen <= 5 * 64) select_sector<5>(lane, j, sp, slen, rbeg, curv, picked, label, gap, sel_sh, sel_sh_n, sel_fl, sel_fl_n, scratch);
+        else if (slen <= 6 * 64) select_sector<6>(lane, j, sp, slen, rbeg, curv, picked, label, gap, sel_sh, sel_sh_n, sel_fl, sel_fl_n, scratch);
+        else select_sector<kSelMaxPerLane>(lane, j, sp, slen, rbeg, curv, picked, label, gap, sel_sh, sel_sh_n, sel_fl, sel_fl_n, scratch);
     }
 }
 
@@ -1061,31 +970,42 @@ __device__ __forceinline__ void voxel_ring(BatchView &b, int r, int s)
 // provided no point precedes a point whose line is >= 3 lower ("regular"); irregular clouds are flagged and walked
 // in array order instead.  Lines are not monotone in general: A-LOAM's relTime can be negative (line = ring - 1).
 // ------------------------------------------------------------------------------------------------
-#ifndef LMONO_COMPACT_T
-#define LMONO_COMPACT_T 256
-#endif
-constexpr int kCompT = LMONO_COMPACT_T;      // threads per scan of the stand-alone kernel; 256 / 512 / 1024 measured the same 2.0 ms per pass (profiles/r4).
-// Not "bound by its traffic", as this line said until round 8: the fused kernel moved 12.7 GB per pass (5.7 fetched + 7.0 written) in 3.97 ms,
-// 3.2 TB/s, with ONE workgroup per CU; at two per CU, one read of the "last" clouds fewer and the start tables written in rows it moves 10.9 GB
-// in about 3.1 ms, 3.5 TB/s (profiles/r8/NOTES.md).  Residency and its own chain of phases bound it first, bytes second.
-static_assert(kCompT >= 256 && kCompT % 64 == 0, "the four prefixes take one wave each");
 
-// What compact_scan tells about the two "last" clouds (cld 0: less sharp, 1: less flat) while their points pass through its copy loops.  kOn = false:
-// nothing (k_compact).  k_compact_index (odometry.hip) counts the points per (line, azimuth bin) there instead of reading the cloud once more.
+// compact_scan's feed: what happens to the two "last" clouds (cld 0: less sharp, 1: less flat) while their points pass through its copy loops.  The
+// points are counted per (line, azimuth bin) and feed the elevation bounds while the loop holds them, instead of the cloud being read once more; tables
+// and scatter follow the loop.  The feed's state (the 16-bit counters of line_index.hip) serves one cloud after the other.
 //   reset(cld, n)   before the cloud's copy loop, by every thread; a barrier of compact_scan follows before the first point()
 //   point(ok, p)    every point the loop writes, called by WHOLE waves (ok = false: a lane without a point)
 //   finish(cld, n)  behind the loop, by every thread; holds barriers
-struct CompactNoFeed {
-    static constexpr bool kOn = false;
-    __device__ __forceinline__ void reset(int, int) {}
-    __device__ __forceinline__ void point(bool, const float4 &) {}
-    __device__ __forceinline__ void finish(int, int) {}
+struct CompactIndexFeed {
+    const BatchView &b;
+    LiLds L;
+    int s;
+    bool on;                       // false: a cloud of more than 65535 points, copied plainly and listed for the full-width launch
+    __device__ __forceinline__ void reset(int cld, int n)
+    {
+        on = n <= 65535;
+        if (on) li_reset<true>(L);
+        else if (threadIdx.x == 0) b.li_todo[1 + atomicAdd(&b.li_todo[0], 1)] = s * 2 + cld;
+    }
+    __device__ __forceinline__ void point(bool ok, const float4 &p) { if (on) li_count<true>(L, ok, p.x, p.y, p.z, p.w); }
+    __device__ __forceinline__ void finish(int cld, int n)
+    {
+        if (!on) return;
+        __syncthreads();
+        li_tables<true>(b, L, s, cld != 0, n);
+        // this workgroup's own stores (the cloud) are read back by the scatter: they are out of the vector unit before anybody loads
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+        __syncthreads();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+        li_scatter<true>(b, L, s, cld != 0, n);
+    }
 };
 
-// one scan's feature clouds compacted by kT threads (k_compact: kCompT; k_compact_index, odometry.hip: the line index's 1024)
-template <int kT, class Feed>
-__device__ __forceinline__ void compact_scan(const BatchView &b, int s, Feed &feed)
+// one scan's feature clouds compacted and indexed by the kLiT threads of k_compact_index
+__device__ __forceinline__ void compact_scan(const BatchView &b, int s, CompactIndexFeed &feed)
 {
+    constexpr int kT = kLiT;
     const int tid = threadIdx.x;
     const int64_t off = b.off[s];
     constexpr int NE = kMaxRings * kSectors;   // 384
@@ -1188,12 +1108,10 @@ __device__ __forceinline__ void compact_scan(const BatchView &b, int s, Feed &fe
         for (int q = 0; q < 2; q++) if (pos[q] >= 0) flat[pos[q]] = p2[q];
     }
     // the feed's state serves one cloud after the other
-    if (Feed::kOn) {
-        feed.finish(0, n_ls);
-        __syncthreads();
-        feed.reset(1, n_lf);
-        __syncthreads();
-    }
+    feed.finish(0, n_ls);
+    __syncthreads();
+    feed.reset(1, n_lf);
+    __syncthreads();
     // less-flat cloud = the rings' voxel outputs back to back: every thread finds the ring of its output index by a binary
     // search over the ring prefix (all loads independent, four per thread in flight)
     for (int base = 0; base < n_lf; base += 4 * kT) {      // uniform trip count: feed.point() needs whole waves
@@ -1246,10 +1164,25 @@ __device__ __forceinline__ void compact_scan(const BatchView &b, int s, Feed &fe
     }
 }
 
-__global__ __launch_bounds__(kCompT) void k_compact(BatchView b)
+// Compaction and the 16-bit line index as ONE kernel (round 5, VERDICT r4 #2a): a workgroup compacts its scan's feature clouds and indexes the two "last"
+// clouds right away.  Round 5 measured the fusion as neutral against the two stand-alone kernels (1.90 + 2.02 -> 3.92 ms per pass; that pair was removed
+// in round 9) and put that down to traffic; round 8 found the cause in
+// the kernel's resources: 91 VGPRs, so ONE 1024-thread workgroup per CU (the stand-alone kernels ran two), and the re-reads of the clouds it had just
+// written were not served by L2 (1.25 MB fetched per scan for 0.55 MB of clouds).  Since round 8 (profiles/r8/NOTES.md):
+//   * the copy loops of compact_scan count the points per (line, bin) and feed the elevation bounds while they hold them (CompactIndexFeed): the
+//     separate count pass over the written cloud is gone, 0.94 MB fetched per scan;
+//   * the phases are separate functions over LDS state with nothing carried between them in registers: 52 VGPRs, 48 B of scratch, 57.5 KB of LDS,
+//     TWO workgroups per CU (the launch bound pins 8 waves per SIMD; the occupancy query of -DLMONO_TILE_PROF builds reports it);
+//   * the start table leaves LDS in rows (li_tables).
+// 3.97 -> 3.10 ms per pass: 10.9 GB moved in about 3.1 ms, 3.5 TB/s, where one workgroup per CU moved 12.7 GB in 3.97 ms.  Residency and its own chain
+// of phases bound it first, bytes second.  The 16-bit counters serve one cloud after the other; a cloud of more than 65535 points is copied plainly and
+// goes to the full-width launch's list (k_line_index<false>, line_index.hip).
+__global__ __launch_bounds__(kLiT, 8) void k_compact_index(BatchView b)
 {
-    CompactNoFeed feed;
-    compact_scan<kCompT>(b, b.scan0 + blockIdx.x, feed);
+    extern __shared__ __align__(16) int s_cnt[];
+    __shared__ int s_wsum[kLiT / 64], s_emin[66], s_emax[66];
+    CompactIndexFeed feed = { b, { s_cnt, s_wsum, s_emin, s_emax }, b.scan0 + (int)blockIdx.x, false };
+    compact_scan(b, feed.s, feed);
 }
 
 } // namespace lmono

@@ -108,11 +108,7 @@ static int scanreg_launch(lmono_ctx *c, lmono_scan_batch *b, int scan0, int n_sc
     if (rt_tiles > 0) hipLaunchKernelGGL(k_ring_scatter, dim3(rt_tiles, n_scans), dim3(kRtT), 0, st, v);
     HIP_TRY(c, hipEventRecord(c->ev[1], st));
     const int tiles = (int)((max_pts + kCurvTile - 1) / kCurvTile);
-#if !LMONO_FUSE_CURV_SELECT
     if (tiles > 0) hipLaunchKernelGGL(k_curvature, dim3(tiles, n_scans), dim3(256), 0, st, v);
-#else
-    (void)tiles;                                    // the curvature is computed inside k_select
-#endif
     HIP_TRY(c, hipEventRecord(c->ev[2], st));
     // the kernels below run one workgroup per ring of the sensor; the counters of the rings it cannot produce stay zero
     const int n_rings = rings_used(b->v.n_lines);
@@ -125,11 +121,7 @@ static int scanreg_launch(lmono_ctx *c, lmono_scan_batch *b, int scan0, int n_sc
     hipLaunchKernelGGL((k_voxel<kVoxSmallSlots, kVoxSmallBits, true>), dim3(n_rings, n_scans), dim3(256), kVoxLdsSmall, st, v);
     hipLaunchKernelGGL((k_voxel<kVoxBigSlots, kVoxBigBits, false>), dim3(kVoxBigGrid), dim3(256), kVoxLdsBig, st, v);
     HIP_TRY(c, hipEventRecord(c->ev[4], st));
-#if LMONO_FUSE_COMPACT_INDEX
     hipLaunchKernelGGL(k_compact_index, dim3(n_scans), dim3(kLiT), kLiLdsHalf, st, v);       // compaction + (line, bin) index of the two "last" clouds
-#else
-    hipLaunchKernelGGL(k_compact, dim3(n_scans), dim3(kCompT), 0, st, v);
-#endif
     HIP_TRY(c, hipEventRecord(c->ev[5], st));
     // the hash grids serve the 32-lane-group search (LMONO_OPT_CORR_TILE 0) and the deferred lists of modes 1 and 2; the default
     // (flattened sweeps) works on the line index alone, so the grids are built on demand (ensure_grid)
@@ -140,9 +132,6 @@ static int scanreg_launch(lmono_ctx *c, lmono_scan_batch *b, int scan0, int n_sc
     }
 #endif
     HIP_TRY(c, hipEventRecord(c->ev[6], st));
-#if !LMONO_FUSE_COMPACT_INDEX
-    hipLaunchKernelGGL(k_line_index<true>, dim3(n_scans, 2), dim3(kLiT), kLiLdsHalf, st, v);
-#endif
     hipLaunchKernelGGL(k_line_index<false>, dim3(kLiBigGrid), dim3(kLiT), kLiLdsFull, st, v);
     HIP_TRY(c, hipEventRecord(c->ev[7], st));
     return check_launch(c, "scanreg kernels");

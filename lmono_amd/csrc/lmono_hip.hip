@@ -1,5 +1,6 @@
 // lmono_amd/csrc/lmono_hip.hip -- C ABI (include/lmono_hip.h) over the gfx950 kernels.  Single translation unit: the kernel files are included here, in one
 // fixed order, and the ABI of each subsystem (*_abi.hip, at the end) behind lmono_ctx, so that one `hipcc -shared` produces liblmono_hip.so.
+#include "line_index.hip"
 #include "frontend.hip"
 #include "odometry.hip"
 #include "corr_flat.hip"
@@ -232,7 +233,6 @@ extern "C" lmono_ctx *lmono_create(int device)
 #ifdef LMONO_DIAG_SEARCH
     if (hipFuncSetAttribute((const void *)k_grid_build, hipFuncAttributeMaxDynamicSharedMemorySize, kGridLds) != hipSuccess) { delete c; return nullptr; }
 #endif
-    if (hipFuncSetAttribute((const void *)k_line_index<true>, hipFuncAttributeMaxDynamicSharedMemorySize, kLiLdsHalf) != hipSuccess) { delete c; return nullptr; }
     if (hipFuncSetAttribute((const void *)k_compact_index, hipFuncAttributeMaxDynamicSharedMemorySize, kLiLdsHalf) != hipSuccess) { delete c; return nullptr; }
     if (hipFuncSetAttribute((const void *)k_line_index<false>, hipFuncAttributeMaxDynamicSharedMemorySize, kLiLdsFull) != hipSuccess) { delete c; return nullptr; }
     // the BA-side kernels with large dynamic LDS: per device, so per context (a second context on another GPU needs them too)

@@ -175,9 +175,6 @@ static inline void launch_cloud_grids(hipStream_t st, const CloudJob *jobs_d, in
 }
 
 // ---- small dense pieces, same arithmetic as oracle/lo_mapping.c --------------------------------------------------
-#ifndef LMONO_MAP_FAST_ROT
-#define LMONO_MAP_FAST_ROT 0      // 1: the 3 x 3 Jacobi rotations from v_rsq / v_rcp (a measurement: the oracle's arithmetic is the default)
-#endif
 // ascending eigenvalues / eigenvectors (columns) of a symmetric 3x3: cyclic Jacobi
 __device__ void sym_eig3(const double *A, double *evals, double *evecs)
 {
@@ -191,14 +188,9 @@ __device__ void sym_eig3(const double *A, double *evals, double *evecs)
             for (int q = p + 1; q < 3; q++) {
                 const double apq = a[p * 3 + q];
                 if (apq == 0.0) continue;
-#if LMONO_MAP_FAST_ROT
-                double c, s;
-                jacobi_cs(a[p * 3 + p], a[q * 3 + q], apq, c, s);
-#else
                 const double theta = (a[q * 3 + q] - a[p * 3 + p]) / (2.0 * apq);
                 const double t = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
                 const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-#endif
                 for (int k = 0; k < 3; k++) {
                     const double akp = a[k * 3 + p], akq = a[k * 3 + q];
                     a[k * 3 + p] = c * akp - s * akq; a[k * 3 + q] = s * akp + c * akq;
@@ -1340,7 +1332,7 @@ struct MapDev {                              // one per mapper, lives as long as
     int err;                                 // sticky error bits of the updates (kMdErr*)
     int n_gjobs;
     int last_sum[2];                         // points of the cubes the last update touched, per type   (bump .. last_sum: one read-back)
-    CopyJob gjobs[kMdGJobs];                 // the neighbourhood gather
+    CopyJob gjobs[kMdGJobs];                 // unused since the gather cuts its chunks itself (k_map_gather_copy_clear); kept: the fields behind it keep their places
     CloudJob cj[2];                          // its grids (everything but n is constant)
 };
 struct MapFrame {                            // one per frame, uploaded by the host (two buffers, by frame parity)
@@ -1349,7 +1341,7 @@ struct MapFrame {                            // one per frame, uploaded by the h
     unsigned int bar[16];
     int n_stack[2];                          // the scan filter's counts
     int n_map[2];                            // out: sizes of the neighbourhood clouds
-    int snap[6];                             // out: the map's bump[2] | err | n_gjobs | last_sum[2] as k_map_plan_gather found them -- behind the previous frame's commit,
+    int snap[6];                             // out: the map's bump[2] | err | n_gjobs | last_sum[2] as k_map_gather_copy_clear found them -- behind the previous frame's commit,
                                              // before this frame's update: the read-back of a frame takes THIS copy (x .. snap: one read-back), not the live words the
                                              // same frame's k_map_plan_update / k_map_commit are about to rewrite
     int cen[3], n_valid;
@@ -1392,59 +1384,6 @@ __global__ __launch_bounds__(256) void k_map_shift(MapDev *dev, int axis, int di
     dev->tab[t][c] = v;
 }
 
-// the cubes of the neighbourhood, in validInd order, become the two map clouds: copy jobs, sizes for the grids and the optimisation
-__global__ __launch_bounds__(192) void k_map_plan_gather(MapDevCfg cfg)
-{
-    __shared__ int2 s_seg[2][kMdValidMax + 1];
-    MapDev *dev = cfg.dev;
-    const MapFrame *F = cfg.frame;
-    const int tid = threadIdx.x, nv = F->n_valid;
-    if (tid < 2 * kMdValidMax) {
-        const int t = tid / kMdValidMax, v = tid - t * kMdValidMax;
-        s_seg[t][v] = v < nv ? dev->tab[t][F->valid[v]] : make_int2(0, 0);
-    }
-    __syncthreads();
-    __shared__ int s_at[2][kMdValidMax + 1], s_job[2][kMdValidMax + 1], s_tot[2][2];
-    if (tid < 128) {         // wave t sums type t: two cubes per lane (75 <= 128), one scan for the points and one for the copy jobs
-        const int t = tid >> 6, lane = tid & 63;
-        int n[2], jn[2];
-#pragma unroll
-        for (int u = 0; u < 2; u++) { const int v = 2 * lane + u; n[u] = v < nv ? max(s_seg[t][v].y, 0) : 0; jn[u] = (n[u] + 4095) / 4096; }
-        const int in_n = wave_scan_incl(n[0] + n[1]), in_j = wave_scan_incl(jn[0] + jn[1]);
-        int at = in_n - n[0] - n[1], jb = in_j - jn[0] - jn[1];
-#pragma unroll
-        for (int u = 0; u < 2; u++) { const int v = 2 * lane + u; if (v < nv) { s_at[t][v] = at; s_job[t][v] = jb; } at += n[u]; jb += jn[u]; }
-        if (lane == 63) { s_tot[t][0] = in_n; s_tot[t][1] = in_j; }
-    }
-    __syncthreads();
-    const bool over = s_tot[0][0] > kMdNeighMax || s_tot[1][0] > kMdNeighMax;       // refused: the frame runs on an empty neighbourhood and reports it
-    if (tid >= 128 && tid < 134) {           // (this kernel runs behind the previous commit on the main stream: the words are that update's, whole)
-        const int k = tid - 128;
-        cfg.frame->snap[k] = k < 2 ? dev->bump[k] : k == 2 ? dev->err : k == 3 ? dev->n_gjobs : dev->last_sum[k - 4];
-    }
-    if (tid < 2) {
-        const int at = over ? 0 : s_tot[tid][0];
-        dev->cj[tid].n = at;
-        cfg.S->n_map[tid] = at;
-        cfg.frame->n_map[tid] = at;
-    }
-    if (tid == 0) {
-        dev->n_gjobs = over ? 0 : s_tot[0][1] + s_tot[1][1];
-        if (over) atomicOr(&dev->err, kMdErrNeigh);
-    }
-    if (over) return;
-    if (tid < 2 * kMdValidMax) {
-        const int t = tid / kMdValidMax, v = tid - t * kMdValidMax;
-        if (v < nv) {
-            const int2 sg = s_seg[t][v];
-            for (int o = 0, j = s_job[t][v] + (t ? s_tot[0][1] : 0); o < sg.y; o += 4096, j++) {
-                CopyJob J; J.src = cfg.arena[t] + sg.x + o; J.dst = cfg.neigh[t] + s_at[t][v] + o; J.n = min(4096, sg.y - o);
-                dev->gjobs[j] = J;
-            }
-        }
-    }
-}
-
 // jobs[0 .. *n_jobs): dst[0..n) = src[0..n), the workgroups stride over the table
 __global__ __launch_bounds__(256) void k_copy_jobs_n(const CopyJob *jobs, const int *n_jobs)
 {
@@ -1455,10 +1394,11 @@ __global__ __launch_bounds__(256) void k_copy_jobs_n(const CopyJob *jobs, const 
     }
 }
 
-// k_map_plan_gather + k_copy_jobs_n + k_grid_clear in ONE launch (round 6: the single-stream frame is a chain of ~35 dependent launches; these three were
-// ~17 us of kernels and two launch gaps).  EVERY workgroup forms the neighbourhood's plan for itself (150 table rows, two wave scans: a few microseconds,
+// The neighbourhood's plan, its copies (k_copy_jobs_n's work) and k_grid_clear in ONE launch (round 6: the single-stream frame is a chain of ~35 dependent
+// launches; as three launches these were ~17 us of kernels and two launch gaps -- profiles/r6; the three-launch form was removed in round 9).  The cubes of
+// the neighbourhood, in validInd order, become the two map clouds.  EVERY workgroup forms the neighbourhood's plan for itself (150 table rows, two wave scans: a few microseconds,
 // no cross-workgroup dependency); workgroup 0 publishes it (sizes for the grids and the optimisation, the read-back snapshot); then the workgroups stride
-// over the copy chunks (<= 4096 points each, as k_map_plan_gather cut them) and over the cells of the two hash tables, which k_grid_insert expects empty.
+// over the copy chunks (<= 4096 points each) and over the cells of the two hash tables, which k_grid_insert expects empty.
 constexpr int kMgcT = 256, kMgcGrid = 256;
 __global__ __launch_bounds__(kMgcT) void k_map_gather_copy_clear(MapDevCfg cfg)
 {

@@ -499,7 +499,7 @@ CloudJob neigh_cloud_job(const lmono_mapper *m, int t, int n)
     J.slot_of = m->slot[t]; J.rank_of = m->rank[t]; J.mask_out = m->masks + t; J.bump = m->masks + 2 + t;
     return J;
 }
-// the optimisation's view of a mapper: the stack sizes are read from the device (n_stack_d), the map's too when n_map is null (k_map_plan_gather writes them);
+// the optimisation's view of a mapper: the stack sizes are read from the device (n_stack_d), the map's too when n_map is null (k_map_gather_copy_clear writes them);
 // pose, statistics and barrier counters live in the frame's block
 MapStream map_stream(const lmono_mapper *m, const int *n_map, const int *n_stack_d, double *x, int *stats, unsigned int *bar)
 {
@@ -634,17 +634,11 @@ static int mapper_process_dev(lmono_ctx *c, lmono_mapper *m, lmono_scan_batch *b
         HIP_TRY(c, hipMemcpyAsync(&m->dev->tmp[0][0], &m->dev->tab[0][0], sizeof(int2) * 2 * kMapCubes, hipMemcpyDeviceToDevice, side));
         hipLaunchKernelGGL(k_map_shift, dim3((2 * kMapCubes + 255) / 256), dim3(256), 0, side, m->dev, sh.first, sh.second);
     }
-    // the neighbourhood's plan, its copies and the emptied hash tables in one launch (LMONO_MAP_MERGED=0: the three launches of rounds 4-5, for measurements)
-    static const bool merged = [] { const char *e = getenv("LMONO_MAP_MERGED"); return !(e && atoi(e) == 0); }();
-    if (merged)
-        hipLaunchKernelGGL(k_map_gather_copy_clear, dim3(kMgcGrid), dim3(kMgcT), 0, side, cfg);
-    else {
-        hipLaunchKernelGGL(k_map_plan_gather, dim3(1), dim3(192), 0, side, cfg);
-        hipLaunchKernelGGL(k_copy_jobs_n, dim3(128), dim3(256), 0, side, (const CopyJob *)m->dev->gjobs, (const int *)&m->dev->n_gjobs);
-    }
+    // the neighbourhood's plan, its copies and the emptied hash tables in one launch
+    hipLaunchKernelGGL(k_map_gather_copy_clear, dim3(kMgcGrid), dim3(kMgcT), 0, side, cfg);
     {
         const int est = std::max(65536, std::max(m->nmap_seen[0], m->nmap_seen[1]) * 5 / 4 + 32768);
-        launch_cloud_grids(side, (const CloudJob *)m->dev->cj, 2, est, merged);
+        launch_cloud_grids(side, (const CloudJob *)m->dev->cj, 2, est, true);
     }
     HIP_TRY(c, hipEventRecord(m->ev_side, side));
     // ---- main stream: the optimisation
@@ -652,7 +646,7 @@ static int mapper_process_dev(lmono_ctx *c, lmono_mapper *m, lmono_scan_batch *b
     launch_map_optimise(st, (const MapStream *)(blob + o_S), 1, n_last[0] + n_last[1], c->map_budget);
     HIP_TRY(c, hipEventRecord(m->ev_solve, st));
     // the read-back leaves on the side stream (the main stream goes straight on): [x | stats | bar | n_stack | n_map | snap] of the frame -- snap = the map's
-    // [bump | err | . | last_sum] as k_map_plan_gather copied them at the head of this frame (the live words are rewritten by this frame's own
+    // [bump | err | . | last_sum] as k_map_gather_copy_clear copied them at the head of this frame (the live words are rewritten by this frame's own
     // update on the main stream while the side stream reads; the snapshot is the previous update's, whole, as the header promises for stats[7])
     constexpr size_t kBackA = sizeof(double) * 8 + sizeof(int) * 8 + sizeof(unsigned int) * 16 + sizeof(int) * 4;
     static_assert(offsetof(MapFrame, snap) == kBackA, "the frame's read-back is one copy: x .. snap");

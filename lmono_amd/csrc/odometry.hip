@@ -5,7 +5,6 @@
 //   k_grid_build  one workgroup per (scan, table page): 1 m hash grid over less_sharp / less_flat (the "last" clouds
 //                 of the next scan), built page by page in LDS.  Exact 1-NN needs only neighbours closer than 5 m
 //                 (DISTANCE_SQ_THRESHOLD).
-//   k_line_index  one workgroup per (scan, cloud): copy of the cloud counting-sorted by (scan line, azimuth bin)
 //   k_correspond  32 lanes per feature point: de-skew transform (fp64), exact 1-NN over the 27 cells around the point
 //                 (candidates as u64 keys, four cells per round in 8-lane sub-groups; arc sweep of the line index for the
 //                 rare far cases), then the reference's scan-line walk restricted to the lines ra-2..ra+2 and the azimuth
@@ -13,6 +12,8 @@
 //   k_lm_solve    one workgroup per chain: <= 4 Levenberg-Marquardt iterations restating Ceres' trust-region loop,
 //                 closed-form edge/plane Jacobians, reduction into the 6x6 normal equations (fp64)
 //   k_pose_prefix sequential pose accumulation
+// The (scan line, azimuth bin) index the searches sweep (lb_key, az_bin, line_of, elev_of, lb_for_runs) is line_index.hip's, included ahead of this file;
+// the front end builds it (k_compact_index).
 #include "batch.hpp"
 
 namespace lmono {
@@ -478,270 +479,6 @@ __device__ __forceinline__ double boundary_residual(const double *a, const doubl
     for (int i = 0; i < 4; i++) r = fmax(r, fabs(a[i] - sg * b[i]));
     for (int i = 4; i < 7; i++) r = fmax(r, 0.1 * fabs(a[i] - b[i]));
     return r == r ? r : 1e300;            // a NaN never agrees
-}
-
-// ---- (line, azimuth-bin) index of a feature cloud -------------------------------------------------------------
-// Every candidate the searches ever accept lies closer than 5 m to the (transformed) feature point, i.e. within +-asin(r / rho_xy)
-// of its azimuth and within a few scan lines of its elevation.  k_line_index sorts a copy of every "last" cloud by (scan line,
-// azimuth bin) once per scan (counting sort in LDS) and keeps the start of every (line, bin) bucket: the candidates of a ball are ONE
-// contiguous run per scan line -- a handful of short coalesced sweeps instead of a pass over whole scan lines.  A point of the copy carries
-// (cloud index << 7 | line) in .w, the low word of the searches' u64 keys.
-// Round 4 measured the (bin, line)-major order beside this one (commit 9c24d9d holds both behind LMONO_LB_ORDER; profiles/r4/NOTES.md section 1):
-// equal for the chunked search (0.250 against 0.236 ms per launch), 3.0 instead of 2.2 ms per pass to build (a ring's consecutive points land 66
-// buckets apart: scattered 16-B writes).  Removed again.
-constexpr int kAzBins = 384;           // 0.9375 deg: about one point of a 0.2 m-voxelised cloud per bin and line at 12 m
-constexpr int kLineKeys = 66 * kAzBins;
-__device__ __forceinline__ int lb_key(int bin, int line) { return line * kAzBins + bin; }
-constexpr int kLbPad = 4;              // entries behind the index copies: k_corr_flat's 64-B chunks may read up to three points past a run
-// the runs of the copy that hold the lines va .. vb of the bins [b_lo, b_lo + nbins) (wrapping past the last bin): f(first point, count).
-// Fall-back kernels only: simple beats fast.
-template <class F>
-__device__ __forceinline__ void lb_for_runs(const int *table, int b_lo, int nbins, int va, int vb, F f)
-{
-    const int b_end = b_lo + nbins;
-    for (int part = 0; part < 2; part++) {
-        if (part == 1 && b_end <= kAzBins) break;
-        const int p0 = part ? 0 : b_lo, p1 = part ? b_end - kAzBins : min(b_end, kAzBins);
-        for (int v = va; v <= vb; v++) { const int s0 = table[v * kAzBins + p0]; f(s0, table[v * kAzBins + p1] - s0); }
-    }
-}
-
-__device__ __forceinline__ int az_bin(float x, float y)
-{
-    const float t = (atan2f(y, x) + 3.14159265f) * (kAzBins / 6.28318531f);
-    const int bi = (int)t;
-    return bi < 0 ? 0 : (bi >= kAzBins ? kAzBins - 1 : bi);
-}
-__device__ __forceinline__ int line_of(float w)
-{
-    const int v = (int)w;
-    return v < 0 ? 0 : (v > 65 ? 65 : v);
-}
-// elevation angle of a point as the index sees it (only ever compared with margins: no exactness requirement on atan2f)
-__device__ __forceinline__ float elev_of(float x, float y, float z) { return atan2f(z, sqrtf(x * x + y * y)); }
-// order-preserving float <-> int map for LDS atomicMin / atomicMax
-__device__ __forceinline__ int f2ord(float f) { const int i = __float_as_int(f); return i >= 0 ? i : i ^ 0x7fffffff; }
-__device__ __forceinline__ float ord2f(int i) { return __int_as_float(i >= 0 ? i : i ^ 0x7fffffff); }
-
-constexpr int kLiT = 1024;     // threads of k_line_index
-constexpr int kLiLdsHalf = kLineKeys * 2, kLiLdsFull = kLineKeys * 4;   // dynamic LDS: one 16-bit / 32-bit counter per (line, bin)
-constexpr int kLiBigGrid = 64;
-
-// One (scan, cloud): copy of the cloud counting-sorted by (line, azimuth bin), the (line, bin) start table, per-line elevation bounds.
-// kHalf: the counters are 16-bit halves of 32-bit LDS words (50 KB instead of 101 KB: more workgroups per CU -- the kernel is bound
-// by its own dependent rounds, not by bytes); a cloud of more than 65535 points cannot be counted in 16 bits and goes through the
-// work list `li_todo` to the full-width launch (small fixed grid, normally empty).
-// The steps, each by every thread of the workgroup: li_reset | barrier | li_count for every point | barrier | li_tables | barrier |
-// li_scatter.  k_line_index reads the cloud for the count; k_compact_index counts while compact_scan writes the cloud.
-struct LiLds { int *cnt, *wsum, *emin, *emax; };      // counters (dynamic LDS), the waves' sums, the lines' elevation bounds (66 each)
-
-// counter `key`: add one, return the old value
-template <bool kHalf>
-__device__ __forceinline__ int li_bump(const LiLds &L, int key)
-{
-    if (kHalf) { const int sh = (key & 1) * 16; return (int)((atomicAdd((unsigned int *)L.cnt + (key >> 1), 1u << sh) >> sh) & 0xffffu); }
-    return atomicAdd(&L.cnt[key], 1);
-}
-
-template <bool kHalf>
-__device__ __forceinline__ void li_reset(const LiLds &L)
-{
-    const int tid = threadIdx.x;
-    constexpr int kWords = kHalf ? kLineKeys / 2 : kLineKeys;
-    static_assert(kLineKeys % 2 == 0, "two 16-bit counters per LDS word");
-    for (int i = tid; i < kWords; i += kLiT) L.cnt[i] = 0;
-    if (tid < 66) { L.emin[tid] = INT_MAX; L.emax[tid] = INT_MIN; }
-}
-
-// one point per lane of a WHOLE wave (ok = false: a lane without one).  A wave holds 64 consecutive points, which nearly always
-// share one scan line: their elevation bounds are reduced in the wave (DPP) and leave as ONE pair of LDS atomics
-template <bool kHalf>
-__device__ __forceinline__ void li_count(const LiLds &L, bool ok, float x, float y, float z, float w)
-{
-    const int ln = line_of(w);
-    if (ok) (void)li_bump<kHalf>(L, lb_key(az_bin(x, y), ln));
-    const unsigned long long act = __ballot(ok);
-    if (act == 0ull) return;
-    const int eo = f2ord(elev_of(x, y, z));
-    const int ln0 = __shfl(ln, __ffsll((long long)act) - 1);
-    if (__ballot(ok && ln != ln0) == 0ull) {
-        const unsigned int lo = wave_min_u32_uniform(ok ? (unsigned int)eo ^ 0x80000000u : ~0u);
-        const unsigned int hi = wave_max_u32_uniform(ok ? (unsigned int)eo ^ 0x80000000u : 0u);
-        if ((threadIdx.x & 63) == 0) { atomicMin(&L.emin[ln0], (int)(lo ^ 0x80000000u)); atomicMax(&L.emax[ln0], (int)(hi ^ 0x80000000u)); }
-    } else if (ok) {
-        atomicMin(&L.emin[ln], eo);
-        atomicMax(&L.emax[ln], eo);
-    }
-}
-
-// the elevation rows and the start table of the counted cloud; the counters become the buckets' write cursors.  Holds barriers.
-template <bool kHalf>
-__device__ __forceinline__ void li_tables(const BatchView &b, const LiLds &L, int s, bool surf, int n)
-{
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    int *table = b.lb_start + (size_t)(s * 2 + (surf ? 1 : 0)) * (kLineKeys + 1);
-    unsigned int *s_c32 = (unsigned int *)L.cnt;
-    // per-line elevation bounds of the cloud (empty line: lo > hi), used by the searches to bound the lines a ball can meet:
-    // (lo, hi, A = min of lo over lines <= v, B = max of hi over lines >= v).  A and B are monotone (non-increasing in v) whatever
-    // the sensor, so the lines that can meet an elevation window [a, b] lie between the first v with A_v <= b and the last with B_v >= a
-    if (tid < 66) {
-        float4 *el = b.lb_elev + (size_t)(s * 2 + (surf ? 1 : 0)) * 66;
-        float A = 1e30f, B = -1e30f;
-        for (int v = 0; v <= tid; v++) if (L.emin[v] != INT_MAX) A = fminf(A, ord2f(L.emin[v]));
-        for (int v = tid; v < 66; v++) if (L.emin[v] != INT_MAX) B = fmaxf(B, ord2f(L.emax[v]));
-        el[tid] = L.emin[tid] == INT_MAX ? make_float4(1e30f, -1e30f, A, B) : make_float4(ord2f(L.emin[tid]), ord2f(L.emax[tid]), A, B);
-    }
-    // exclusive prefix over the kLineKeys counters: kPer consecutive counters per thread (kPer even: whole LDS words; last threads padded)
-    constexpr int kPer = (((kLineKeys + kLiT - 1) / kLiT) + 1) & ~1;
-    auto get = [&](int idx) -> int { return kHalf ? (int)((s_c32[idx >> 1] >> ((idx & 1) * 16)) & 0xffffu) : L.cnt[idx]; };
-    int local = 0;
-    for (int i = 0; i < kPer; i++) { const int idx = tid * kPer + i; if (idx < kLineKeys) local += get(idx); }
-    const int incl = wave_scan_incl(local);
-    if (lane == 63) L.wsum[wave] = incl;
-    __syncthreads();
-    int run = incl - local;
-    for (int w = 0; w < wave; w++) run += L.wsum[w];
-    if (kHalf) {
-        // a thread owns whole words (kPer is even): no other thread touches them here.  Cursors are < n <= 65535.
-        for (int i = 0; i < kPer; i += 2) {
-            const int idx = tid * kPer + i;
-            if (idx < kLineKeys) {
-                const unsigned int wv = s_c32[idx >> 1];
-                const int c0 = (int)(wv & 0xffffu), c1 = (int)(wv >> 16);
-                s_c32[idx >> 1] = (unsigned int)run | ((unsigned int)(run + c0) << 16);
-                run += c0 + c1;
-            }
-        }
-        // the table leaves LDS in rows (a wave writes 512 consecutive bytes; a thread's own counters lie 104 B apart): the cursors are the
-        // buckets' starts until the scatter moves them
-        __syncthreads();
-        for (int w = tid; w < kLineKeys / 2; w += kLiT) { const unsigned int wv = s_c32[w]; table[2 * w] = (int)(wv & 0xffffu); table[2 * w + 1] = (int)(wv >> 16); }
-    } else {
-        for (int i = 0; i < kPer; i++) {
-            const int idx = tid * kPer + i;
-            if (idx < kLineKeys) { const int cnt = L.cnt[idx]; L.cnt[idx] = run; table[idx] = run; run += cnt; }
-        }
-    }
-    if (tid == kLiT - 1) table[kLineKeys] = n;
-}
-
-// every point of the cloud to the next free place of its bucket
-template <bool kHalf>
-__device__ __forceinline__ void li_scatter(const BatchView &b, const LiLds &L, int s, bool surf, int n)
-{
-    const int tid = threadIdx.x;
-    const float4 *src = surf ? b.less_flat + b.off[s] : b.less_sharp + (size_t)s * kMaxLessSharp;
-    float4 *dst = surf ? b.lbs_pts + b.off[s] : b.lbc_pts + (size_t)s * kMaxLessSharp;
-    for (int i0 = tid; i0 < n; i0 += 4 * kLiT) {
-        float4 p[4];
-#pragma unroll
-        for (int q = 0; q < 4; q++) { const int i = i0 + kLiT * q; p[q] = src[i < n ? i : 0]; }      // unconditional (clamped): really four in flight
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-            const int i = i0 + kLiT * q;
-            if (i < n) {
-                const int ln = line_of(p[q].w);
-                const int d = li_bump<kHalf>(L, lb_key(az_bin(p[q].x, p[q].y), ln));
-                dst[d] = make_float4(p[q].x, p[q].y, p[q].z, __int_as_float((i << 7) | ln));
-            }
-        }
-    }
-}
-
-// the whole of it for a cloud that lies in memory (k_line_index)
-template <bool kHalf>
-__device__ __forceinline__ void line_index_cloud(const BatchView &b, int s, bool surf, int n, const LiLds &L)
-{
-    const int tid = threadIdx.x;
-    const float4 *src = surf ? b.less_flat + b.off[s] : b.less_sharp + (size_t)s * kMaxLessSharp;
-    li_reset<kHalf>(L);
-    __syncthreads();
-    // four points per thread and round, their loads in flight together
-    for (int base = 0; base < n; base += 4 * kLiT) {      // uniform trip count: the wave reductions need every lane
-        float4 p[4];
-#pragma unroll
-        for (int q = 0; q < 4; q++) { const int i = base + tid + kLiT * q; p[q] = src[i < n ? i : 0]; }      // unconditional (clamped): really four in flight
-#pragma unroll
-        for (int q = 0; q < 4; q++) li_count<kHalf>(L, base + tid + kLiT * q < n, p[q].x, p[q].y, p[q].z, p[q].w);
-    }
-    __syncthreads();
-    li_tables<kHalf>(b, L, s, surf, n);
-    __syncthreads();
-    li_scatter<kHalf>(b, L, s, surf, n);
-}
-
-// from_list = 0: grid (n_scans, 2), 16-bit counters, clouds of more than 65535 points deferred; 1: kLiBigGrid workgroups over the list
-template <bool kHalf>
-__global__ __launch_bounds__(kLiT) void k_line_index(BatchView b)
-{
-    extern __shared__ __align__(16) int s_cnt[];      // points per (line, bin); after the prefix: write cursor of the bucket
-    __shared__ int s_wsum[kLiT / 64], s_emin[66], s_emax[66];
-    const LiLds L = { s_cnt, s_wsum, s_emin, s_emax };
-    if (kHalf) {
-        const int s = b.scan0 + blockIdx.x;
-        const bool surf = blockIdx.y == 1;
-        if (b.feat_n[s * 4 + (surf ? 3 : 1)] > 65535) {
-            if (threadIdx.x == 0) b.li_todo[1 + atomicAdd(&b.li_todo[0], 1)] = s * 2 + (surf ? 1 : 0);
-            return;
-        }
-        line_index_cloud<true>(b, s, surf, b.feat_n[s * 4 + (surf ? 3 : 1)], L);
-    } else {
-        const int n_todo = b.li_todo[0];
-        for (int k = blockIdx.x; k < n_todo; k += gridDim.x) {
-            const int e = b.li_todo[1 + k];
-            __syncthreads();                            // the previous cloud's scatter is done with the counters
-            line_index_cloud<false>(b, e >> 1, (e & 1) != 0, b.feat_n[(e >> 1) * 4 + ((e & 1) ? 3 : 1)], L);
-        }
-    }
-}
-
-// k_compact and k_line_index<true> as ONE kernel (round 5, VERDICT r4 #2a): a workgroup compacts its scan's feature clouds and indexes the two "last"
-// clouds right away.  Round 5 measured the fusion as neutral (1.90 + 2.02 -> 3.92 ms per pass) and put that down to traffic; round 8 found the cause in
-// the kernel's resources: 91 VGPRs, so ONE 1024-thread workgroup per CU (the stand-alone kernels ran two), and the re-reads of the clouds it had just
-// written were not served by L2 (1.25 MB fetched per scan for 0.55 MB of clouds).  Since round 8 (profiles/r8/NOTES.md):
-//   * the copy loops of compact_scan count the points per (line, bin) and feed the elevation bounds while they hold them (CompactIndexFeed): the
-//     separate count pass over the written cloud is gone, 0.94 MB fetched per scan;
-//   * the phases are separate functions over LDS state with nothing carried between them in registers: 52 VGPRs, 48 B of scratch, 57.5 KB of LDS,
-//     TWO workgroups per CU (the launch bound pins 8 waves per SIMD; the occupancy query of -DLMONO_TILE_PROF builds reports it);
-//   * the start table leaves LDS in rows (li_tables).
-// 3.97 -> 3.10 ms per pass.  The 16-bit counters serve one cloud after the other; a cloud of more than 65535 points is copied plainly and goes to the
-// full-width launch's list.
-#ifndef LMONO_FUSE_COMPACT_INDEX
-#define LMONO_FUSE_COMPACT_INDEX 1
-#endif
-// compact_scan's feed: the points are counted while the copy loop holds them; tables and scatter follow the loop
-struct CompactIndexFeed {
-    static constexpr bool kOn = true;
-    const BatchView &b;
-    LiLds L;
-    int s;
-    bool on;                       // false: a cloud of more than 65535 points, copied plainly and listed for the full-width launch
-    __device__ __forceinline__ void reset(int cld, int n)
-    {
-        on = n <= 65535;
-        if (on) li_reset<true>(L);
-        else if (threadIdx.x == 0) b.li_todo[1 + atomicAdd(&b.li_todo[0], 1)] = s * 2 + cld;
-    }
-    __device__ __forceinline__ void point(bool ok, const float4 &p) { if (on) li_count<true>(L, ok, p.x, p.y, p.z, p.w); }
-    __device__ __forceinline__ void finish(int cld, int n)
-    {
-        if (!on) return;
-        __syncthreads();
-        li_tables<true>(b, L, s, cld != 0, n);
-        // this workgroup's own stores (the cloud) are read back by the scatter: they are out of the vector unit before anybody loads
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-        __syncthreads();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-        li_scatter<true>(b, L, s, cld != 0, n);
-    }
-};
-
-__global__ __launch_bounds__(kLiT, 8) void k_compact_index(BatchView b)
-{
-    extern __shared__ __align__(16) int s_cnt[];
-    __shared__ int s_wsum[kLiT / 64], s_emin[66], s_emax[66];
-    CompactIndexFeed feed = { b, { s_cnt, s_wsum, s_emin, s_emax }, b.scan0 + (int)blockIdx.x, false };
-    compact_scan<kLiT>(b, feed.s, feed);
 }
 
 // Slack of an azimuth arc in bins.  A point within r of the feature differs from it by at most asin(r / rho) in azimuth; both bins come

@@ -2,6 +2,7 @@
 // fixed order, and the ABI of each subsystem (*_abi.hip, at the end) behind lmono_ctx, so that one `hipcc -shared` produces liblmono_hip.so.
 #include "line_index.hip"
 #include "frontend.hip"
+#include "trust_region.hpp"
 #include "odometry.hip"
 #include "corr_flat.hip"
 #include "mapping.hip"

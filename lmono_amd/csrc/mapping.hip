@@ -11,6 +11,8 @@
 //   k_map_solve    one workgroup per stream: ceres::Solve restated (trust-region LM, <= 4 iterations, Huber 0.1) over
 //                  the records (LidarEdgeFactor / LidarPlaneNormFactor, closed-form Jacobians)
 // The map bookkeeping (cube array, voxel re-filtering) is not part of this file yet.
+// Included behind odometry.hip and trust_region.hpp.  From the first the search here takes cell_key, hash_key, kInvCell, kGroup, group_min_u64 and
+// quat_rotate; from the second the solve takes its whole core (listed above map_row).
 #include "batch.hpp"
 
 namespace lmono {
@@ -464,8 +466,11 @@ __global__ __launch_bounds__(64) void k_map_factor(const MapStream *streams, int
 
 // ---- solve -----------------------------------------------------------------------------------------------------------
 // Same structure as k_lm_solve (odometry.hip): straight-line edge / plane-norm blocks over a per-sweep rotation matrix, the rotation
-// part of a Jacobian row as 2 (Rv x d), the accepted / candidate sums in LDS, packed in-place Cholesky.  No FMA contraction here: the
-// tests compare this kernel's LM iteration counts with the oracle's, and a contracted trace can stop one iteration apart on a knife edge.
+// part of a Jacobian row as 2 (Rv x d), the accepted / candidate sums in LDS, and the solver core of trust_region.hpp (LmAcc, accumulate_row, huber, sym6,
+// chol_solve6_packed, manifold_plus, norm7, TrustRegion); from odometry.hip itself this file takes nothing for the solve.  Only accumulate_row and
+// chol_solve6_packed contract to FMA (their own pragmas).  The rest of this evaluation (map_row, map_eval_block, map_evaluate) and all of TrustRegion are
+// compiled uncontracted, here and in k_lm_solve: the tests compare this kernel's LM iteration counts with the oracle's, and a trace contracted further
+// can stop one iteration apart on a knife edge.
 __device__ __forceinline__ void map_row(LmAcc &acc, double d0, double d1, double d2, double rvx, double rvy, double rvz, double res, double sr)
 {
     double J[6];
@@ -624,8 +629,8 @@ __device__ __forceinline__ void map_evaluate(const MapRec *rec, int n_edge, int 
     __syncthreads();
 }
 
-// One kMsT-thread workgroup per stream (a frame has ~8 k residual blocks); the trust-region control flow runs redundantly
-// in every thread on the block-reduced sums in LDS, exactly like k_lm_solve.
+// One kMsT-thread workgroup per stream (a frame has ~8 k residual blocks); the trust-region control flow is k_lm_solve's (TrustRegion, trust_region.hpp)
+// on the block-reduced sums in LDS, run by wave 0.
 // grid: ceil(n_streams / 8) x 8 K blocks; block b = 8 K g + 8 rank + j works on stream 8 g + j: the K workgroups of a stream are 8 blocks apart
 __global__ __launch_bounds__(kMsT) void k_map_solve(const MapStream *streams, int n_streams, int K, int outer)
 {
@@ -642,22 +647,17 @@ __global__ __launch_bounds__(kMsT) void k_map_solve(const MapStream *streams, in
     const int n_used = S.stats[outer] + S.stats[2 + outer];
     double x[7];
     for (int i = 0; i < 7; i++) x[i] = S.x[i];
-    const int max_iter = 4;
-    const double function_tol = 1e-6, gradient_tol = 1e-10, parameter_tol = 1e-8;
-    const double min_rel_decrease = 1e-3, min_diag = 1e-6, max_diag = 1e32, max_radius = 1e16, min_radius = 1e-32;
-    double radius = 1e4, decrease_factor = 2.0;
-    bool reuse_diagonal = false;
-    int invalid_steps = 0, iter = 0;
+    TrustRegion<false> tr(4);           // ceres max_num_iterations of laserMapping; the damping term divides by the radius as the oracle does
     // Round 5: the trust-region arithmetic between two evaluations (~1.5 k dependent fp64 instructions) runs on wave 0 alone -- every wave used to repeat it,
     // two waves per SIMD taking turns at the issue port -- and hands the next candidate to the workgroup through LDS: ctl 0 = evaluate it with its Jacobian
-    // (the next linearisation when it is accepted), 1 = its cost only (the last iteration), 2 = finished.  Same arithmetic, same order of decisions.
+    // (the next linearisation when it is accepted), 1 = its cost only (the last iteration), 2 = finished (TrustRegion::propose).
     __shared__ double s_xc[8];
     __shared__ int s_ctl;
     if (n_used > 0) {
         map_evaluate<true>(S.rec, n_edge, nq, x, s_red, s_sum, cl);
         const bool w0 = tid < 64;
-        bool first = true, last = false;
-        double x_cost = 0.0, x_norm = 0.0, model_change = 0.0, scale[6] = { 0, 0, 0, 0, 0, 0 }, diag[6] = { 0, 0, 0, 0, 0, 0 }, cand[7] = { 0, 0, 0, 0, 0, 0, 0 };
+        bool first = true;
+        double cand[7] = { 0, 0, 0, 0, 0, 0, 0 };
         for (;;) {
             if (w0) {
                 auto take_linearisation = [&]() {          // s_cur <- s_sum inside the wave (its LDS operations execute in order)
@@ -668,85 +668,13 @@ __global__ __launch_bounds__(kMsT) void k_map_solve(const MapStream *streams, in
                     __builtin_amdgcn_wave_barrier();
                     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
                 };
-                bool proceed = true;
+                bool proceed;
                 if (first) {
                     take_linearisation();
-                    x_cost = s_cur[27];
-                    double gmax = 0.0;
-                    for (int i = 0; i < 6; i++) gmax = fmax(gmax, fabs(s_cur[21 + i]));
-                    if (gmax > gradient_tol) {
-                        x_norm = norm7(x);
-                        for (int i = 0; i < 6; i++) scale[i] = 1.0 / (1.0 + sqrt(s_cur[sym6(i, i)]));
-                    } else proceed = false;
-                } else {
-                    const double cand_cost = s_sum[27];
-                    double sn = 0.0;
-                    for (int i = 0; i < 7; i++) sn += (x[i] - cand[i]) * (x[i] - cand[i]);
-                    sn = sqrt(sn);
-                    if (sn <= parameter_tol * (x_norm + parameter_tol)) proceed = false;
-                    else if (fabs(x_cost - cand_cost) <= function_tol * x_cost) proceed = false;
-                    else {
-                        const double rel = (x_cost - cand_cost) / model_change;
-                        if (rel > min_rel_decrease) {
-                            for (int i = 0; i < 7; i++) x[i] = cand[i];
-                            if (last) proceed = false;
-                            else {
-                                x_norm = norm7(x);
-                                x_cost = cand_cost;
-                                take_linearisation();
-                                const double tt = 2.0 * rel - 1.0;
-                                double den = 1.0 - tt * tt * tt;
-                                if (den < 1.0 / 3.0) den = 1.0 / 3.0;
-                                radius = radius / den;
-                                if (radius > max_radius) radius = max_radius;
-                                decrease_factor = 2.0; reuse_diagonal = false;
-                                double gmax = 0.0;
-                                for (int i = 0; i < 6; i++) gmax = fmax(gmax, fabs(s_cur[21 + i]));
-                                if (gmax <= gradient_tol) proceed = false;
-                            }
-                        } else {
-                            radius = radius / decrease_factor; decrease_factor *= 2.0; reuse_diagonal = true;
-                        }
-                        if (proceed && radius <= min_radius) proceed = false;
-                    }
-                }
-                int ctl = 2;
-                while (proceed) {
-                    if (iter >= max_iter) break;
-                    iter++;
-                    double gs[6], A[21], stepv[6];
-#pragma unroll
-                    for (int i = 0; i < 6; i++) {
-                        gs[i] = s_cur[21 + i] * scale[i];
-#pragma unroll
-                        for (int j = 0; j <= i; j++) A[i * (i + 1) / 2 + j] = s_cur[sym6(i, j)] * scale[i] * scale[j];
-                    }
-                    if (!reuse_diagonal)
-                        for (int i = 0; i < 6; i++) { double d = A[i * (i + 1) / 2 + i]; d = d < min_diag ? min_diag : d; d = d > max_diag ? max_diag : d; diag[i] = d; }
-                    for (int i = 0; i < 6; i++) A[i * (i + 1) / 2 + i] += diag[i] / radius;
-                    bool ok = chol_solve6_packed(A, gs, stepv);
-                    for (int i = 0; i < 6; i++) if (!isfinite(stepv[i])) ok = false;
-                    model_change = 0.0;
-                    if (ok) {
-                        for (int i = 0; i < 6; i++) stepv[i] = -stepv[i];
-                        double dg = 0.0, dHd = 0.0;
-                        for (int i = 0; i < 6; i++) { dg += stepv[i] * gs[i]; for (int j = 0; j < 6; j++) dHd += stepv[i] * (s_cur[sym6(i, j)] * scale[i] * scale[j]) * stepv[j]; }
-                        model_change = -(dg + 0.5 * dHd);
-                    }
-                    if (!ok || !(model_change > 0.0)) {
-                        if (++invalid_steps >= 5) break;
-                        radius *= 0.5; reuse_diagonal = true;
-                        continue;
-                    }
-                    invalid_steps = 0;
-                    double delta[6];
-                    for (int i = 0; i < 6; i++) delta[i] = stepv[i] * scale[i];
-                    manifold_plus(x, delta, cand);
-                    // candidate evaluated with its Jacobian (reused as the next linearisation); the last iteration needs the cost only
-                    last = iter == max_iter;
-                    ctl = last ? 1 : 0;
-                    break;
-                }
+                    proceed = tr.begin(s_cur, x);
+                } else
+                    proceed = tr.judge(s_sum, s_cur, x, cand, take_linearisation);
+                const int ctl = proceed ? tr.propose(s_cur, x, cand) : 2;
                 if (tid == 0) { s_ctl = ctl; for (int i = 0; i < 7; i++) s_xc[i] = cand[i]; }
             }
             __syncthreads();
@@ -762,7 +690,7 @@ __global__ __launch_bounds__(kMsT) void k_map_solve(const MapStream *streams, in
     __syncthreads();
     if (tid == 0 && cl.rank == 0) {
         for (int i = 0; i < 7; i++) S.x[i] = x[i];
-        S.stats[4 + outer] = iter;
+        S.stats[4 + outer] = tr.iter;
     }
 }
 

@@ -875,7 +875,7 @@ __global__ __launch_bounds__(256, 8) void k_correspond(BatchView b, OdomView o, 
 #endif // LMONO_DIAG_SEARCH
 
 // The same search for the feature points of a device work list ([0] = count, then chain << 12 | feature index): the points the
-// LDS tile search (corr_tile.hip) defers.  Phase 1 serves them with 32-lane groups; phase 2 (scan pairs flagged irregular / dense:
+// LDS tile search (k_corr_flat, corr_flat.hip) defers.  Phase 1 serves them with 32-lane groups; phase 2 (scan pairs flagged irregular / dense:
 // rare) with the whole-wave array-order walk.  Fixed grid, items strided over it.
 __global__ __launch_bounds__(256, 4) void k_correspond_list(BatchView b, OdomView o, int step, int outer, const unsigned int *wl, unsigned long long *stats)
 {
@@ -906,47 +906,10 @@ __global__ __launch_bounds__(256, 4) void k_correspond_list(BatchView b, OdomVie
 // plane r = (lp - j) . n (1 row).  d r / d lp is constant: [b-a]_x / |a-b| and n^T.
 constexpr int kLmT = 256;   // threads per chain in k_lm_solve (512 measured slower, with and without register spills: reductions and the serial trust-region part dominate)
 constexpr int kLmW = kLmT / 64;
-struct LmAcc { double H[21]; double g[6]; double cost; };
-
-// The LM solve below (accumulate_row .. k_lm_solve) allows contraction to FMA: its parity bar is a tolerance (1e-9 against the oracle's
-// loop), and with -ffp-contract=off every a * b + c of the 6 x 6 normal equations is two dependent instructions on the one wave per
-// SIMD that runs a chain's solve.  The de-skew transform of the SEARCH (quat_rotate in the correspondence kernels) stays uncontracted:
-// its float result must equal the oracle's bit for bit.
-__device__ __forceinline__ void quat_rotate_fma(const double *q, double vx, double vy, double vz, double &ox, double &oy, double &oz)
-{
-#pragma clang fp contract(fast)
-    const double ux = q[0], uy = q[1], uz = q[2], w = q[3];
-    const double uvx = 2.0 * (uy * vz - uz * vy);
-    const double uvy = 2.0 * (uz * vx - ux * vz);
-    const double uvz = 2.0 * (ux * vy - uy * vx);
-    ox = vx + w * uvx + (uy * uvz - uz * uvy);
-    oy = vy + w * uvy + (uz * uvx - ux * uvz);
-    oz = vz + w * uvz + (ux * uvy - uy * uvx);
-}
-
-__device__ __forceinline__ void accumulate_row(LmAcc &a, const double *J, double r)
-{
-#pragma clang fp contract(fast)
-    int t = 0;
-#pragma unroll
-    for (int i = 0; i < 6; i++) {
-        a.g[i] += J[i] * r;
-#pragma unroll
-        for (int j = i; j < 6; j++) a.H[t++] += J[i] * J[j];
-    }
-}
-
-__device__ __forceinline__ void huber(double s, double &rho0, double &rho1)
-{
-    const double a = 0.1, bb = 0.1 * 0.1;
-    if (s > bb) {
-        const double r = sqrt(s);
-        rho0 = 2.0 * a * r - bb;
-        rho1 = a / r;
-        if (rho1 < DBL_MIN) rho1 = DBL_MIN;
-    } else { rho0 = s; rho1 = 1.0; }
-}
-
+// The LM solve below (lm_row .. k_lm_solve, and accumulate_row / chol_solve6_packed of trust_region.hpp) allows contraction to FMA: its parity
+// bar is a tolerance (1e-9 against the oracle's loop), and with -ffp-contract=off every a * b + c of the 6 x 6 normal equations is two
+// dependent instructions on the one wave per SIMD that runs a chain's solve.  The de-skew transform of the SEARCH (quat_rotate in the
+// correspondence kernels) stays uncontracted: its float result must equal the oracle's bit for bit.
 // A staged residual block (64 B in LDS, planes of 16 B): (cp, kind) as float4, then six doubles that do not depend on the pose and
 // are computed once per launch instead of once per evaluation (up to nine per launch):
 //   edge   a, e^ = (a - b) / |a - b|:          r = (lp - a) x e^   [= ((lp - a) x (lp - b)) / |a - b| since (lp - a) x (lp - a) = 0],  d r / d lp = -[e^]_x
@@ -1071,206 +1034,22 @@ __device__ __forceinline__ void evaluate_block(const float4 *srec, int n_edge, i
     __syncthreads();
 }
 
-// entry (i, j) of a symmetric 6 x 6 matrix stored as its upper triangle row by row (the order of accumulate_row)
-__device__ __forceinline__ int sym6(int i, int j) { const int a = i < j ? i : j, b = i < j ? j : i; return a * 6 - a * (a - 1) / 2 + (b - a); }
-
-__device__ __forceinline__ bool chol_solve6(const double *A, const double *bvec, double *xo)
-{
-    double L[36];
-    for (int i = 0; i < 36; i++) L[i] = 0.0;
-    for (int i = 0; i < 6; i++)
-        for (int j = 0; j <= i; j++) {
-            double s = A[i * 6 + j];
-            for (int k = 0; k < j; k++) s -= L[i * 6 + k] * L[j * 6 + k];
-            if (i == j) { if (!(s > 0.0)) return false; L[i * 6 + i] = sqrt(s); }
-            else L[i * 6 + j] = s / L[j * 6 + j];
-        }
-    double y[6];
-    for (int i = 0; i < 6; i++) { double s = bvec[i]; for (int k = 0; k < i; k++) s -= L[i * 6 + k] * y[k]; y[i] = s / L[i * 6 + i]; }
-    for (int i = 5; i >= 0; i--) { double s = y[i]; for (int k = i + 1; k < 6; k++) s -= L[k * 6 + i] * xo[k]; xo[i] = s / L[i * 6 + i]; }
-    return true;
-}
-
-// The same factorisation and substitutions on the LOWER triangle stored row by row (entry (i, j), j <= i, at i (i + 1) / 2 + j),
-// in place: 21 doubles instead of two 6 x 6 arrays, same operations in the same order.
-// Round 4: the 27 divisions by the factor's diagonal are multiplications by its six reciprocals (an fp64 division is ~35 instructions on the one wave
-// per SIMD that runs a chain's solve, and every thread of the workgroup runs this redundantly four times per launch: ~24 k of a launch's ~126 k cycles).
-// Same factorisation to rounding; the solve's parity bar is 1e-9 against the oracle's loop.
-__device__ __forceinline__ bool chol_solve6_packed(double *L, const double *bvec, double *xo)
-{
-#pragma clang fp contract(fast)
-    double inv[6];
-#pragma unroll
-    for (int i = 0; i < 6; i++)
-#pragma unroll
-        for (int j = 0; j <= i; j++) {
-            double s = L[i * (i + 1) / 2 + j];
-#pragma unroll
-            for (int k = 0; k < j; k++) s -= L[i * (i + 1) / 2 + k] * L[j * (j + 1) / 2 + k];
-            if (i == j) { if (!(s > 0.0)) return false; const double d = sqrt(s); L[i * (i + 1) / 2 + i] = d; inv[i] = 1.0 / d; }
-            else L[i * (i + 1) / 2 + j] = s * inv[j];
-        }
-    double y[6];
-#pragma unroll
-    for (int i = 0; i < 6; i++) {
-        double s = bvec[i];
-#pragma unroll
-        for (int k = 0; k < i; k++) s -= L[i * (i + 1) / 2 + k] * y[k];
-        y[i] = s * inv[i];
-    }
-#pragma unroll
-    for (int i = 5; i >= 0; i--) {
-        double s = y[i];
-#pragma unroll
-        for (int k = i + 1; k < 6; k++) s -= L[k * (k + 1) / 2 + i] * xo[k];
-        xo[i] = s * inv[i];
-    }
-    return true;
-}
-
-__device__ __forceinline__ void manifold_plus(const double *x, const double *d, double *o)
-{
-    const double nd = sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
-    if (nd > 0.0) {
-        const double sc = sin(nd) / nd;
-        const double ax = sc * d[0], ay = sc * d[1], az = sc * d[2], aw = cos(nd);
-        const double bx = x[0], by = x[1], bz = x[2], bw = x[3];
-        o[3] = aw * bw - ax * bx - ay * by - az * bz;
-        o[0] = aw * bx + ax * bw + ay * bz - az * by;
-        o[1] = aw * by + ay * bw + az * bx - ax * bz;
-        o[2] = aw * bz + az * bw + ax * by - ay * bx;
-    } else { o[0] = x[0]; o[1] = x[1]; o[2] = x[2]; o[3] = x[3]; }
-    o[4] = x[4] + d[3]; o[5] = x[5] + d[4]; o[6] = x[6] + d[5];
-}
-
-__device__ __forceinline__ double norm7(const double *x)
-{
-    double s = 0.0;
-    for (int i = 0; i < 7; i++) s += x[i] * x[i];
-    return sqrt(s);
-}
-
-__device__ __forceinline__ void unpack_sym(const double *Hu, double *H)
-{
-    int t = 0;
-    for (int i = 0; i < 6; i++)
-        for (int j = i; j < 6; j++) { H[i * 6 + j] = Hu[t]; H[j * 6 + i] = Hu[t]; t++; }
-}
-
 constexpr int kLmRecLds = 4 * kMaxQueries * 16;   // the chain's records in LDS
 #ifndef LMONO_CF_T
 #define LMONO_CF_T 128
 #endif
 constexpr int kThinBlocks = kMaxQueries / LMONO_CF_T;     // = kCfBlocks of corr_flat.hip: feature qi belongs to workgroup qi % kThinBlocks
 
-// One kLmT-thread workgroup per chain.  Every thread runs the (uniform) trust-region control flow redundantly on the
-// block-reduced sums; residual blocks come from the 64-B records written by k_correspond.
-// k_lm_solve's evaluation: the chain's records staged in LDS
-struct LmRecEval {
-    const float4 *srec; int n_edge, nq; double (*s_red)[28]; double *s_sum;
-    template <bool kJac> __device__ __forceinline__ void run(const double *x) const { evaluate_block<kJac>(srec, n_edge, nq, x, s_red, s_sum); }
-};
-
-// Ceres' trust-region loop (Levenberg-Marquardt, DENSE_QR restated on the 6 x 6 normal equations, <= 4 iterations) over
-// an evaluation functor: ev.run<kJac>(pose) leaves the sums H (21), g (6), cost in s_sum (with the workgroup barriers that takes).  On
-// entry s_sum holds the linearisation at x; on return x is the accepted pose, the same in every thread.  Shared by k_lm_solve
-// (records in LDS, 256 threads) and k_odom_chain (records in registers, 1024 threads).
-template <class Eval>
-__device__ __forceinline__ void lm_trust_region(const Eval &ev, double *x, double *s_cur, double *s_sum, int n_used, int &iter)
-{
-    const int tid = threadIdx.x;
 #ifndef LMONO_LM_MAX_ITER
 #define LMONO_LM_MAX_ITER 4          // ceres max_num_iterations of laserOdometry (any other value is a TIMING experiment: results change)
 #endif
-    const int max_iter = LMONO_LM_MAX_ITER;
-    const double function_tol = 1e-6, gradient_tol = 1e-10, parameter_tol = 1e-8;
-    const double min_rel_decrease = 1e-3, min_diag = 1e-6, max_diag = 1e32, max_radius = 1e16, min_radius = 1e-32;
-    double radius = 1e4, decrease_factor = 2.0;
-    bool reuse_diagonal = false;
-    int invalid_steps = 0;
-    iter = 0;
-    // The accepted linearisation (H, g, cost) lives in LDS (s_cur), a candidate's in s_sum: every thread runs the uniform trust-region
-    // arithmetic on the same LDS numbers, and only the scaled, damped system of the current iteration is ever in registers -- with
-    // H, Hs, a second matrix for the factor and two accumulator sets per thread the kernel needed ~350 registers and could not run
-    // two waves per SIMD.
-    if (tid < 28) s_cur[tid] = s_sum[tid];
-    __syncthreads();
-    double x_cost = s_cur[27];
-    double scale[6], diag[6];
-    double gmax = 0.0;
-    for (int i = 0; i < 6; i++) gmax = fmax(gmax, fabs(s_cur[21 + i]));
-    if (n_used > 0 && gmax > gradient_tol) {
-        double x_norm = norm7(x);
-        for (int i = 0; i < 6; i++) scale[i] = 1.0 / (1.0 + sqrt(s_cur[sym6(i, i)]));
-        while (iter < max_iter) {
-            iter++;
-            double gs[6], A[21], stepv[6];
-            // lower triangle of A = Hs = H scale_i scale_j, then + diag / radius on the diagonal
-#pragma unroll
-            for (int i = 0; i < 6; i++) {
-                gs[i] = s_cur[21 + i] * scale[i];
-#pragma unroll
-                for (int j = 0; j <= i; j++) A[i * (i + 1) / 2 + j] = s_cur[sym6(i, j)] * scale[i] * scale[j];
-            }
-            if (!reuse_diagonal)
-                for (int i = 0; i < 6; i++) { double d = A[i * (i + 1) / 2 + i]; d = d < min_diag ? min_diag : d; d = d > max_diag ? max_diag : d; diag[i] = d; }
-            { const double ir = 1.0 / radius; for (int i = 0; i < 6; i++) A[i * (i + 1) / 2 + i] += diag[i] * ir; }
-            bool ok = chol_solve6_packed(A, gs, stepv);
-            for (int i = 0; i < 6; i++) if (!isfinite(stepv[i])) ok = false;
-            double model_change = 0.0;
-            if (ok) {
-                for (int i = 0; i < 6; i++) stepv[i] = -stepv[i];
-                double dg = 0.0, dHd = 0.0;
-                for (int i = 0; i < 6; i++) { dg += stepv[i] * gs[i]; for (int j = 0; j < 6; j++) dHd += stepv[i] * (s_cur[sym6(i, j)] * scale[i] * scale[j]) * stepv[j]; }
-                model_change = -(dg + 0.5 * dHd);
-            }
-            if (!ok || !(model_change > 0.0)) {
-                if (++invalid_steps >= 5) break;
-                radius *= 0.5; reuse_diagonal = true;
-                continue;
-            }
-            invalid_steps = 0;
-            double delta[6], cand[7];
-            for (int i = 0; i < 6; i++) delta[i] = stepv[i] * scale[i];
-            manifold_plus(x, delta, cand);
-            // The candidate is evaluated WITH its Jacobian (it is accepted almost always, and then this is the linearisation of
-            // the next iteration -- the same numbers a separate pass would give).  The last iteration only needs the cost, but a
-            // second, cost-only copy of the sweep inside this loop costs the kernel its second wave per SIMD (81 spilled registers).
-            const bool last = iter == max_iter;
-            if (last) ev.template run<false>(cand);
-            else ev.template run<true>(cand);
-            const double cand_cost = s_sum[27];
-            double sn = 0.0;
-            for (int i = 0; i < 7; i++) sn += (x[i] - cand[i]) * (x[i] - cand[i]);
-            sn = sqrt(sn);
-            if (sn <= parameter_tol * (x_norm + parameter_tol)) break;
-            if (fabs(x_cost - cand_cost) <= function_tol * x_cost) break;
-            const double rel = (x_cost - cand_cost) / model_change;
-            if (rel > min_rel_decrease) {
-                for (int i = 0; i < 7; i++) x[i] = cand[i];
-                if (last) break;                 // nothing after the last accepted step is used
-                x_norm = norm7(x);
-                x_cost = cand_cost;
-                __syncthreads();                 // every thread has read the old linearisation
-                if (tid < 28) s_cur[tid] = s_sum[tid];
-                __syncthreads();
-                const double tt = 2.0 * rel - 1.0;
-                double den = 1.0 - tt * tt * tt;
-                if (den < 1.0 / 3.0) den = 1.0 / 3.0;
-                radius = radius / den;
-                if (radius > max_radius) radius = max_radius;
-                decrease_factor = 2.0; reuse_diagonal = false;
-                gmax = 0.0;
-                for (int i = 0; i < 6; i++) gmax = fmax(gmax, fabs(s_cur[21 + i]));
-                if (gmax <= gradient_tol) break;
-            } else {
-                radius = radius / decrease_factor; decrease_factor *= 2.0; reuse_diagonal = true;
-            }
-            if (radius <= min_radius) break;
-        }
-    }
-}
 
+// One kLmT-thread workgroup per chain; residual blocks come from the 64-B records written by k_correspond.  Every thread runs the
+// (uniform) trust-region control flow -- TrustRegion, trust_region.hpp -- redundantly on the block-reduced sums.
+// The accepted linearisation (H, g, cost) lives in LDS (s_cur), a candidate's in s_sum: every thread runs the uniform trust-region
+// arithmetic on the same LDS numbers, and only the scaled, damped system of the current iteration is ever in registers -- with
+// H, Hs, a second matrix for the factor and two accumulator sets per thread the kernel needed ~350 registers and could not run
+// two waves per SIMD.
 __global__ __launch_bounds__(kLmT) void k_lm_solve(BatchView b, OdomView o, int step, int outer, unsigned int *wl_reset)
 {
     const int c = o.clist ? o.clist[o.chain0 + blockIdx.x] : o.chain0 + (int)blockIdx.x;
@@ -1308,15 +1087,32 @@ __global__ __launch_bounds__(kLmT) void k_lm_solve(BatchView b, OdomView o, int 
     double x[7];
     for (int i = 0; i < 7; i++) x[i] = o.state[c * 8 + i];
 
-    LmRecEval ev{ s_rec, n_edge, nq, s_red, s_sum };
-    int iter = 0;
-    ev.run<true>(x);
+    evaluate_block<true>(s_rec, n_edge, nq, x, s_red, s_sum);
     n_used = wave_sum_i(n_used);
     if (lane == 0) s_used[wave] = n_used;
     __syncthreads();
     n_used = 0;
     for (int w = 0; w < kLmW; w++) n_used += s_used[w];
-    lm_trust_region(ev, x, s_cur, s_sum, n_used, iter);
+    TrustRegion<true> tr(LMONO_LM_MAX_ITER);
+    auto take = [&]() {                      // s_cur <- s_sum, once every thread has read the old linearisation
+        __syncthreads();
+        if (tid < 28) s_cur[tid] = s_sum[tid];
+        __syncthreads();
+    };
+    if (tid < 28) s_cur[tid] = s_sum[tid];
+    __syncthreads();
+    if (n_used > 0 && tr.begin(s_cur, x))
+        for (;;) {
+            double cand[7];
+            if (tr.propose(s_cur, x, cand) == 2) break;
+            // The last iteration needs the cost only.  The two sweeps are the two arms of ONE branch on tr.last() on purpose: the compiler then
+            // forms the candidate's rotation matrix once, ahead of the branch.  The sweep is contracted code, and what the back end fuses there
+            // depends on where the code ends up: behind a branch on propose()'s result each arm got a matrix of its own, with other fusions, and
+            // the increments of the 4541-scan sequence moved in the last bits (profiles/r10/NOTES.md, section 4).
+            if (tr.last()) evaluate_block<false>(s_rec, n_edge, nq, cand, s_red, s_sum);
+            else evaluate_block<true>(s_rec, n_edge, nq, cand, s_red, s_sum);
+            if (!tr.judge(s_sum, s_cur, x, cand, take)) break;
+        }
     if (tid == 0) {
         for (int i = 0; i < 7; i++) o.state[c * 8 + i] = x[i];
         if (o.repair && outer == 1) {
@@ -1337,7 +1133,7 @@ __global__ __launch_bounds__(kLmT) void k_lm_solve(BatchView b, OdomView o, int 
             for (int i = 0; i < 7; i++) o.incr[(size_t)k * 7 + i] = x[i];
         if (o.ws && !o.repair && outer == 1 && k == s - 1)
             for (int i = 0; i < 7; i++) o.ws[c * 8 + i] = x[i];       // the warm start of the chain's first owned pair
-        if (o.lm_info) { o.lm_info[c * 4 + outer] = iter; o.lm_info[c * 4 + 2 + outer] = n_used; }
+        if (o.lm_info) { o.lm_info[c * 4 + outer] = tr.iter; o.lm_info[c * 4 + 2 + outer] = n_used; }
     }
 }
 

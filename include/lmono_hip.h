@@ -418,6 +418,37 @@ int lmono_map_builder_cloud(lmono_ctx *, lmono_map_builder *, int which, lmono_p
 int64_t lmono_map_builder_map(lmono_ctx *, lmono_map_builder *, lmono_point_rgb *out_h, int64_t cap);   /* rgb_map; returns its size */
 int lmono_map_builder_clear(lmono_ctx *, lmono_map_builder *);                         /* rgb_map->clear()                    */
 
+/* ---- voxel-grid global colour map -------------------------------------------------------------------------
+ * The pcl::VoxelGrid<pcl::PointXYZRGB> at a 0.1 m leaf that MapBuilder::processMapping carries commented out
+ * (mono_lidar_mapping/src/map_builder/Map_Builder.cc:82-98): the filter the reference left commented out; a definition of this
+ * project (16-bit fixed-point in-cell offsets summed as integers, 64-bit cell keys with no bounding box, output in ascending key order:
+ * z-major, then y, then x).  A device-resident hash table bounded by the number of occupied voxels; its content is the same bytes
+ * for every insertion order, split and batch.  Points with a non-finite coordinate or a cell index outside -2^20 .. 2^20 - 1 are
+ * rejected and counted.
+ * leaf finite and > 0, 1 <= max_voxels <= 2^30 (else NULL + lmono_last_error).  stats (optional) [4] per map: points inserted, points
+ * rejected, voxels new in this call, voxels in the map afterwards.  An insert that needs more than max_voxels voxels returns
+ * LMONO_ECAPACITY and leaves nothing of that call in the map; from then on the map is full: every insert returns LMONO_ECAPACITY
+ * until lmono_voxel_map_clear (size / read / cells keep working), an insert of n == 0 points included: the full map wins.  At most
+ * 2^30 points per call; on a map that is not full n == 0 is a successful no-op with no launch. */
+typedef struct lmono_voxel_map lmono_voxel_map;
+lmono_voxel_map *lmono_voxel_map_create(lmono_ctx *, float leaf, int64_t max_voxels);
+void             lmono_voxel_map_destroy(lmono_voxel_map *);
+int              lmono_voxel_map_clear(lmono_ctx *, lmono_voxel_map *);
+int              lmono_voxel_map_insert(lmono_ctx *, lmono_voxel_map *, const lmono_point_rgb *pts_h, int64_t n, int64_t *stats);
+int              lmono_voxel_map_insert_d(lmono_ctx *, lmono_voxel_map *, const lmono_point_rgb *pts_d, int64_t n, int64_t *stats);
+/* n distinct maps each take the world-frame cloud of the last frame of one of n distinct builders, straight from the builder's
+ * device memory; two launches in all.  LMONO_EINVAL when a builder's last world cloud is no longer in rgb_map (as
+ * lmono_map_builder_cloud(which = 1)); a builder with an empty last frame contributes nothing.  A stream that does not fit is refused
+ * as above (LMONO_ECAPACITY); the other streams of the call are inserted.  If one of the maps is full already, the whole call is refused
+ * with LMONO_ECAPACITY before any launch and no stream is inserted. */
+int              lmono_voxel_map_insert_frames(lmono_ctx *, int n, lmono_voxel_map *const *maps, lmono_map_builder *const *mbs, int64_t *stats);
+int64_t          lmono_voxel_map_size(lmono_ctx *, lmono_voxel_map *);
+/* one point per voxel in ascending key order; returns the voxel count (copies when out_h != NULL) */
+int64_t          lmono_voxel_map_read(lmono_ctx *, lmono_voxel_map *, lmono_point_rgb *out_h, int64_t cap);
+/* diagnostic view: keys ascending, counts, sums [n][6] (offsets x y z in 2^-16 leaf, colour r g b); any output may be NULL */
+int64_t          lmono_voxel_map_cells(lmono_ctx *, lmono_voxel_map *, uint64_t *keys_h, uint32_t *counts_h, uint64_t *sums_h, int64_t cap);
+int              lmono_voxel_map_tile(void);   /* points a workgroup of the insert sums on chip (tests place point counts around it) */
+
 /* ---- image feature tracker ---------------------------------------------------------------------------------
  * Replaces FeatureTracker::trackImage of the mono path, use_rejectF = 0 or 1 (lmono_tracker_set_reject_f) (mono_lidar_mapping/src/image_process/
  * FeatureTracker.cc:189-433): BGR2GRAY (:193), forward / backward pyramidal LK with the 0.5 px round-trip and inBorder tests

@@ -16,6 +16,8 @@ SYMBOLS = [
     "lmono_pose_prefix_d", "lmono_pose_rebase_d", "lmono_map_refine", "lmono_voxel_filter", "lmono_mapper_create", "lmono_mapper_destroy", "lmono_mapper_reset", "lmono_mapper_process", "lmono_mapper_process_batch", "lmono_mapper_cube",
     "lmono_map_builder_create", "lmono_map_builder_destroy", "lmono_associate_to_map", "lmono_associate_to_map_batch", "lmono_map_builder_depth",
     "lmono_map_builder_cloud", "lmono_map_builder_map", "lmono_map_builder_clear",
+    "lmono_voxel_map_create", "lmono_voxel_map_destroy", "lmono_voxel_map_clear", "lmono_voxel_map_insert", "lmono_voxel_map_insert_d", "lmono_voxel_map_insert_frames",
+    "lmono_voxel_map_size", "lmono_voxel_map_read", "lmono_voxel_map_cells", "lmono_voxel_map_tile",
     "lmono_tracker_create", "lmono_tracker_destroy", "lmono_tracker_reset", "lmono_tracker_track", "lmono_tracker_track_batch", "lmono_tracker_pyramid",
     "lmono_tracker_response", "lmono_tracker_lk", "lmono_tracker_set_reject_f", "lmono_tracker_reject_stats", "lmono_tracker_reject_f",
     "lmono_keyframes_create", "lmono_keyframes_destroy", "lmono_keyframes_clear", "lmono_keyframes_size", "lmono_keyframes_add", "lmono_keyframes_add_batch",
@@ -779,6 +781,118 @@ class MapBuilder:
     def close(self):
         if getattr(self, "h", None):
             self.ctx.L.lmono_map_builder_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _voxel_map_prototypes(L):
+    L.lmono_voxel_map_create.restype = C.c_void_p
+    L.lmono_voxel_map_create.argtypes = [C.c_void_p, C.c_float, C.c_int64]
+    L.lmono_voxel_map_destroy.argtypes = [C.c_void_p]
+    L.lmono_voxel_map_clear.argtypes = [C.c_void_p, C.c_void_p]
+    L.lmono_voxel_map_insert.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+    L.lmono_voxel_map_insert_d.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+    L.lmono_voxel_map_insert_frames.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.lmono_voxel_map_size.restype = C.c_int64
+    L.lmono_voxel_map_size.argtypes = [C.c_void_p, C.c_void_p]
+    L.lmono_voxel_map_read.restype = C.c_int64
+    L.lmono_voxel_map_read.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
+    L.lmono_voxel_map_cells.restype = C.c_int64
+    L.lmono_voxel_map_cells.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
+    L.lmono_voxel_map_tile.restype = C.c_int
+
+
+class VoxelMap:
+    """The voxel-grid global colour map on the device (lmono_voxel_map_*): clouds of POINT_RGB folded in frame by frame,
+    bounded by the number of occupied voxels, the same bytes for every insertion order.  insert* return the call's stats
+    [points inserted, points rejected, voxels new, voxels afterwards]; an LmonoError carries the C return value in .code."""
+
+    def __init__(self, ctx, leaf=0.1, max_voxels=1 << 22):
+        self.ctx = ctx
+        ctx._children.add(self)
+        _voxel_map_prototypes(ctx.L)
+        self.leaf = float(np.float32(leaf))
+        self.max_voxels = int(max_voxels)
+        self.TILE = int(ctx.L.lmono_voxel_map_tile())       # points a workgroup of the insert sums on chip
+        self.h = ctx.L.lmono_voxel_map_create(ctx.h, C.c_float(leaf), int(max_voxels))
+        if not self.h:
+            raise LmonoError("lmono_voxel_map_create failed: " + ctx.last_error())
+
+    def _check(self, rc):
+        if rc < 0:
+            e = LmonoError("lmono error %d: %s" % (rc, self.ctx.last_error()))
+            e.code = int(rc)
+            raise e
+        return rc
+
+    def insert(self, points, bgra=None):
+        """points: a POINT_RGB array, or xyz [n][3] float32 with bgra [n] uint32."""
+        if bgra is not None:
+            xyz = np.ascontiguousarray(points, np.float32).reshape(-1, 3)
+            p = np.zeros(len(xyz), POINT_RGB)
+            p["x"] = xyz[:, 0]; p["y"] = xyz[:, 1]; p["z"] = xyz[:, 2]; p["bgra"] = np.asarray(bgra, np.uint32).reshape(-1)
+        else:
+            p = np.ascontiguousarray(points)
+            if p.dtype != POINT_RGB:
+                raise LmonoError("points must be a POINT_RGB array (or xyz float32 with bgra uint32)")
+        stats = np.zeros(4, np.int64)
+        self._check(self.ctx.L.lmono_voxel_map_insert(self.ctx.h, self.h, p.ctypes.data if len(p) else None, len(p), stats.ctypes.data))
+        return stats
+
+    def insert_d(self, ptr, n):
+        """n lmono_point_rgb records in device memory."""
+        stats = np.zeros(4, np.int64)
+        self._check(self.ctx.L.lmono_voxel_map_insert_d(self.ctx.h, self.h, C.c_void_p(int(ptr)), int(n), stats.ctypes.data))
+        return stats
+
+    def insert_frame(self, builder):
+        """The world-frame cloud of a MapBuilder's last frame, straight from its device memory."""
+        return VoxelMap.insert_frames(self.ctx, [self], [builder])[0]
+
+    @staticmethod
+    def insert_frames(ctx, maps, builders):
+        """One frame of several builders into as many maps, two launches in all; returns stats [n][4]."""
+        n = len(maps)
+        if len(builders) != n:
+            raise LmonoError("one builder per map")
+        mh = (C.c_void_p * n)(*[m.h for m in maps]); bh = (C.c_void_p * n)(*[b.h for b in builders])
+        stats = np.zeros((n, 4), np.int64)
+        rc = ctx.L.lmono_voxel_map_insert_frames(ctx.h, n, mh, bh, stats.ctypes.data)
+        if rc < 0:
+            e = LmonoError("lmono error %d: %s" % (rc, ctx.last_error()))
+            e.code = int(rc)
+            raise e
+        return stats
+
+    @property
+    def size(self):
+        return int(self._check(self.ctx.L.lmono_voxel_map_size(self.ctx.h, self.h)))
+
+    def read(self):
+        """One POINT_RGB per voxel, ascending key order (z-major, then y, then x)."""
+        n = self.size
+        out = np.zeros(max(n, 1), POINT_RGB)
+        self._check(self.ctx.L.lmono_voxel_map_read(self.ctx.h, self.h, out.ctypes.data, n))
+        return out[:n]
+
+    def cells(self):
+        """Diagnostic view: keys [n] uint64 ascending, counts [n] uint32, sums [n][6] uint64 (offsets x y z, colour r g b)."""
+        n = self.size
+        keys = np.zeros(max(n, 1), np.uint64); counts = np.zeros(max(n, 1), np.uint32); sums = np.zeros((max(n, 1), 6), np.uint64)
+        self._check(self.ctx.L.lmono_voxel_map_cells(self.ctx.h, self.h, keys.ctypes.data, counts.ctypes.data, sums.ctypes.data, n))
+        return keys[:n], counts[:n], sums[:n]
+
+    def clear(self):
+        self._check(self.ctx.L.lmono_voxel_map_clear(self.ctx.h, self.h))
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.ctx.L.lmono_voxel_map_destroy(self.h)
             self.h = None
 
     def __del__(self):

@@ -1,0 +1,223 @@
+// voxel_map_abi.hip -- C ABI of the voxel-grid colour map (included by lmono_hip.hip after colour_abi.hip: insert_frames reads a map builder)
+#pragma once
+#include "voxel_map.hip"
+
+struct lmono_voxel_map {
+    lmono_ctx *ctx = nullptr;
+    float leaf = 0.0f, inv = 0.0f;
+    int64_t max_voxels = 0, n_vox = 0;       // n_vox: voxels with count > 0 (what size / read / cells see)
+    uint64_t slots = 0;
+    bool full = false;                       // an insert was refused: every further one is, until clear
+    int form = kVmLdsTable;                  // LMONO_VOXEL_FORM=0 at create (measurement switch): one probe and one set of adds per point instead of the LDS table; a batched call runs in its first map's form
+    DevOwner mem;
+    VmRec *rec = nullptr;
+    unsigned *ctl = nullptr;                 // [0] claimed slots, [1] counter of k_vm_compact
+    PtRgb *pts = nullptr;                    // staging of the host-buffer entry
+    int64_t pts_cap = 0;
+    VmEnt *ent = nullptr;                   // per-call scratch: entries per tile, entry counts
+    int64_t ent_cap = 0;                     // in tiles
+    unsigned *tile_n = nullptr;
+    int64_t tile_cap = 0;
+    VmRec *rd_rec = nullptr;                // read / cells: the occupied records
+    PtRgb *rd_pts = nullptr;
+    int64_t rd_rec_cap = 0, rd_pts_cap = 0;
+    // per-call job table + results of a batch led by this map
+    VmJob *jobs = nullptr;
+    int *results = nullptr;
+    int jobs_cap = 0;
+};
+
+static constexpr int64_t kVmMaxCall = (int64_t)1 << 30;    // points of one insert
+
+extern "C" void lmono_voxel_map_destroy(lmono_voxel_map *m) { delete m; }
+
+static int vm_clear(lmono_ctx *c, lmono_voxel_map *m)
+{
+    k_vm_clear<<<(unsigned)((m->slots * 8 + kVmT - 1) / kVmT), kVmT, 0, c->stream>>>(m->rec, m->slots);
+    if (int rc = check_launch(c, "k_vm_clear")) return rc;
+    HIP_TRY(c, hipMemsetAsync(m->ctl, 0, 2 * sizeof(unsigned), c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    m->n_vox = 0; m->full = false;
+    return LMONO_OK;
+}
+
+extern "C" lmono_voxel_map *lmono_voxel_map_create(lmono_ctx *c, float leaf, int64_t max_voxels)
+{
+    if (!c) return nullptr;
+    if (!std::isfinite(leaf) || !(leaf > 0.0f) || max_voxels < 1 || max_voxels > ((int64_t)1 << 30) || !std::isfinite(1.0f / leaf) || !(1.0f / leaf > 0.0f)) {
+        c->err = "lmono_voxel_map_create: leaf must be finite and > 0 (with a finite 1 / leaf), max_voxels in 1 .. 2^30";
+        return nullptr;
+    }
+    if (hipSetDevice(c->device) != hipSuccess) { c->err = "hipSetDevice failed"; return nullptr; }
+    lmono_voxel_map *m = new lmono_voxel_map();
+    m->ctx = c;
+    m->leaf = leaf; m->inv = 1.0f / leaf;
+    m->max_voxels = max_voxels;
+    m->slots = 2;
+    while (m->slots < 2 * (uint64_t)max_voxels) m->slots <<= 1;
+    if (const char *e = getenv("LMONO_VOXEL_FORM")) { const int v = atoi(e); if (v == kVmPlain || v == kVmLdsTable) m->form = v; }
+    const bool ok = m->mem.alloc(m->rec, (size_t)m->slots) && m->mem.alloc(m->ctl, 2);
+    if (!ok || vm_clear(c, m) != LMONO_OK) { c->err = "lmono_voxel_map_create: device allocation failed"; lmono_voxel_map_destroy(m); return nullptr; }
+    return m;
+}
+
+extern "C" int lmono_voxel_map_clear(lmono_ctx *c, lmono_voxel_map *m)
+{
+    if (!c || !m || m->ctx != c) return LMONO_EINVAL;
+    return vm_clear(c, m);
+}
+
+// one insert for n maps: pts_d[s] device clouds of ns[s] points.  Two launches in all; ends synchronised.
+static int vm_insert_batch(lmono_ctx *c, const char *who, int n, lmono_voxel_map *const *maps, const PtRgb *const *pts_d, const int64_t *ns, int64_t *stats)
+{
+    int64_t max_n = 0;
+    for (int s = 0; s < n; s++) {
+        lmono_voxel_map *m = maps[s];
+        if (m->full) { c->err = std::string(who) + ": the map is full (an insert needed more than max_voxels voxels; clear it or create it larger)"; return LMONO_ECAPACITY; }
+        max_n = std::max(max_n, ns[s]);
+    }
+    if (stats)
+        for (int s = 0; s < n; s++) { stats[4 * s] = stats[4 * s + 1] = stats[4 * s + 2] = 0; stats[4 * s + 3] = maps[s]->n_vox; }
+    if (max_n == 0) return LMONO_OK;                           // nothing to do: no launch
+    lmono_voxel_map *lead = maps[0];
+    if (!job_table(lead->mem, lead->jobs, lead->results, lead->jobs_cap, n, 4)) { c->err = std::string(who) + ": job table allocation failed"; return LMONO_ENOMEM; }
+    std::vector<VmJob> jobs((size_t)n);
+    for (int s = 0; s < n; s++) {
+        lmono_voxel_map *m = maps[s];
+        const int64_t tiles = (ns[s] + kVmTile - 1) / kVmTile;
+        // every insert ends synchronised, so nothing in flight reads an outgrown scratch (grow_replace)
+        if (!m->mem.grow_replace(m->ent, m->ent_cap, (size_t)tiles, /*floor=*/64, /*per=*/kVmTile) || !m->mem.grow_replace(m->tile_n, m->tile_cap, (size_t)tiles, /*floor=*/64)) {
+            c->err = std::string(who) + ": scratch allocation failed"; return LMONO_ENOMEM;
+        }
+        VmJob &j = jobs[(size_t)s];
+        j.pts = pts_d[s]; j.n = ns[s];
+        j.rec = m->rec; j.occ = m->ctl; j.mask = (unsigned)(m->slots - 1); j.max_voxels = (unsigned)m->max_voxels; j.inv = m->inv;
+        j.ent = m->ent; j.tile_n = m->tile_n; j.res = lead->results + 4 * s;
+    }
+    HIP_TRY(c, hipMemcpyAsync(lead->jobs, jobs.data(), sizeof(VmJob) * (size_t)n, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemsetAsync(lead->results, 0, sizeof(int) * 4 * (size_t)n, c->stream));
+    const dim3 grid((unsigned)((max_n + kVmTile - 1) / kVmTile), (unsigned)n);
+    if (lead->form == kVmPlain) k_vm_find<kVmPlain><<<grid, kVmT, 0, c->stream>>>(lead->jobs);
+    else k_vm_find<kVmLdsTable><<<grid, kVmT, 0, c->stream>>>(lead->jobs);
+    if (int rc = check_launch(c, "k_vm_find")) return rc;
+    k_vm_accum<<<grid, kVmT, 0, c->stream>>>(lead->jobs);
+    if (int rc = check_launch(c, "k_vm_accum")) return rc;
+    std::vector<int> res((size_t)n * 4);
+    HIP_TRY(c, hipMemcpyAsync(res.data(), lead->results, sizeof(int) * res.size(), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    int rc = LMONO_OK;
+    for (int s = 0; s < n; s++) {
+        lmono_voxel_map *m = maps[s];
+        if (ns[s] == 0) continue;
+        const int *r = res.data() + 4 * (size_t)s;
+        if (stats) stats[4 * s + 1] = r[1];
+        if (r[0]) {                                             // nothing of this call is in the map; keys it claimed stay with count 0, unseen
+            m->full = true;
+            c->err = std::string(who) + ": the points need more than max_voxels voxels; nothing was inserted and the map is full until cleared";
+            rc = LMONO_ECAPACITY;
+            continue;
+        }
+        if (stats) { stats[4 * s] = r[2]; stats[4 * s + 2] = (int64_t)(unsigned)r[3] - m->n_vox; stats[4 * s + 3] = (int64_t)(unsigned)r[3]; }
+        m->n_vox = (int64_t)(unsigned)r[3];
+    }
+    return rc;
+}
+
+extern "C" int lmono_voxel_map_insert_d(lmono_ctx *c, lmono_voxel_map *m, const lmono_point_rgb *pts_d, int64_t n, int64_t *stats)
+{
+    if (!c || !m || m->ctx != c || n < 0 || (n > 0 && !pts_d)) return LMONO_EINVAL;
+    if (n > kVmMaxCall) { c->err = "lmono_voxel_map_insert: more than 2^30 points in one call"; return LMONO_EINVAL; }
+    const PtRgb *p = (const PtRgb *)pts_d;
+    return vm_insert_batch(c, "lmono_voxel_map_insert", 1, &m, &p, &n, stats);
+}
+
+extern "C" int lmono_voxel_map_insert(lmono_ctx *c, lmono_voxel_map *m, const lmono_point_rgb *pts_h, int64_t n, int64_t *stats)
+{
+    if (!c || !m || m->ctx != c || n < 0 || (n > 0 && !pts_h)) return LMONO_EINVAL;
+    if (n > kVmMaxCall) { c->err = "lmono_voxel_map_insert: more than 2^30 points in one call"; return LMONO_EINVAL; }
+    if (n > 0 && !m->full) {
+        if (!m->mem.grow_replace(m->pts, m->pts_cap, (size_t)n, /*floor=*/1 << 16)) { c->err = "lmono_voxel_map_insert: staging allocation failed"; return LMONO_ENOMEM; }
+        HIP_TRY(c, hipMemcpyAsync(m->pts, pts_h, sizeof(PtRgb) * (size_t)n, hipMemcpyHostToDevice, c->stream));
+    }
+    const PtRgb *p = m->pts;
+    const int rc = vm_insert_batch(c, "lmono_voxel_map_insert", 1, &m, &p, &n, stats);
+    if (rc != LMONO_OK) (void)hipStreamSynchronize(c->stream);      // an early return must not leave the copy from the caller's buffer in flight
+    return rc;
+}
+
+extern "C" int lmono_voxel_map_insert_frames(lmono_ctx *c, int n, lmono_voxel_map *const *maps, lmono_map_builder *const *mbs, int64_t *stats)
+{
+    if (!c || n <= 0 || !maps || !mbs) return LMONO_EINVAL;
+    std::vector<const PtRgb *> pts((size_t)n);
+    std::vector<int64_t> ns((size_t)n);
+    for (int s = 0; s < n; s++) {
+        const int fm = batch_handle_fault(c, s, maps), fb = batch_handle_fault(c, s, mbs);
+        if (fm == kHandleForeign || fb == kHandleForeign) { c->err = "lmono_voxel_map_insert_frames: bad stream arguments"; return LMONO_EINVAL; }
+        if (fm == kHandleRepeated || fb == kHandleRepeated) { c->err = "lmono_voxel_map_insert_frames: maps and map builders must be distinct"; return LMONO_EINVAL; }
+        const lmono_map_builder *b = mbs[s];
+        if (b->last_off + b->last_n > b->map_n) { c->err = "lmono_voxel_map_insert_frames: the world cloud of a builder's last frame is no longer in rgb_map"; return LMONO_EINVAL; }
+        pts[(size_t)s] = b->map + b->last_off;
+        ns[(size_t)s] = b->last_n;
+    }
+    return vm_insert_batch(c, "lmono_voxel_map_insert_frames", n, maps, pts.data(), ns.data(), stats);
+}
+
+extern "C" int64_t lmono_voxel_map_size(lmono_ctx *c, lmono_voxel_map *m)
+{
+    if (!c || !m || m->ctx != c) return LMONO_EINVAL;
+    return m->n_vox;
+}
+
+// the occupied records in ascending key order: compacted on the device, ordered on the host (the read ends in host memory and is no hot path)
+static int vm_collect(lmono_ctx *c, lmono_voxel_map *m, std::vector<VmRec> &recs)
+{
+    recs.clear();
+    if (m->n_vox == 0) return LMONO_OK;
+    if (!m->mem.grow_replace(m->rd_rec, m->rd_rec_cap, (size_t)m->n_vox, /*floor=*/1024)) { c->err = "lmono_voxel_map: read buffer allocation failed"; return LMONO_ENOMEM; }
+    HIP_TRY(c, hipMemsetAsync(m->ctl + 1, 0, sizeof(unsigned), c->stream));
+    k_vm_compact<<<(unsigned)((m->slots + kVmT - 1) / kVmT), kVmT, 0, c->stream>>>(m->rec, m->slots, m->rd_rec, (unsigned)m->n_vox, m->ctl + 1);
+    if (int rc = check_launch(c, "k_vm_compact")) return rc;
+    unsigned found = 0;
+    HIP_TRY(c, hipMemcpyAsync(&found, m->ctl + 1, sizeof found, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    if ((int64_t)found != m->n_vox) { c->err = "lmono_voxel_map: the table's occupied records do not match its size"; return LMONO_ENODEV; }
+    recs.resize((size_t)found);
+    HIP_TRY(c, hipMemcpy(recs.data(), m->rd_rec, sizeof(VmRec) * recs.size(), hipMemcpyDeviceToHost));
+    std::sort(recs.begin(), recs.end(), [](const VmRec &a, const VmRec &b) { return a.key < b.key; });
+    return LMONO_OK;
+}
+
+extern "C" int64_t lmono_voxel_map_cells(lmono_ctx *c, lmono_voxel_map *m, uint64_t *keys_h, uint32_t *counts_h, uint64_t *sums_h, int64_t cap)
+{
+    if (!c || !m || m->ctx != c) return LMONO_EINVAL;
+    if (!keys_h && !counts_h && !sums_h) return m->n_vox;
+    if (cap < m->n_vox) { c->err = "lmono_voxel_map_cells: output capacity too small"; return LMONO_ECAPACITY; }
+    std::vector<VmRec> recs;
+    if (int rc = vm_collect(c, m, recs)) return rc;
+    for (size_t i = 0; i < recs.size(); i++) {
+        if (keys_h) keys_h[i] = recs[i].key;
+        if (counts_h) counts_h[i] = (uint32_t)recs[i].w[0];
+        if (sums_h) for (int w = 0; w < 6; w++) sums_h[6 * i + w] = recs[i].w[1 + w];
+    }
+    return m->n_vox;
+}
+
+extern "C" int64_t lmono_voxel_map_read(lmono_ctx *c, lmono_voxel_map *m, lmono_point_rgb *out_h, int64_t cap)
+{
+    if (!c || !m || m->ctx != c) return LMONO_EINVAL;
+    if (!out_h) return m->n_vox;
+    if (cap < m->n_vox) { c->err = "lmono_voxel_map_read: output capacity too small"; return LMONO_ECAPACITY; }
+    std::vector<VmRec> recs;
+    if (int rc = vm_collect(c, m, recs)) return rc;
+    if (recs.empty()) return 0;
+    if (!m->mem.grow_replace(m->rd_pts, m->rd_pts_cap, recs.size(), /*floor=*/1024)) { c->err = "lmono_voxel_map_read: output buffer allocation failed"; return LMONO_ENOMEM; }
+    HIP_TRY(c, hipMemcpyAsync(m->rd_rec, recs.data(), sizeof(VmRec) * recs.size(), hipMemcpyHostToDevice, c->stream));
+    k_vm_finish<<<(unsigned)((recs.size() + kVmT - 1) / kVmT), kVmT, 0, c->stream>>>(m->rd_rec, (unsigned)recs.size(), m->leaf, m->rd_pts);
+    if (int rc = check_launch(c, "k_vm_finish")) return rc;
+    HIP_TRY(c, hipMemcpyAsync(out_h, m->rd_pts, sizeof(PtRgb) * recs.size(), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return m->n_vox;
+}
+
+/* tile size of k_vm_find, for tests that place point counts around it */
+extern "C" int lmono_voxel_map_tile(void) { return kVmTile; }

@@ -1444,6 +1444,7 @@ std::string MapBuilder::processMapping()
     std::string written;
     if (!pending_) return written;
     pending_ = false;
+    if (fold_) fold_();                                                 // :82-98 (setVoxelMap, map_builder_voxel.cpp), before the clear
     map_index++;                                                        // Map_Builder.cc:64
     if (map_index > 0 && map_index % 10 == 0) {                         // :72
         if (save_map_) {

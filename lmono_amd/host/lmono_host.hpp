@@ -413,11 +413,20 @@ public:
     std::string processMapping();
     std::vector<lmono_point_rgb> rgbCloud(int which);        // last frame: 0 camera frame (topic rgb_points), 1 world frame
     std::vector<lmono_point_rgb> rgbMap();                   // rgb_map
+    // The pcl::VoxelGrid the reference carries commented out in processMapping (Map_Builder.cc:82-98), as this project defines it (DESIGN.md
+    // 6c-2): once set, processMapping() also folds the queued frame into a device-resident voxel map, before the every-tenth-frame clear.
+    void setVoxelMap(float leaf, int64_t max_voxels);
+    std::vector<lmono_point_rgb> voxelMap();                 // one point per voxel, ascending key order (empty when not set)
     std::vector<uint8_t> depthMap();                         // filled depth map of the last frame (topic depth_map before COLORMAP_JET)
     int map_index = 0;
 private:
     HipContext &hip_;
     lmono_map_builder *mb_;
+    // the voxel map and its step of processMapping live in map_builder_voxel.cpp: a program that links the mirror without the
+    // lmono_voxel_map_* entry points (the CPU baseline of the frame loop) still links
+    // (fold_ captures this: a MapBuilder is neither copied nor moved, see the deleted copy operations above)
+    std::shared_ptr<lmono_voxel_map> vm_;
+    std::function<void()> fold_;
     lmono_camera cam_;
     bool save_map_, pending_ = false;
     std::string map_dir_;

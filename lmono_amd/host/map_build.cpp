@@ -4,13 +4,16 @@
 // -> MapBuilder::associateToMap -> processMapping; writes <out>/rgb_map<index>.ply every 10 frames and the timing log
 // <out>/mapping_recorder.txt, and dumps the products of the last frame (<out>/depth_last.u8, <out>/cloud_cam_last.bin,
 // <out>/cloud_world_last.bin) for inspection.
-//   map_build <sequence_dir> <trajectory.txt> <out_dir> [n_frames] [width height fx fy cx cy]
+//   map_build <sequence_dir> <trajectory.txt> <out_dir> [n_frames] [width height fx fy cx cy] [voxel=LEAF[:MAX_VOXELS]]
+// With the trailing voxel= argument every frame is also folded into a voxel-grid map, written at the end as
+// <out>/rgb_map_voxel.ply; without it nothing changes.
 #include "kitti_io.hpp"
 #include "lmono_host.hpp"
 
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 
 using namespace lmono_host;
 
@@ -34,7 +37,16 @@ template <typename T> static bool dump(const std::string &path, const std::vecto
 
 int main(int argc, char **argv)
 {
-    if (argc < 4) { std::fprintf(stderr, "usage: map_build <sequence_dir> <trajectory.txt> <out_dir> [n_frames] [width height fx fy cx cy]\n"); return 2; }
+    float voxel_leaf = 0.0f;
+    long long voxel_max = 1 << 22;
+    if (argc > 4 && std::strncmp(argv[argc - 1], "voxel=", 6) == 0) {
+        char *end = nullptr;
+        voxel_leaf = std::strtof(argv[argc - 1] + 6, &end);
+        if (end && *end == ':') voxel_max = std::atoll(end + 1);
+        if (!(voxel_leaf > 0.0f)) { std::fprintf(stderr, "map_build: voxel=LEAF[:MAX_VOXELS] needs a leaf > 0\n"); return 2; }
+        argc--;
+    }
+    if (argc < 4) { std::fprintf(stderr, "usage: map_build <sequence_dir> <trajectory.txt> <out_dir> [n_frames] [width height fx fy cx cy] [voxel=LEAF[:MAX_VOXELS]]\n"); return 2; }
     const std::string seq = argv[1], traj = argv[2], out = argv[3];
     int n_frames = argc > 4 ? std::atoi(argv[4]) : -1;
     lmono_camera cam = { 1241, 376, 718.856, 718.856, 607.1928, 185.2157, 0, 0, 0, 0, 5, 0, 0 };   // kitti00_cam.yaml, kitti_map_config_00.yaml
@@ -53,6 +65,7 @@ int main(int argc, char **argv)
     try {
         HipContext hip(0);
         MapBuilder map_builder(hip, cam, true, out);
+        if (voxel_leaf > 0.0f) map_builder.setVoxelMap(voxel_leaf, voxel_max);
         MappingLog recorder(out + "/mapping_recorder.txt");
         if (!recorder.ok()) { std::fprintf(stderr, "cannot write into %s\n", out.c_str()); return 1; }
         std::vector<uint8_t> image;
@@ -72,6 +85,11 @@ int main(int argc, char **argv)
                 if (!dump(out + "/depth_last.u8", map_builder.depthMap()) || !dump(out + "/cloud_cam_last.bin", map_builder.rgbCloud(0))) return 1;
                 if (written.empty() && !dump(out + "/cloud_world_last.bin", map_builder.rgbCloud(1))) return 1;
             }
+        }
+        if (voxel_leaf > 0.0f) {
+            const std::vector<lmono_point_rgb> v = map_builder.voxelMap();
+            const std::string path = out + "/rgb_map_voxel.ply";
+            if (!write_ply_binary(path, reinterpret_cast<const PointRgb *>(v.data()), v.size())) { std::fprintf(stderr, "cannot write %s\n", path.c_str()); return 1; }
         }
     } catch (const std::exception &e) {
         std::fprintf(stderr, "map_build: %s\n", e.what());

@@ -25,6 +25,8 @@ struct lmono_scan_batch {
     double *state = nullptr, *incr = nullptr, *poses = nullptr, *xq = nullptr;
     int *corr = nullptr, *lm_info = nullptr, *corr_pair = nullptr, *seed = nullptr;
     float4 *crec = nullptr, *crec_pair = nullptr;
+    float4 *lmrec = nullptr;               // the planes of k_lm_solve's staged blocks that are not in LDS: [chains_cap][4 - lm_planes][kMaxQueries]
+    size_t lmrec_cap = 0;                  // float4 entries of lmrec
     unsigned int *wl = nullptr;            // work list of feature points the LDS tile search defers: [0] = count
     size_t wl_cap = 0;
     // boundary validation of the chained schedule
@@ -326,9 +328,15 @@ extern "C" int lmono_batch_get_curvature(lmono_ctx *c, lmono_scan_batch *b, int 
 
 static int ensure_odom_ws(lmono_ctx *c, lmono_scan_batch *b, int n_chains)
 {
+    DevOwner &m = b->mem;
+    // k_lm_solve<planes>'s scratch: sized for the calling context's instantiation (a batch may meet contexts that differ in it)
+    const size_t lmrec_need = (size_t)(n_chains > b->chains_cap ? n_chains : b->chains_cap) * (4 - c->lm_planes) * kMaxQueries;
+    if (lmrec_need > b->lmrec_cap) {
+        if (!m.alloc(b->lmrec, lmrec_need)) { c->err = "odometry workspace: hipMalloc failed"; return LMONO_ENOMEM; }
+        b->lmrec_cap = lmrec_need;
+    }
     if (n_chains <= b->chains_cap) return LMONO_OK;
     // the grow_keep policy, sized by hand: exactly n_chains (no doubling), and the outgrown buffers stay owned until the batch is destroyed
-    DevOwner &m = b->mem;
     bool ok = m.alloc(b->state, (size_t)n_chains * 8) && m.alloc(b->corr, (size_t)n_chains * kMaxQueries * 4) &&
               m.alloc(b->lm_info, (size_t)n_chains * 4) && m.alloc(b->crec, (size_t)n_chains * kMaxQueries * 4) &&
               m.alloc(b->seed, (size_t)n_chains * kMaxQueries) && m.alloc(b->wl, 8 * ((size_t)n_chains * kMaxQueries + 1)) &&
@@ -408,8 +416,11 @@ static int odom_groups(const lmono_ctx *c, int n_ch)
 
 // Steps [step_a, step_b) x 2 outer iterations of the chains [0, n_ch) of view o (o.clist set: of the listed chains), in G chain groups.
 // Chain groups: with LMONO_OPT_ODOM_STREAMS = G > 1 the chains are cut into G groups, each advancing on its own stream, so that
-// one group's solve (one workgroup per chain: a quarter of the CUs' wave slots at most) and the ragged tail of its search kernel
-// run beside the other groups' searches.  Group 0 carries the per-kernel events.  The runtime maps streams onto 4 hardware queues
+// one group's solve and the ragged tail of its search kernel run beside the other groups' searches.  A solve launch is one four-wave
+// workgroup per chain, 64 CUs for a group of 64 chains, and 1.2 - 1.3 such launches are in flight over the main pass: what they leave of
+// those CUs to the search is set by LDS and registers, not by wave slots.  k_lm_solve<0> takes 1.4 KB of LDS and 240 VGPRs, so four
+// k_corr_flat workgroups (two 136-VGPR waves per SIMD) fit beside it; k_lm_solve<4> (144 KB of LDS) excludes the search from its CU.
+// Group 0 carries the per-kernel events.  The runtime maps streams onto 4 hardware queues
 // (GPU_MAX_HW_QUEUES): the null stream on one of its own, created streams round-robin on the other three.  So the default context
 // (null stream) runs group 0 on the null stream + 3 group streams = 4 distinct queues; a context on a caller-created stream runs
 // at most 3 groups, all on the library's own streams (4 created streams would put two groups on one queue: 64-70 instead of 51 ms
@@ -449,7 +460,9 @@ static int odom_launch_steps(lmono_ctx *c, lmono_scan_batch *b, const OdomView &
                     hipLaunchKernelGGL(k_correspond, dim3(8 * ((ng + 7) / 8) * kCorrBlocks), dim3(256), 0, sg, b->v, og, step, outer);
 #endif
                 if (e0 && e1 && e2) (void)hipEventRecord(e1, sg);
-                hipLaunchKernelGGL(k_lm_solve, dim3(ng), dim3(kLmT), kLmRecLds, sg, b->v, og, step, outer, tile ? wlg : (unsigned int *)nullptr);
+                unsigned int *wlr = tile ? wlg : (unsigned int *)nullptr;
+                if (c->lm_planes == 4) hipLaunchKernelGGL(k_lm_solve<4>, dim3(ng), dim3(kLmT), lm_rec_lds(4), sg, b->v, og, step, outer, wlr);
+                else hipLaunchKernelGGL(k_lm_solve<0>, dim3(ng), dim3(kLmT), lm_rec_lds(0), sg, b->v, og, step, outer, wlr);
                 if (e0 && e1 && e2) { (void)hipEventRecord(e2, sg); *ne += 3; }
             }
         }
@@ -532,7 +545,7 @@ static OdomView odom_view(lmono_ctx *c, lmono_scan_batch *b, int n_chains, int l
     OdomView o{};
     o.n_scans = b->n_scans; o.n_chains = n_chains; o.lead = lead; o.first = first; o.fixed_k = -1; o.chain0 = 0; o.chain1 = n_chains;
     o.lead_full = c->opt[LMONO_OPT_CORR_TILE] == 3 ? c->opt[LMONO_OPT_LEAD_FULL] : -1;     // only the default search thins lead-in pairs
-    o.state = b->state; o.corr = b->corr; o.incr = b->incr; o.lm_info = b->lm_info; o.crec = b->crec; o.seed = b->seed;
+    o.state = b->state; o.corr = b->corr; o.incr = b->incr; o.lm_info = b->lm_info; o.crec = b->crec; o.lmrec = b->lmrec; o.seed = b->seed;
     o.ws = b->ws; o.repair = 0; o.step0 = 0; o.clist = nullptr; o.rstat = b->rstat; o.rcount = b->rcount;
     o.tol = 1e-9 * (double)c->opt[LMONO_OPT_BOUNDARY_TOL];
     return o;

@@ -53,6 +53,7 @@ struct lmono_ctx {
     hipStream_t copy_stream = nullptr;       // H2D staging of lmono_batch_stage_h (runs beside the compute stream)
     hipStream_t own_stream = nullptr;        // lmono_use_own_stream: a stream of the library's that this context runs on
     bool odom_prio = false, many_queues = false;     // measurement switches read from the environment at creation (LMONO_ODOM_STREAM_PRIORITY, GPU_MAX_HW_QUEUES >= 8)
+    int lm_planes = kLmPlanesDefault;                // k_lm_solve<planes>: 16-B planes of a staged block kept in LDS (measurement switch LMONO_LM_LDS_PLANES = 4 or 0 at creation)
     // scratch arena of the small host-array entry points (triangulate, outlier scores, marginalise ...): chunks are allocated once and
     // reused by every later call -- no hipMalloc / hipFree (both synchronise the device) in a steady-state frame loop
     struct Chunk { char *base; size_t cap; };
@@ -212,6 +213,7 @@ extern "C" lmono_ctx *lmono_create(int device)
     c->device = device;
     if (const char *e = getenv("LMONO_ODOM_STREAM_PRIORITY")) c->odom_prio = atoi(e) != 0;
     if (const char *e = getenv("GPU_MAX_HW_QUEUES")) c->many_queues = atoi(e) >= 8;
+    if (const char *e = getenv("LMONO_LM_LDS_PLANES")) { const int v = atoi(e); if (lm_planes_valid(v)) c->lm_planes = v; }
     {
         // residency budget of the cluster kernels: every workgroup of a cluster spins on its partners, so all of them must be resident at once.  k_ba_solve
         // takes a whole CU's LDS (one workgroup per CU); half the CUs leaves room for whatever else the card runs (LMONO_CLUSTER_BUDGET overrides: CU masks,
@@ -230,7 +232,7 @@ extern "C" lmono_ctx *lmono_create(int device)
     if (hipFuncSetAttribute((const void *)k_select, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * sel_slice_bytes(kRingCap) + 4 * kSelScratch) != hipSuccess) { delete c; return nullptr; }
     if (hipFuncSetAttribute((const void *)k_voxel<kVoxSmallSlots, kVoxSmallBits, true>, hipFuncAttributeMaxDynamicSharedMemorySize, kVoxLdsSmall) != hipSuccess) { delete c; return nullptr; }
     if (hipFuncSetAttribute((const void *)k_voxel<kVoxBigSlots, kVoxBigBits, false>, hipFuncAttributeMaxDynamicSharedMemorySize, kVoxLdsBig) != hipSuccess) { delete c; return nullptr; }
-    if (hipFuncSetAttribute((const void *)k_lm_solve, hipFuncAttributeMaxDynamicSharedMemorySize, kLmRecLds) != hipSuccess) { delete c; return nullptr; }
+    if (hipFuncSetAttribute((const void *)k_lm_solve<4>, hipFuncAttributeMaxDynamicSharedMemorySize, lm_rec_lds(4)) != hipSuccess) { delete c; return nullptr; }
 #ifdef LMONO_DIAG_SEARCH
     if (hipFuncSetAttribute((const void *)k_grid_build, hipFuncAttributeMaxDynamicSharedMemorySize, kGridLds) != hipSuccess) { delete c; return nullptr; }
 #endif

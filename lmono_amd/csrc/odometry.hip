@@ -259,6 +259,7 @@ struct OdomView {
     double *state;        // [n_chains][8]  q(xyzw), t, pad
     int *corr;            // [n_chains][kMaxQueries][4]
     float4 *crec;         // [n_chains][kMaxQueries][4] residual-block records: (cp, kind), a, b, c
+    float4 *lmrec;        // [n_chains][4 - planes][kMaxQueries] the planes of k_lm_solve<planes>'s staged blocks that are not in LDS (LmRec)
     double *incr;         // [n_scans][7]
     int *lm_info;         // [n_chains][4]
     int *seed;            // [n_chains][kMaxQueries] nearest point found by the previous outer iteration of the same scan pair (-1: none)
@@ -977,12 +978,50 @@ __device__ __forceinline__ void eval_block(const float4 cp, const double2 P01, c
         lm_row(acc, qx, qy, qz, rvx, rvy, rvz, r0, sr);
 }
 
+// Where a chain's staged blocks live.  A block is four 16-B planes of kMaxQueries entries each: plane 0 = (cp, kind), planes 1 - 3 = the six
+// doubles of stage_block.  The first kPlanes planes are in LDS (conflict-free 16-B reads), the others in the chain's rows of OdomView::lmrec.
+// kPlanes = 4 (the A/B side, LMONO_LM_LDS_PLANES=4) is all of a CU's LDS but 13 KB: no k_corr_flat workgroup fits beside the solve, and the
+// solve starts only on a CU that has drained of them.  With 0 (shipped) the registers alone decide (LMONO_LM_VGPRS): four search workgroups
+// share the CU.  2 (72 KB, three search workgroups) was measured between the two and dropped (profiles/r12/NOTES.md).
+// The memory planes need no fence: thread tid stages the blocks tid + kLmT * t and is the only thread that ever reads them back, so every
+// load follows, in program order, the same thread's store to the same address.  (Anything read across threads would need the
+// workgroup-scope release / acquire pair of CompactIndexFeed::finish.)
+struct LmBlk { float4 cp; double2 p01, p23, p45; };
+template <int kPlanes>
+struct LmRec {
+    static_assert(kPlanes == 0 || kPlanes == 4, "the instantiations the library holds");
+    float4 *lds;      // [kPlanes][kMaxQueries]
+    float4 *mem;      // [4 - kPlanes][kMaxQueries], this chain's
+    template <int p> __device__ __forceinline__ float4 *plane() const { return p < kPlanes ? lds + p * kMaxQueries : mem + (p - kPlanes) * kMaxQueries; }
+    __device__ __forceinline__ void put(int qi, const float4 cp, const double *P) const
+    {
+        plane<0>()[qi] = cp;
+        ((double2 *)plane<1>())[qi] = make_double2(P[0], P[1]);
+        ((double2 *)plane<2>())[qi] = make_double2(P[2], P[3]);
+        ((double2 *)plane<3>())[qi] = make_double2(P[4], P[5]);
+    }
+    // the planes of block qi that are in memory / in LDS
+    __device__ __forceinline__ void request(int qi, LmBlk &k) const
+    {
+        if (kPlanes < 1) k.cp = plane<0>()[qi];
+        if (kPlanes < 2) k.p01 = ((const double2 *)plane<1>())[qi];
+        if (kPlanes < 3) k.p23 = ((const double2 *)plane<2>())[qi];
+        if (kPlanes < 4) k.p45 = ((const double2 *)plane<3>())[qi];
+    }
+    __device__ __forceinline__ void local(int qi, LmBlk &k) const
+    {
+        if (kPlanes >= 1) k.cp = plane<0>()[qi];
+        if (kPlanes >= 2) k.p01 = ((const double2 *)plane<1>())[qi];
+        if (kPlanes >= 3) k.p23 = ((const double2 *)plane<2>())[qi];
+        if (kPlanes >= 4) k.p45 = ((const double2 *)plane<3>())[qi];
+    }
+};
+
 // Sum over all residual blocks of a chain by the kLmT threads of its workgroup (wave butterfly, then the wave partials are added in
 // fixed order); the sums -- H (21, upper triangle row by row), g (6), cost -- are left in LDS (s_sum) for every thread to read: the
-// trust-region code below keeps no copy of them in registers.  srec = the chain's records in LDS, one plane of kMaxQueries float4
-// per record field (conflict-free 16-B reads).
-template <bool kJac>
-__device__ __forceinline__ void evaluate_block(const float4 *srec, int n_edge, int nq, const double *x, double (*s_red)[28], double *s_sum)
+// trust-region code below keeps no copy of them in registers.  rec = the chain's staged blocks (LmRec).
+template <bool kJac, int kPlanes>
+__device__ __forceinline__ void evaluate_block(const LmRec<kPlanes> rec, int n_edge, int nq, const double *x, double (*s_red)[28], double *s_sum)
 {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     LmAcc acc;
@@ -1004,12 +1043,33 @@ __device__ __forceinline__ void evaluate_block(const float4 *srec, int n_edge, i
     }
     // a thread visits its blocks in ascending order as before (edge blocks are the first n_edge of a chain's list), but every loop body
     // is one kind: no divergence inside a wave except at unused blocks
-    const double2 *sp = (const double2 *)srec;
     int qi = tid;
-    for (; qi < n_edge; qi += kLmT)
-        eval_block<kJac, true>(srec[qi], sp[kMaxQueries + qi], sp[2 * kMaxQueries + qi], sp[3 * kMaxQueries + qi], Rm, x, acc);
-    for (; qi < nq; qi += kLmT)
-        eval_block<kJac, false>(srec[qi], sp[kMaxQueries + qi], sp[2 * kMaxQueries + qi], sp[3 * kMaxQueries + qi], Rm, x, acc);
+    if (kPlanes == 4) {
+        const float4 *srec = rec.lds;
+        const double2 *sp = (const double2 *)srec;
+        for (; qi < n_edge; qi += kLmT)
+            eval_block<kJac, true>(srec[qi], sp[kMaxQueries + qi], sp[2 * kMaxQueries + qi], sp[3 * kMaxQueries + qi], Rm, x, acc);
+        for (; qi < nq; qi += kLmT)
+            eval_block<kJac, false>(srec[qi], sp[kMaxQueries + qi], sp[2 * kMaxQueries + qi], sp[3 * kMaxQueries + qi], Rm, x, acc);
+    } else {
+        // the memory planes of the thread's next block (at most nine per thread) are requested before this one is evaluated: they come from L2
+        LmBlk cur = {}, nxt;
+        if (qi < nq) rec.request(qi, cur);
+        for (; qi < n_edge; qi += kLmT) {
+            nxt = cur;
+            if (qi + kLmT < nq) rec.request(qi + kLmT, nxt);
+            rec.local(qi, cur);
+            eval_block<kJac, true>(cur.cp, cur.p01, cur.p23, cur.p45, Rm, x, acc);
+            cur = nxt;
+        }
+        for (; qi < nq; qi += kLmT) {
+            nxt = cur;
+            if (qi + kLmT < nq) rec.request(qi + kLmT, nxt);
+            rec.local(qi, cur);
+            eval_block<kJac, false>(cur.cp, cur.p01, cur.p23, cur.p45, Rm, x, acc);
+            cur = nxt;
+        }
+    }
     acc.cost = wave_sum_d(acc.cost);
     if (kJac) {
 #pragma unroll
@@ -1034,7 +1094,16 @@ __device__ __forceinline__ void evaluate_block(const float4 *srec, int n_edge, i
     __syncthreads();
 }
 
-constexpr int kLmRecLds = 4 * kMaxQueries * 16;   // the chain's records in LDS
+constexpr int lm_rec_lds(int planes) { return planes * kMaxQueries * 16; }   // dynamic LDS of k_lm_solve<planes>: the chain's blocks, planes of 16 B
+constexpr int kLmPlanesDefault = 0;   // the shipped instantiation (LMONO_LM_LDS_PLANES at context creation picks the other: a measurement switch)
+__host__ inline bool lm_planes_valid(int planes) { return planes == 4 || planes == 0; }
+// Register cap of k_lm_solve: a k_corr_flat wave is allocated 136 VGPRs (134 in granules of 8), a SIMD has 512, and 512 - 240 = 2 x 136: at
+// 240 or fewer two search waves fit on a SIMD beside a solve wave, at the 255 the kernel takes uncapped only one (profiles/r12/NOTES.md).
+// The cap acts at register allocation, behind instruction selection: it moves spills, not fusions.  On gfx90a and later the back end doubles
+// the attribute's argument (it counts the unified VGPR + AGPR file in pairs), hence the / 2.
+#ifndef LMONO_LM_VGPRS
+#define LMONO_LM_VGPRS 240
+#endif
 #ifndef LMONO_CF_T
 #define LMONO_CF_T 128
 #endif
@@ -1050,7 +1119,8 @@ constexpr int kThinBlocks = kMaxQueries / LMONO_CF_T;     // = kCfBlocks of corr
 // arithmetic on the same LDS numbers, and only the scaled, damped system of the current iteration is ever in registers -- with
 // H, Hs, a second matrix for the factor and two accumulator sets per thread the kernel needed ~350 registers and could not run
 // two waves per SIMD.
-__global__ __launch_bounds__(kLmT) void k_lm_solve(BatchView b, OdomView o, int step, int outer, unsigned int *wl_reset)
+template <int kPlanes>
+__global__ __launch_bounds__(kLmT) __attribute__((amdgpu_num_vgpr(LMONO_LM_VGPRS / 2))) void k_lm_solve(BatchView b, OdomView o, int step, int outer, unsigned int *wl_reset)
 {
     const int c = o.clist ? o.clist[o.chain0 + blockIdx.x] : o.chain0 + (int)blockIdx.x;
     if (wl_reset && blockIdx.x == 0 && threadIdx.x == 0) wl_reset[0] = 0u;      // the work list of the next correspondence launch starts empty
@@ -1062,14 +1132,14 @@ __global__ __launch_bounds__(kLmT) void k_lm_solve(BatchView b, OdomView o, int 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int n_edge = b.feat_n[k * 4 + 0], nq = n_edge + b.feat_n[k * 4 + 2];
     const float4 *crec = o.crec + (size_t)c * kMaxQueries * 4;
-    // the chain's residual-block records (64 B each, <= 144 KB) are read once and stay in LDS for the up to nine
-    // evaluations of this launch; eight 16-B loads per thread in flight
+    // the chain's residual-block records (64 B each, <= 144 KB) are read once and stay staged (LmRec: LDS and / or the chain's rows of
+    // o.lmrec) for the up to nine evaluations of this launch; eight 16-B loads per thread in flight
     extern __shared__ __align__(16) float4 s_rec[];
+    const LmRec<kPlanes> rec = { s_rec, kPlanes < 4 ? o.lmrec + (size_t)c * (4 - kPlanes) * kMaxQueries : nullptr };
     int n_used = 0;
     {
         // one record per thread and round: its four 16-B quarters are requested together, the pose-independent part of the
-        // residual block is computed once (stage_block) and the block goes to LDS as (cp, kind) + six doubles
-        double2 *sp = (double2 *)s_rec;
+        // residual block is computed once (stage_block) and the block is staged as (cp, kind) + six doubles
         const bool thin = lead_in_thinned(o, k, s);
         for (int qi = tid; qi < nq; qi += kLmT) {
             float4 cp = crec[qi * 4];
@@ -1077,17 +1147,14 @@ __global__ __launch_bounds__(kLmT) void k_lm_solve(BatchView b, OdomView o, int 
             if (thin && (qi % kThinBlocks) % kThinStride != 0) cp.w = 0.f;       // not searched in this launch: a stale record
             double P[6] = { 0.0, 0.0, 0.0, 0.0, 0.0, 0.0 };
             if (__float_as_int(cp.w) != 0) { stage_block(cp, A, B, Cc, P); n_used++; }
-            s_rec[qi] = cp;
-            sp[kMaxQueries + qi] = make_double2(P[0], P[1]);
-            sp[2 * kMaxQueries + qi] = make_double2(P[2], P[3]);
-            sp[3 * kMaxQueries + qi] = make_double2(P[4], P[5]);
+            rec.put(qi, cp, P);
         }
     }
     __syncthreads();
     double x[7];
     for (int i = 0; i < 7; i++) x[i] = o.state[c * 8 + i];
 
-    evaluate_block<true>(s_rec, n_edge, nq, x, s_red, s_sum);
+    evaluate_block<true>(rec, n_edge, nq, x, s_red, s_sum);
     n_used = wave_sum_i(n_used);
     if (lane == 0) s_used[wave] = n_used;
     __syncthreads();
@@ -1109,8 +1176,8 @@ __global__ __launch_bounds__(kLmT) void k_lm_solve(BatchView b, OdomView o, int 
             // forms the candidate's rotation matrix once, ahead of the branch.  The sweep is contracted code, and what the back end fuses there
             // depends on where the code ends up: behind a branch on propose()'s result each arm got a matrix of its own, with other fusions, and
             // the increments of the 4541-scan sequence moved in the last bits (profiles/r10/NOTES.md, section 4).
-            if (tr.last()) evaluate_block<false>(s_rec, n_edge, nq, cand, s_red, s_sum);
-            else evaluate_block<true>(s_rec, n_edge, nq, cand, s_red, s_sum);
+            if (tr.last()) evaluate_block<false>(rec, n_edge, nq, cand, s_red, s_sum);
+            else evaluate_block<true>(rec, n_edge, nq, cand, s_red, s_sum);
             if (!tr.judge(s_sum, s_cur, x, cand, take)) break;
         }
     if (tid == 0) {

@@ -449,6 +449,39 @@ int64_t          lmono_voxel_map_read(lmono_ctx *, lmono_voxel_map *, lmono_poin
 int64_t          lmono_voxel_map_cells(lmono_ctx *, lmono_voxel_map *, uint64_t *keys_h, uint32_t *counts_h, uint64_t *sums_h, int64_t cap);
 int              lmono_voxel_map_tile(void);   /* points a workgroup of the insert sums on chip (tests place point counts around it) */
 
+/* ---- statistical outlier removal in front of the voxel map ---------------------------------------------------
+ * The pcl::StatisticalOutlierRemoval<pcl::PointXYZRGB> with setMeanK(100) / setStddevMulThresh(1.0) that MapBuilder::processMapping
+ * carries commented out in front of its voxel grid (mono_lidar_mapping/src/map_builder/Map_Builder.cc:24-29), as a device-resident
+ * filter between the map builder and the voxel map.  A definition of this project (lmono_amd/csrc/sor.hpp): the score of a point is
+ * the sum of the distances to its mean_k nearest neighbours in units of 2^-16 m, an exact integer; a point with fewer than mean_k
+ * neighbours within rho = (max_rings - 0.25) cell is isolated and removed without entering the statistics (PCL would look as far as
+ * it must); a scored point is kept iff score <= mean + stddev_mul * sample standard deviation of the scores.  Points the voxel map
+ * would reject at leaf = cell (non-finite, cell index outside -2^20 .. 2^20 - 1) are rejected: counted, never neighbours, never kept.
+ * The result is a pure function of the set of input points; the output is the kept points in input order, payload untouched.
+ * create: 1 <= max_points <= 2^28, 1 <= mean_k <= 128, stddev_mul finite, cell finite and > 0, 1 <= max_rings <= 64 and
+ * (max_rings - 0.25) cell <= 256 (else NULL + lmono_last_error).  stats (optional) [8] per stream: points in, rejected, isolated,
+ * scored (M), kept, A = sum of scores, Bhi, Blo = high and low 32-bit halves of the squared scores, summed.  n > max_points returns
+ * LMONO_ECAPACITY before any launch; n == 0 is a successful empty result with no launch.  Every call replaces the filter's last result. */
+typedef struct lmono_sor lmono_sor;
+lmono_sor *lmono_sor_create(lmono_ctx *, int64_t max_points, int mean_k, double stddev_mul, float cell, int max_rings);
+void       lmono_sor_destroy(lmono_sor *);
+int        lmono_sor_filter(lmono_ctx *, lmono_sor *, const lmono_point_rgb *pts_h, int64_t n, int64_t *stats);
+int        lmono_sor_filter_d(lmono_ctx *, lmono_sor *, const lmono_point_rgb *pts_d, int64_t n, int64_t *stats);
+/* n distinct filters each take the world-frame cloud of the last frame of one of n distinct builders, straight from the builder's
+ * device memory; one launch per phase for all streams.  LMONO_EINVAL when a builder's last world cloud is no longer in rgb_map; a
+ * builder with an empty last frame gives an empty result.  A stream's bytes do not depend on the batch it travels in. */
+int        lmono_sor_filter_frames(lmono_ctx *, int n, lmono_sor *const *sors, lmono_map_builder *const *mbs, int64_t *stats);
+/* the kept points of the last call in input order; returns their count (copies when out_h != NULL) */
+int64_t    lmono_sor_cloud(lmono_ctx *, lmono_sor *, lmono_point_rgb *out_h, int64_t cap);
+/* diagnostic view of the last call, per input point: keep flag and score (0xffffffff = isolated or rejected); returns the point count */
+int64_t    lmono_sor_scores(lmono_ctx *, lmono_sor *, uint8_t *keep_h, uint32_t *v_h, int64_t cap);
+int        lmono_sor_threshold(lmono_ctx *, lmono_sor *, double out[3]);            /* mean, sqrt(var), thr in v units */
+/* measurement view of the last call: out[0] rings scanned, summed over the valid points; out[1] points scored by the radix select */
+int        lmono_sor_diag(lmono_ctx *, lmono_sor *, int64_t out[2]);
+/* n distinct maps each fold in the last output of one of n distinct filters, from device memory: the two insert launches and the
+ * capacity rules of lmono_voxel_map_insert_frames, unchanged (stats [4] per map as there). */
+int        lmono_voxel_map_insert_filtered(lmono_ctx *, int n, lmono_voxel_map *const *maps, lmono_sor *const *sors, int64_t *stats);
+
 /* ---- image feature tracker ---------------------------------------------------------------------------------
  * Replaces FeatureTracker::trackImage of the mono path, use_rejectF = 0 or 1 (lmono_tracker_set_reject_f) (mono_lidar_mapping/src/image_process/
  * FeatureTracker.cc:189-433): BGR2GRAY (:193), forward / backward pyramidal LK with the 0.5 px round-trip and inBorder tests

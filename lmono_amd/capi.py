@@ -18,6 +18,8 @@ SYMBOLS = [
     "lmono_map_builder_cloud", "lmono_map_builder_map", "lmono_map_builder_clear",
     "lmono_voxel_map_create", "lmono_voxel_map_destroy", "lmono_voxel_map_clear", "lmono_voxel_map_insert", "lmono_voxel_map_insert_d", "lmono_voxel_map_insert_frames",
     "lmono_voxel_map_size", "lmono_voxel_map_read", "lmono_voxel_map_cells", "lmono_voxel_map_tile",
+    "lmono_sor_create", "lmono_sor_destroy", "lmono_sor_filter", "lmono_sor_filter_d", "lmono_sor_filter_frames", "lmono_sor_cloud", "lmono_sor_scores",
+    "lmono_sor_threshold", "lmono_sor_diag", "lmono_voxel_map_insert_filtered",
     "lmono_tracker_create", "lmono_tracker_destroy", "lmono_tracker_reset", "lmono_tracker_track", "lmono_tracker_track_batch", "lmono_tracker_pyramid",
     "lmono_tracker_response", "lmono_tracker_lk", "lmono_tracker_set_reject_f", "lmono_tracker_reject_stats", "lmono_tracker_reject_f",
     "lmono_keyframes_create", "lmono_keyframes_destroy", "lmono_keyframes_clear", "lmono_keyframes_size", "lmono_keyframes_add", "lmono_keyframes_add_batch",
@@ -887,12 +889,134 @@ class VoxelMap:
         self._check(self.ctx.L.lmono_voxel_map_cells(self.ctx.h, self.h, keys.ctypes.data, counts.ctypes.data, sums.ctypes.data, n))
         return keys[:n], counts[:n], sums[:n]
 
+    @staticmethod
+    def insert_filtered(maps, filters):
+        """The last output of each OutlierFilter into its map, from device memory: the two insert launches and the capacity rules of
+        insert_frames; returns stats [n][4]."""
+        n = len(maps)
+        if n == 0 or len(filters) != n:
+            raise LmonoError("one filter per map")
+        ctx = maps[0].ctx
+        _sor_prototypes(ctx.L)
+        mh = (C.c_void_p * n)(*[m.h for m in maps]); fh = (C.c_void_p * n)(*[f.h for f in filters])
+        stats = np.zeros((n, 4), np.int64)
+        _raise_coded(ctx, ctx.L.lmono_voxel_map_insert_filtered(ctx.h, n, mh, fh, stats.ctypes.data))
+        return stats
+
     def clear(self):
         self._check(self.ctx.L.lmono_voxel_map_clear(self.ctx.h, self.h))
 
     def close(self):
         if getattr(self, "h", None):
             self.ctx.L.lmono_voxel_map_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _raise_coded(ctx, rc):
+    if rc < 0:
+        e = LmonoError("lmono error %d: %s" % (rc, ctx.last_error()))
+        e.code = int(rc)
+        raise e
+    return rc
+
+
+def _sor_prototypes(L):
+    L.lmono_sor_create.restype = C.c_void_p
+    L.lmono_sor_create.argtypes = [C.c_void_p, C.c_int64, C.c_int, C.c_double, C.c_float, C.c_int]
+    L.lmono_sor_destroy.argtypes = [C.c_void_p]
+    L.lmono_sor_filter.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+    L.lmono_sor_filter_d.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+    L.lmono_sor_filter_frames.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.lmono_sor_cloud.restype = C.c_int64
+    L.lmono_sor_cloud.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
+    L.lmono_sor_scores.restype = C.c_int64
+    L.lmono_sor_scores.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
+    L.lmono_sor_threshold.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.lmono_sor_diag.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    L.lmono_voxel_map_insert_filtered.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+
+
+class OutlierFilter:
+    """Statistical outlier removal on the device, between MapBuilder and VoxelMap (lmono_sor_*).  filter* return the call's
+    stats [points in, rejected, isolated, scored, kept, A, Bhi, Blo]; the kept points stay on the device for VoxelMap.insert_filtered and
+    come to the host with cloud().  An LmonoError carries the C return value in .code."""
+
+    def __init__(self, ctx, max_points, mean_k=100, stddev_mul=1.0, cell=0.1, max_rings=8):
+        self.ctx = ctx
+        ctx._children.add(self)
+        _sor_prototypes(ctx.L)
+        self.max_points = int(max_points)
+        self.stats = np.zeros(8, np.int64)
+        self.h = ctx.L.lmono_sor_create(ctx.h, int(max_points), int(mean_k), C.c_double(stddev_mul), C.c_float(cell), int(max_rings))
+        if not self.h:
+            raise LmonoError("lmono_sor_create failed: " + ctx.last_error())
+
+    def filter(self, points):
+        """points: a POINT_RGB array on the host."""
+        p = np.ascontiguousarray(points)
+        if p.dtype != POINT_RGB:
+            raise LmonoError("points must be a POINT_RGB array")
+        stats = np.zeros(8, np.int64)
+        _raise_coded(self.ctx, self.ctx.L.lmono_sor_filter(self.ctx.h, self.h, p.ctypes.data if len(p) else None, len(p), stats.ctypes.data))
+        self.stats = stats
+        return stats
+
+    def filter_d(self, ptr, n):
+        """n lmono_point_rgb records in device memory."""
+        stats = np.zeros(8, np.int64)
+        _raise_coded(self.ctx, self.ctx.L.lmono_sor_filter_d(self.ctx.h, self.h, C.c_void_p(int(ptr)), int(n), stats.ctypes.data))
+        self.stats = stats
+        return stats
+
+    @staticmethod
+    def filter_frames(filters, builders):
+        """The world-frame cloud of each builder's last frame through its filter, one launch per phase for all; returns stats [n][8]."""
+        n = len(filters)
+        if n == 0 or len(builders) != n:
+            raise LmonoError("one builder per filter")
+        ctx = filters[0].ctx
+        fh = (C.c_void_p * n)(*[f.h for f in filters]); bh = (C.c_void_p * n)(*[b.h for b in builders])
+        stats = np.zeros((n, 8), np.int64)
+        _raise_coded(ctx, ctx.L.lmono_sor_filter_frames(ctx.h, n, fh, bh, stats.ctypes.data))
+        for f, s in zip(filters, stats):
+            f.stats = s.copy()
+        return stats
+
+    def cloud(self):
+        """The kept points of the last call, in input order."""
+        n = int(_raise_coded(self.ctx, self.ctx.L.lmono_sor_cloud(self.ctx.h, self.h, None, 0)))
+        out = np.zeros(max(n, 1), POINT_RGB)
+        _raise_coded(self.ctx, self.ctx.L.lmono_sor_cloud(self.ctx.h, self.h, out.ctypes.data, n))
+        return out[:n]
+
+    def scores(self):
+        """Diagnostic view of the last call, per input point: keep [n] uint8 and v [n] uint32 (0xffffffff: isolated or rejected)."""
+        n = int(_raise_coded(self.ctx, self.ctx.L.lmono_sor_scores(self.ctx.h, self.h, None, None, 0)))
+        keep = np.zeros(max(n, 1), np.uint8); v = np.zeros(max(n, 1), np.uint32)
+        _raise_coded(self.ctx, self.ctx.L.lmono_sor_scores(self.ctx.h, self.h, keep.ctypes.data, v.ctypes.data, n))
+        return keep[:n], v[:n]
+
+    def threshold(self):
+        """mean, sqrt(var), thr of the last call in v units (2^-16 m, summed over the mean_k distances)."""
+        out = np.zeros(3, np.float64)
+        _raise_coded(self.ctx, self.ctx.L.lmono_sor_threshold(self.ctx.h, self.h, out.ctypes.data))
+        return out
+
+    def diag(self):
+        """Measurement view of the last call: rings scanned summed over the valid points, points scored by the radix select."""
+        out = np.zeros(2, np.int64)
+        _raise_coded(self.ctx, self.ctx.L.lmono_sor_diag(self.ctx.h, self.h, out.ctypes.data))
+        return out
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.ctx.L.lmono_sor_destroy(self.h)
             self.h = None
 
     def __del__(self):

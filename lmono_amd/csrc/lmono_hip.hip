@@ -353,6 +353,7 @@ template <typename H> static int batch_handle_fault(const lmono_ctx *c, int s, H
 #include "mapping_abi.hip"
 #include "colour_abi.hip"
 #include "voxel_map_abi.hip"
+#include "sor_abi.hip"
 #include "track_abi.hip"
 #include "keyframe_abi.hip"
 #include "pnp_abi.hip"

@@ -417,6 +417,9 @@ public:
     // 6c-2): once set, processMapping() also folds the queued frame into a device-resident voxel map, before the every-tenth-frame clear.
     void setVoxelMap(float leaf, int64_t max_voxels);
     std::vector<lmono_point_rgb> voxelMap();                 // one point per voxel, ascending key order (empty when not set)
+    // The pcl::StatisticalOutlierRemoval the reference carries commented out in front of that grid (Map_Builder.cc:24-29), as this project
+    // defines it: once set, the queued frame goes through the filter on the device and the voxel map takes the kept points.
+    void setOutlierFilter(int mean_k, double stddev_mul, float cell = 0.1f, int max_rings = 8);
     std::vector<uint8_t> depthMap();                         // filled depth map of the last frame (topic depth_map before COLORMAP_JET)
     int map_index = 0;
 private:
@@ -426,6 +429,7 @@ private:
     // lmono_voxel_map_* entry points (the CPU baseline of the frame loop) still links
     // (fold_ captures this: a MapBuilder is neither copied nor moved, see the deleted copy operations above)
     std::shared_ptr<lmono_voxel_map> vm_;
+    std::shared_ptr<lmono_sor> sor_;
     std::function<void()> fold_;
     lmono_camera cam_;
     bool save_map_, pending_ = false;

@@ -4,9 +4,10 @@
 // -> MapBuilder::associateToMap -> processMapping; writes <out>/rgb_map<index>.ply every 10 frames and the timing log
 // <out>/mapping_recorder.txt, and dumps the products of the last frame (<out>/depth_last.u8, <out>/cloud_cam_last.bin,
 // <out>/cloud_world_last.bin) for inspection.
-//   map_build <sequence_dir> <trajectory.txt> <out_dir> [n_frames] [width height fx fy cx cy] [voxel=LEAF[:MAX_VOXELS]]
+//   map_build <sequence_dir> <trajectory.txt> <out_dir> [n_frames] [width height fx fy cx cy] [sor=K:MULT[:CELL:RINGS]] [voxel=LEAF[:MAX_VOXELS]]
 // With the trailing voxel= argument every frame is also folded into a voxel-grid map, written at the end as
-// <out>/rgb_map_voxel.ply; without it nothing changes.
+// <out>/rgb_map_voxel.ply; without it nothing changes.  With sor= in front of it every frame passes the statistical outlier removal
+// (CELL 0.1 and RINGS 8 unless given) on its way into that map.
 #include "kitti_io.hpp"
 #include "lmono_host.hpp"
 
@@ -46,7 +47,15 @@ int main(int argc, char **argv)
         if (!(voxel_leaf > 0.0f)) { std::fprintf(stderr, "map_build: voxel=LEAF[:MAX_VOXELS] needs a leaf > 0\n"); return 2; }
         argc--;
     }
-    if (argc < 4) { std::fprintf(stderr, "usage: map_build <sequence_dir> <trajectory.txt> <out_dir> [n_frames] [width height fx fy cx cy] [voxel=LEAF[:MAX_VOXELS]]\n"); return 2; }
+    int sor_k = 0, sor_rings = 8;
+    double sor_mul = 1.0;
+    float sor_cell = 0.1f;
+    if (argc > 4 && std::strncmp(argv[argc - 1], "sor=", 4) == 0) {
+        const int got = std::sscanf(argv[argc - 1] + 4, "%d:%lf:%f:%d", &sor_k, &sor_mul, &sor_cell, &sor_rings);
+        if ((got != 2 && got != 4) || sor_k < 1 || !(voxel_leaf > 0.0f)) { std::fprintf(stderr, "map_build: sor=K:MULT[:CELL:RINGS] needs K >= 1 and a voxel= argument behind it\n"); return 2; }
+        argc--;
+    }
+    if (argc < 4) { std::fprintf(stderr, "usage: map_build <sequence_dir> <trajectory.txt> <out_dir> [n_frames] [width height fx fy cx cy] [sor=K:MULT[:CELL:RINGS]] [voxel=LEAF[:MAX_VOXELS]]\n"); return 2; }
     const std::string seq = argv[1], traj = argv[2], out = argv[3];
     int n_frames = argc > 4 ? std::atoi(argv[4]) : -1;
     lmono_camera cam = { 1241, 376, 718.856, 718.856, 607.1928, 185.2157, 0, 0, 0, 0, 5, 0, 0 };   // kitti00_cam.yaml, kitti_map_config_00.yaml
@@ -66,6 +75,7 @@ int main(int argc, char **argv)
         HipContext hip(0);
         MapBuilder map_builder(hip, cam, true, out);
         if (voxel_leaf > 0.0f) map_builder.setVoxelMap(voxel_leaf, voxel_max);
+        if (sor_k > 0) map_builder.setOutlierFilter(sor_k, sor_mul, sor_cell, sor_rings);
         MappingLog recorder(out + "/mapping_recorder.txt");
         if (!recorder.ok()) { std::fprintf(stderr, "cannot write into %s\n", out.c_str()); return 1; }
         std::vector<uint8_t> image;

@@ -13,8 +13,20 @@ void MapBuilder::setVoxelMap(float leaf, int64_t max_voxels)
     vm_ = std::shared_ptr<lmono_voxel_map>(vm, lmono_voxel_map_destroy);
     fold_ = [this] {
         lmono_voxel_map *m = vm_.get();
+        if (lmono_sor *f = sor_.get()) {                                   // :24-29 in front of :82-98
+            hip_.check(lmono_sor_filter_frames(hip_.get(), 1, &f, &mb_, nullptr), "lmono_sor_filter_frames");
+            hip_.check(lmono_voxel_map_insert_filtered(hip_.get(), 1, &m, &f, nullptr), "lmono_voxel_map_insert_filtered");
+            return;
+        }
         hip_.check(lmono_voxel_map_insert_frames(hip_.get(), 1, &m, &mb_, nullptr), "lmono_voxel_map_insert_frames");
     };
+}
+
+void MapBuilder::setOutlierFilter(int mean_k, double stddev_mul, float cell, int max_rings)
+{
+    lmono_sor *f = lmono_sor_create(hip_.get(), (int64_t)cam_.width * cam_.height, mean_k, stddev_mul, cell, max_rings);
+    if (!f) throw std::runtime_error(std::string("lmono_sor_create: ") + lmono_last_error(hip_.get()));
+    sor_ = std::shared_ptr<lmono_sor>(f, lmono_sor_destroy);
 }
 
 std::vector<lmono_point_rgb> MapBuilder::voxelMap()

@@ -35,7 +35,7 @@ struct BatchView {
     int *seg_hist;           // [(total >> 10) + n_scans + 1][64] ring histogram of every 1024-point segment, then its exclusive prefix within the scan
     int *scan_ends;          // [n_scans][2] first / last valid input point (-1: none)
     int *scan_half;          // [n_scans] first input point past the half sweep (INT_MAX: none)
-    float *scan_ori;         // [n_scans][2] start / end azimuth of the sweep
+    float *scan_ori;         // [n_scans][4] start / end azimuth of the sweep, unit vector of its start direction (ring_decide.hpp)
     int *ring_begin;         // [n_scans][65]
     int *n_cloud;            // [n_scans]
     int *status;             // [n_scans]

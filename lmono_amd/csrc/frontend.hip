@@ -3,7 +3,8 @@
 //
 // Five kernel stages per batch of scans over HBM-resident SoA/float4 pools:
 //   k_ring_*     filter, ring id, azimuth, stable counting sort into ring-major order: four tile-parallel launches (ends, tag,
-//                offsets, scatter); every wave owns a 1024-point segment in both passes, no barriers inside the passes
+//                offsets, scatter); every wave owns a 1024-point segment in both passes, no barriers inside the passes; the tag
+//                pass decides ring and half sweep without an arctangent (ring_decide.hpp), fp64 forms inside the guard bands
 //   k_curvature  one workgroup per 1024-point tile: LDS tile with +-5 halo, curvature and neighbour-gap flags
 //   k_select     one wave per (scan, ring): per-sector edge/planar selection as repeated 64-lane arg-max/arg-min (DPP
 //                reductions) over register-resident (curvature, index) keys with neighbour suppression (no sort needed);
@@ -14,6 +15,7 @@
 //                azimuth bin) index of the two "last" clouds (the steps of line_index.hip) built while their points pass through
 // Arithmetic is float/double exactly as the CPU restatement evaluates it (compiled with -ffp-contract=off).
 #include "batch.hpp"
+#include "ring_decide.hpp"
 
 namespace lmono {
 
@@ -39,13 +41,13 @@ __device__ __forceinline__ int ring_of(float angle, int n_lines, bool &discard)
 
 __device__ __forceinline__ bool point_valid(const float4 &p, float mr2)
 {
-    return isfinite(p.x) && isfinite(p.y) && isfinite(p.z) && !(p.x * p.x + p.y * p.y + p.z * p.z < mr2);
+    return isfinite(p.x) & isfinite(p.y) & isfinite(p.z) & !(p.x * p.x + p.y * p.y + p.z * p.z < mr2);
 }
 
 // ------------------------------------------------------------------------------------------------
 // Ring sort = stable counting sort of a scan's valid points into ring-major order, as four tile-parallel launches (round 3: one
 // workgroup per scan kept ~2 long workgroups per wave slot -- a third of the launch was its tail -- and made one scan alone take 1.1 ms):
-//   k_ring_ends     per scan: first / last valid point -> start / end azimuth of the sweep
+//   k_ring_ends     per scan: first / last valid point -> start / end azimuth of the sweep, unit vector of its start direction
 //   k_ring_tag      per 4096-point tile: ring id of every point, a [64]-ring histogram per 1024-point wave segment, the first point
 //                   past the half sweep, the last valid point
 //   k_ring_offsets  per scan: exclusive prefix of the segment histograms in segment order (= input order) per ring, ring_begin
@@ -54,8 +56,6 @@ __device__ __forceinline__ bool point_valid(const float4 &p, float mr2)
 constexpr int kRtT = 256, kRtW = kRtT / 64;    // threads / waves of a tile workgroup
 constexpr int kRtSeg = 1024;                   // points per wave segment (4 rounds of 256)
 constexpr int kRtTile = kRtSeg * kRtW;
-constexpr float kRingGuardDeg = 2e-3f;         // 20x the single-precision angle's error bound
-constexpr float kHalfGuardRad = 4e-5f;         // 20x (the float subtractions near 3 pi / 2 round to 5e-7)
 
 // points of scan s the ring sort looks at: the scan's slot, or the first n_limit of it (one-scan launches of the online stream: the rest of
 // the slot is padding)
@@ -97,7 +97,10 @@ __global__ __launch_bounds__(256) void k_ring_ends(BatchView b)
     }
     if (tid == 0) {
         const float4 p0 = in[s_first];
-        b.scan_ori[s * 2] = (float)(-det_atan2((double)p0.y, (double)p0.x));
+        b.scan_ori[s * 4] = (float)(-det_atan2((double)p0.y, (double)p0.x));
+        float ux, uy;
+        ring_start_dir(p0.x, p0.y, ux, uy);
+        b.scan_ori[s * 4 + 2] = ux; b.scan_ori[s * 4 + 3] = uy;
         b.scan_ends[s * 2] = s_first; b.scan_ends[s * 2 + 1] = -1;
         b.scan_half[s] = INT_MAX;
     }
@@ -116,8 +119,10 @@ __global__ __launch_bounds__(kRtT) void k_ring_tag(BatchView b)
     s_hist[wave][lane] = 0;
     __syncthreads();
     const float mr2 = b.min_range * b.min_range;
-    const float startOri = b.scan_ori[s * 2];
+    const float startOri = b.scan_ori[s * 4];
+    const float ux = b.scan_ori[s * 4 + 2], uy = b.scan_ori[s * 4 + 3];      // start direction (ring_start_dir)
     const int n_lines = b.n_lines;
+    const RingMap map = ring_map(n_lines);
     int lh = INT_MAX, ll = -1;
     const int c_lo = t0 + wave * kRtSeg, c_hi = min(c_lo + kRtSeg, n);
     // four points per thread and round, and the NEXT round's four requested before this round's are worked on (unconditional loads, index clamped
@@ -136,30 +141,17 @@ __global__ __launch_bounds__(kRtT) void k_ring_tag(BatchView b)
             const int i = r0 + 64 * q + lane;
             const float4 p = pq[q];
             int id = -1;
-            if (i < c_hi && point_valid(p, mr2)) {
+            if ((i < c_hi) & point_valid(p, mr2)) {
                 ll = i;                        // i grows with q and r0: the lane's last valid point so far
-                // Ring id and the half-sweep test decide between alternatives, so single-precision angles settle them whenever the
-                // answer is the same over the whole error interval (ring_of is monotone in the angle; the half test has three
-                // thresholds); the fp64 forms run only for the points that fall inside a guard band (and for x = y = 0).
+                // Ring id and the half-sweep test decide between alternatives: ring_decide.hpp settles them without an arctangent (an odd
+                // polynomial in z / rho, the signs of a dot and a cross product with the start direction) and without a branch whenever the
+                // point is farther than a guard from every threshold; the fp64 forms run only for the points inside a guard band (and for
+                // x = y = 0).  The points of a round stay behind one another: with the four fast decisions side by side the compiler paired
+                // their float operations (v_pk_mul_f32 / v_pk_add_f32), took 100 registers (4 waves per SIMD) and the pass lost its whole gain.
                 const float q2 = p.x * p.x + p.y * p.y;
-                bool exact = !(q2 > 1e-30f);
-                bool discard = false, past_half = false;
-                if (!exact) {
-                    const float af = atanf(p.z * __frsqrt_rn(q2)) * 57.29577951308232f;      // |error| < 1e-4 deg (2 ulp atanf, 1 ulp rsqrt)
-                    bool d0, d1;
-                    const int r0i = ring_of(af - kRingGuardDeg, n_lines, d0), r1i = ring_of(af + kRingGuardDeg, n_lines, d1);
-                    if (d0 != d1 || (!d0 && r0i != r1i)) exact = true;
-                    else { discard = d0; id = d0 ? -1 : r0i; }
-                }
-                if (!exact && !discard) {
-                    const float dr = -atan2f(p.y, p.x) - startOri;                               // |error| < 2e-6 rad
-                    float dw = dr;
-                    if (dr < -(float)LM_PI_2) dw = dr + 2.0f * (float)LM_PI;
-                    else if (dr > 1.5f * (float)LM_PI) dw = dr - 2.0f * (float)LM_PI;
-                    if (fabsf(dr + (float)LM_PI_2) < kHalfGuardRad || fabsf(dr - 1.5f * (float)LM_PI) < kHalfGuardRad || fabsf(dw - (float)LM_PI) < kHalfGuardRad) exact = true;
-                    else past_half = dw > (float)LM_PI;
-                }
-                if (exact) {
+                bool past_half;
+                if (!ring_half_fast(p.x, p.y, p.z, q2, __frsqrt_rn(q2) /* within 1 ulp */, map, ux, uy, id, past_half)) {
+                    bool discard;
                     const float angle = (float)(det_atan((double)p.z / sqrt((double)(p.x * p.x + p.y * p.y))) * 180.0 / LM_PI);
                     const int r = ring_of(angle, n_lines, discard);
                     id = -1; past_half = false;
@@ -201,11 +193,11 @@ __global__ __launch_bounds__(64) void k_ring_offsets(BatchView b)
     const int nseg = (n + kRtSeg - 1) / kRtSeg, r = threadIdx.x;
     if (r == 0) {                                  // end azimuth of the sweep from the last valid point k_ring_tag found
         const float4 p1 = b.in[off + b.scan_ends[s * 2 + 1]];
-        const float startOri = b.scan_ori[s * 2];
+        const float startOri = b.scan_ori[s * 4];
         float endOri = (float)((double)(float)(-det_atan2((double)p1.y, (double)p1.x)) + 2.0 * LM_PI);
         if ((double)(endOri - startOri) > 3.0 * LM_PI) endOri = (float)((double)endOri - 2.0 * LM_PI);
         else if ((double)(endOri - startOri) < LM_PI) endOri = (float)((double)endOri + 2.0 * LM_PI);
-        b.scan_ori[s * 2 + 1] = endOri;
+        b.scan_ori[s * 4 + 1] = endOri;
     }
     int *h = b.seg_hist + ((size_t)(off >> 10) + (size_t)s) * 64 + r;
     int run = 0;
@@ -242,7 +234,7 @@ __global__ __launch_bounds__(kRtT) void k_ring_scatter(BatchView b)
     const int c_lo = t0 + wave * kRtSeg, c_hi = min(c_lo + kRtSeg, n);
     s_pos[wave][lane] = c_lo < n ? b.seg_hist[((size_t)(off >> 10) + (size_t)s + (size_t)(c_lo >> 10)) * 64 + lane] + b.ring_begin[s * 65 + lane] : 0;
     __syncthreads();
-    const float startOri = b.scan_ori[s * 2], endOri = b.scan_ori[s * 2 + 1];
+    const float startOri = b.scan_ori[s * 4], endOri = b.scan_ori[s * 4 + 1];
     const int half = b.scan_half[s];
     for (int r0 = c_lo; r0 < c_hi; r0 += 256) {
         int id[4], dstp[4];

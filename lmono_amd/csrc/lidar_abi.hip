@@ -63,7 +63,7 @@ extern "C" lmono_scan_batch *lmono_batch_create(lmono_ctx *c, int n_cap, int64_t
     ok = ok && m.alloc(b->off_d, N + 1);
     ok = ok && m.alloc(v.cloud, T) && m.alloc(v.curv, T) && m.alloc(v.label, T) && m.alloc(v.gap, T);
     ok = ok && m.alloc(v.ring_tmp, T);
-    ok = ok && m.alloc(v.seg_hist, ((T >> 10) + N + 1) * 64) && m.alloc(v.scan_ends, N * 2) && m.alloc(v.scan_half, N) && m.alloc(v.scan_ori, N * 2);
+    ok = ok && m.alloc(v.seg_hist, ((T >> 10) + N + 1) * 64) && m.alloc(v.scan_ends, N * 2) && m.alloc(v.scan_half, N) && m.alloc(v.scan_ori, N * 4);
     ok = ok && m.alloc(v.ring_begin, N * 65) && m.alloc(v.n_cloud, N) && m.alloc(v.status, N);
     ok = ok && m.alloc(v.sel_sharp, N * 64 * 6 * 20) && m.alloc(v.sel_sharp_n, N * 64 * 6);
     ok = ok && m.alloc(v.sel_flat, N * 64 * 6 * 4) && m.alloc(v.sel_flat_n, N * 64 * 6);

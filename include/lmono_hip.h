@@ -445,9 +445,22 @@ int              lmono_voxel_map_insert_frames(lmono_ctx *, int n, lmono_voxel_m
 int64_t          lmono_voxel_map_size(lmono_ctx *, lmono_voxel_map *);
 /* one point per voxel in ascending key order; returns the voxel count (copies when out_h != NULL) */
 int64_t          lmono_voxel_map_read(lmono_ctx *, lmono_voxel_map *, lmono_point_rgb *out_h, int64_t cap);
-/* diagnostic view: keys ascending, counts, sums [n][6] (offsets x y z in 2^-16 leaf, colour r g b); any output may be NULL */
+/* diagnostic view: keys ascending, counts, sums [n][6] (offsets x y z in 2^-16 leaf, colour r g b); any output may be NULL.  counts are
+ * reported modulo 2^32 (the table's are 64-bit): composed counts above that are out of this view's scope */
 int64_t          lmono_voxel_map_cells(lmono_ctx *, lmono_voxel_map *, uint64_t *keys_h, uint32_t *counts_h, uint64_t *sums_h, int64_t cap);
 int              lmono_voxel_map_tile(void);   /* points a workgroup of the insert sums on chip (tests place point counts around it) */
+/* Compose: fold n_src voxel maps, each moved by a rigid transform (row-major 3 x 4 doubles, applied as given), into
+ * dst.  Every occupied source voxel goes where its output point (what read returns) lands after the transform, with its count as weight,
+ * count * offset as offset sums and its own colour sums; all integers, so dst holds the same bytes for every order and split of the
+ * sources, and is an ordinary voxel map afterwards (it takes inserts and can be a source).  Sources are not modified; their leaves and
+ * dst's may differ.  stats (optional) [6]: source voxels moved, source voxels rejected (moved point non-finite or outside the cell range),
+ * points moved (sum of counts), points rejected, voxels new in dst, voxels in dst afterwards.  LMONO_EINVAL before any launch: a NULL or
+ * foreign handle, dst among srcs, a source named twice, a non-finite transform entry, n_src < 0 (or > 65535, or more than 2^30 source
+ * voxels).  A call that needs more than max_voxels voxels returns LMONO_ECAPACITY, leaves nothing of ANY source in dst (one destination:
+ * all or nothing) and dst full until cleared, exactly as an insert; stats are then 0 0 0 0 0 and the size before the call.  n_src == 0
+ * or only empty sources: a successful no-op with no launch, unless dst is full (LMONO_ECAPACITY: the full map wins). */
+int              lmono_voxel_map_compose(lmono_ctx *, lmono_voxel_map *dst, int n_src, lmono_voxel_map *const *srcs,
+                                         const double *transforms /* [n_src][12] */, int64_t *stats /* optional [6] */);
 
 /* ---- statistical outlier removal in front of the voxel map ---------------------------------------------------
  * The pcl::StatisticalOutlierRemoval<pcl::PointXYZRGB> with setMeanK(100) / setStddevMulThresh(1.0) that MapBuilder::processMapping

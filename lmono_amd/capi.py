@@ -17,7 +17,7 @@ SYMBOLS = [
     "lmono_map_builder_create", "lmono_map_builder_destroy", "lmono_associate_to_map", "lmono_associate_to_map_batch", "lmono_map_builder_depth",
     "lmono_map_builder_cloud", "lmono_map_builder_map", "lmono_map_builder_clear",
     "lmono_voxel_map_create", "lmono_voxel_map_destroy", "lmono_voxel_map_clear", "lmono_voxel_map_insert", "lmono_voxel_map_insert_d", "lmono_voxel_map_insert_frames",
-    "lmono_voxel_map_size", "lmono_voxel_map_read", "lmono_voxel_map_cells", "lmono_voxel_map_tile",
+    "lmono_voxel_map_size", "lmono_voxel_map_read", "lmono_voxel_map_cells", "lmono_voxel_map_tile", "lmono_voxel_map_compose",
     "lmono_sor_create", "lmono_sor_destroy", "lmono_sor_filter", "lmono_sor_filter_d", "lmono_sor_filter_frames", "lmono_sor_cloud", "lmono_sor_scores",
     "lmono_sor_threshold", "lmono_sor_diag", "lmono_voxel_map_insert_filtered",
     "lmono_tracker_create", "lmono_tracker_destroy", "lmono_tracker_reset", "lmono_tracker_track", "lmono_tracker_track_batch", "lmono_tracker_pyramid",
@@ -807,6 +807,7 @@ def _voxel_map_prototypes(L):
     L.lmono_voxel_map_cells.restype = C.c_int64
     L.lmono_voxel_map_cells.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
     L.lmono_voxel_map_tile.restype = C.c_int
+    L.lmono_voxel_map_compose.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
 
 
 class VoxelMap:
@@ -903,6 +904,20 @@ class VoxelMap:
         _raise_coded(ctx, ctx.L.lmono_voxel_map_insert_filtered(ctx.h, n, mh, fh, stats.ctypes.data))
         return stats
 
+    def compose(self, sources, transforms, stats=False):
+        """Fold the voxel maps `sources`, each moved by its rigid transform ([n][12] or [n][3][4] float64, row-major 3 x 4, applied as given),
+        into this map (lmono_voxel_map_compose): every source voxel with its count as weight.  All or nothing; the sources are
+        not modified.  With stats=True returns [source voxels moved, source voxels rejected, points moved, points rejected, voxels new,
+        voxels afterwards]."""
+        n = len(sources)
+        t = np.ascontiguousarray(transforms, np.float64).reshape(-1)
+        if t.size != 12 * n:
+            raise LmonoError("one 3 x 4 transform per source")
+        sh = (C.c_void_p * max(n, 1))(*[s.h for s in sources])
+        st = np.zeros(6, np.int64)
+        self._check(self.ctx.L.lmono_voxel_map_compose(self.ctx.h, self.h, n, sh, t.ctypes.data if n else None, st.ctypes.data))
+        return st if stats else None
+
     def clear(self):
         self._check(self.ctx.L.lmono_voxel_map_clear(self.ctx.h, self.h))
 
@@ -910,6 +925,93 @@ class VoxelMap:
         if getattr(self, "h", None):
             self.ctx.L.lmono_voxel_map_destroy(self.h)
             self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _pose_matrix(tq):
+    """[R | t] of a pose (x y z, qx qy qz qw) in fp64; the quaternion is normalised first."""
+    tq = np.asarray(tq, np.float64).reshape(7)
+    x, y, z, w = tq[3:] / np.sqrt((tq[3:] * tq[3:]).sum())
+    R = np.array([[1.0 - 2.0 * (y * y + z * z), 2.0 * (x * y - z * w), 2.0 * (x * z + y * w)],
+                  [2.0 * (x * y + z * w), 1.0 - 2.0 * (x * x + z * z), 2.0 * (y * z - x * w)],
+                  [2.0 * (x * z - y * w), 2.0 * (y * z + x * w), 1.0 - 2.0 * (x * x + y * y)]], np.float64)
+    return R, tq[:3].copy()
+
+
+def pose_delta(inserted_tq, corrected_tq):
+    """The rigid transform that carries what was mapped under the pose `inserted_tq` to where the pose `corrected_tq` puts it:
+    D = T_corrected * T_inserted^-1, as [12] float64 (row-major 3 x 4), for VoxelMap.compose.  Poses are (x y z, qx qy qz qw).  With
+    q / |q| = (x, y, z, w) and
+        R(q) = [[1 - 2(yy + zz), 2(xy - zw), 2(xz + yw)], [2(xy + zw), 1 - 2(xx + zz), 2(yz - xw)], [2(xz - yw), 2(yz + xw), 1 - 2(xx + yy)]]
+    the result is D_R = R_c R_i^T (element [a][b] = (R_c[a][0] R_i[b][0] + R_c[a][1] R_i[b][1]) + R_c[a][2] R_i[b][2]) and
+    D_t = t_c - D_R t_i (element a = t_c[a] - ((D_R[a][0] t_i[0] + D_R[a][1] t_i[1]) + D_R[a][2] t_i[2])), all in numpy fp64."""
+    Ri, ti = _pose_matrix(inserted_tq)
+    Rc, tc = _pose_matrix(corrected_tq)
+    D = np.zeros((3, 4), np.float64)
+    for a in range(3):
+        for b in range(3):
+            D[a, b] = (Rc[a, 0] * Ri[b, 0] + Rc[a, 1] * Ri[b, 1]) + Rc[a, 2] * Ri[b, 2]
+        D[a, 3] = tc[a] - ((D[a, 0] * ti[0] + D[a, 1] * ti[1]) + D[a, 2] * ti[2])
+    return D.reshape(12)
+
+
+class SubmapAtlas:
+    """A sequence as submaps, so that the global map can follow a corrected trajectory: every `frames_per_submap` frames go
+    into a voxel map of their own (leaf_sub), anchored at the pose of its first frame.  compose(dst, corrected poses) moves every submap
+    rigidly by pose_delta(anchor pose, corrected anchor pose) and folds them into dst in one lmono_voxel_map_compose call."""
+
+    def __init__(self, ctx, frames_per_submap, leaf_sub=0.05, max_voxels_sub=1 << 20):
+        if int(frames_per_submap) < 1:
+            raise LmonoError("frames_per_submap must be >= 1")
+        self.ctx = ctx
+        self.frames_per_submap = int(frames_per_submap)
+        self.leaf_sub = float(leaf_sub)
+        self.max_voxels_sub = int(max_voxels_sub)
+        self.submaps = []
+        self.anchor_frames = []
+        self.anchor_poses = []
+        self.n_frames = 0
+
+    @property
+    def anchors(self):
+        """Frame indices [m] int64 and poses [m][7] float64 (as inserted) of the submaps' first frames."""
+        return np.array(self.anchor_frames, np.int64), np.array(self.anchor_poses, np.float64).reshape(-1, 7)
+
+    def insert_frame(self, source, pose_tq):
+        """One frame, already in the world frame of `pose_tq` (x y z, qx qy qz qw): the last frame of a MapBuilder, the last output of an
+        OutlierFilter, or a POINT_RGB array.  Returns the insert's stats."""
+        pose = np.asarray(pose_tq, np.float64).reshape(7)
+        if self.n_frames % self.frames_per_submap == 0:
+            self.submaps.append(VoxelMap(self.ctx, leaf=self.leaf_sub, max_voxels=self.max_voxels_sub))
+            self.anchor_frames.append(self.n_frames)
+            self.anchor_poses.append(pose.copy())
+        sub = self.submaps[-1]
+        self.n_frames += 1
+        if isinstance(source, MapBuilder):
+            return sub.insert_frame(source)
+        if isinstance(source, OutlierFilter):
+            return VoxelMap.insert_filtered([sub], [source])[0]
+        return sub.insert(source)
+
+    def compose(self, dst, corrected_poses_tq, stats=False):
+        """corrected_poses_tq: one pose per anchor, or one per frame (the anchors' are taken).  dst: a VoxelMap, usually fresh."""
+        P = np.asarray(corrected_poses_tq, np.float64).reshape(-1, 7)
+        if len(P) == self.n_frames and self.n_frames != len(self.submaps):
+            P = P[np.array(self.anchor_frames, np.int64)]
+        if len(P) != len(self.submaps):
+            raise LmonoError("corrected poses: one per anchor (%d) or one per frame (%d)" % (len(self.submaps), self.n_frames))
+        T = np.array([pose_delta(a, p) for a, p in zip(self.anchor_poses, P)], np.float64).reshape(-1, 12)
+        return dst.compose(self.submaps, T, stats=stats)
+
+    def close(self):
+        for s in self.submaps:
+            s.close()
+        self.submaps = []
 
     def __del__(self):
         try:

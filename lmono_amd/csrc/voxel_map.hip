@@ -16,6 +16,8 @@
 // 3.3 for 64 first frames, profiles/r11.)  Once the failure word is set, or the counter has reached max_voxels, no further slot is claimed, and every
 // probe loop ends after `slots` steps: no wave waits on the table, whatever is in it.
 // Sums are integers, so the content is the same bytes for every insertion order, split, batch and launch geometry.
+// Whole maps are folded into another one, each under a rigid transform and every voxel with its weight, by k_vm_move_find / k_vm_move_accum below
+// (DESIGN.md 6c-4): the same claim, ticket and refusal rules, 64-bit entries.
 #pragma once
 #include "common.hpp"
 #include "colour.hip"
@@ -178,6 +180,76 @@ __global__ __launch_bounds__(kVmT) void k_vm_compact(const VmRec *rec, unsigned 
     if (r.key == kVmEmpty || r.w[0] == 0) return;
     const unsigned at = atomicAdd(n, 1u);
     if (at < cap) out[at] = r;
+}
+
+// ---- compose: whole voxel maps, each under a rigid transform, folded into one destination ----
+// The sources' occupied records (k_vm_compact, no order) are the input; blockIdx.y = source.  The plain form -- one probe and one entry per record --
+// because a map's records are one per cell already: at comparable leaves about one source voxel lands in a destination voxel per tile, so a
+// workgroup table would find nothing to merge (scripts/voxel_compose_bench.py reports the ratio).  Entries and addends are 64-bit: count * offset
+// passes 32 bits at a count above 65536.
+struct VmMoveEnt { unsigned long long slot, w[7]; };    // slot: kVmNoSlot when the voxel is rejected or found no slot
+struct VmMoveSrc {
+    const VmRec *rec;                      // the source's occupied records
+    unsigned n;
+    float leaf;
+    long long ent_off;                     // this source's part of the call's entries
+    double T[12];
+};
+static_assert(sizeof(VmMoveEnt) == 64, "compose entry layout");
+
+// stat: [0] voxels moved, [1] voxels rejected, [2] points moved, [3] points rejected.  j: the destination (pts, n, ent, tile_n unused);
+// j.res as in k_vm_find: [0] failure word, [3] occupancy after the call
+__global__ __launch_bounds__(kVmT) void k_vm_move_find(const VmJob j, const VmMoveSrc *srcs, VmMoveEnt *ent, unsigned long long *stat)
+{
+    const VmMoveSrc &s = srcs[blockIdx.y];
+    const unsigned base = blockIdx.x * kVmTile;
+    if (base >= s.n) return;
+    __shared__ unsigned l_claims, l_vrej;
+    __shared__ unsigned long long l_pts, l_prej;
+    const int tid = threadIdx.x;
+    if (tid == 0) { l_claims = 0; l_vrej = 0; l_pts = 0; l_prej = 0; }
+    __syncthreads();
+    for (int r = 0; r < kVmTile / kVmT; r++) {
+        const unsigned i = base + r * kVmT + tid;
+        if (i >= s.n) continue;
+        const VmRec rec = s.rec[i];
+        uint64_t key = kVmEmpty, add[7] = { 0, 0, 0, 0, 0, 0, 0 };
+        const bool ok = vm_move(rec, s.leaf, s.T, j.inv, key, add);
+        VmMoveEnt e;
+        e.slot = ok ? vm_find_or_claim(j, key, &l_claims) : kVmNoSlot;
+        for (int w = 0; w < 7; w++) e.w[w] = add[w];
+        ent[s.ent_off + i] = e;
+        if (ok) atomicAdd(&l_pts, (unsigned long long)rec.w[0]);
+        else { atomicAdd(&l_vrej, 1u); atomicAdd(&l_prej, (unsigned long long)rec.w[0]); }
+    }
+    __syncthreads();
+    if (tid == 0) {
+        const unsigned left = s.n - base, in_tile = left < kVmTile ? left : kVmTile;
+        // one block of tickets for the slots this workgroup claimed: a ticket >= max_voxels refuses the call
+        if (l_claims && atomicAdd(j.occ, l_claims) + l_claims > j.max_voxels) atomicExch(j.res, 1);
+        if (in_tile - l_vrej) atomicAdd(stat + 0, (unsigned long long)(in_tile - l_vrej));
+        if (l_vrej) atomicAdd(stat + 1, (unsigned long long)l_vrej);
+        if (l_pts) atomicAdd(stat + 2, l_pts);
+        if (l_prej) atomicAdd(stat + 3, l_prej);
+    }
+}
+
+__global__ __launch_bounds__(kVmT) void k_vm_move_accum(const VmJob j, const VmMoveSrc *srcs, const VmMoveEnt *ent)
+{
+    const VmMoveSrc &s = srcs[blockIdx.y];
+    const unsigned base = blockIdx.x * kVmTile;
+    if (base >= s.n) return;
+    if (blockIdx.x == 0 && threadIdx.x == 0) j.res[3] = (int)*j.occ;      // every source's first workgroup writes the same value
+    if (j.res[0] != 0) return;                 // the sources do not fit: nothing of the call enters the map
+    const unsigned left = s.n - base, n = left < kVmTile ? left : kVmTile;
+    const int w = threadIdx.x & 7;
+    for (unsigned e = threadIdx.x >> 3; e < n; e += kVmT / 8) {
+        const VmMoveEnt *en = ent + s.ent_off + base + e;
+        const unsigned long long slot = en->slot;
+        if (slot == kVmNoSlot || w == 0) continue;      // word 0 of a record is its key
+        const unsigned long long v = en->w[w - 1];
+        if (v) atomicAdd((unsigned long long *)&j.rec[slot].w[w - 1], v);
+    }
 }
 
 __global__ __launch_bounds__(kVmT) void k_vm_finish(const VmRec *rec, unsigned n, float leaf, PtRgb *out)

@@ -1,5 +1,5 @@
 // voxel_map.hpp -- the arithmetic of the voxel-grid colour map: cell, in-cell offset, key, hash and output point.
-// One text for the kernels (voxel_map.hip) and for a CPU program (host/voxel_map_test.cpp); every float operation is a single IEEE
+// One text for the kernels (voxel_map.hip) and for the CPU programs (host/voxel_map_test.cpp, host/voxel_compose_test.cpp); every float operation is a single IEEE
 // operation (build with -ffp-contract=off).  The filter is the pcl::VoxelGrid<pcl::PointXYZRGB> that MapBuilder::processMapping
 // left commented out (Map_Builder.cc:82-98); its definition here is this project's own and differs from PCL's in three ways:
 // in-cell offsets are 16-bit fixed point and summed as integers, cells are 64-bit keys with no bounding box (and no int32 limit on the
@@ -59,6 +59,8 @@ LMONO_VM_HD uint64_t vm_mix(uint64_t k)
     return k;
 }
 
+// exact (every conversion and the sum under the division are exact, so the result is the correctly rounded chain of the formula) while
+// s + count / 2 < 2^53; s <= 65535 * count, so while a voxel's count stays below 2^36 -- composed maps (below) reach counts inserts never do
 LMONO_VM_HD float vm_axis_out(int i, uint64_t s, uint64_t count, float leaf)
 {
     return (float)(((double)i + ((double)s + 0.5 * (double)count) / (65536.0 * (double)count)) * (double)leaf);
@@ -75,6 +77,26 @@ LMONO_VM_HD VmPoint vm_point(const VmRec &r, float leaf)
     p.z = vm_axis_out(iz, r.w[3], n, leaf);
     p.bgra = (uint32_t)(r.w[6] / n) | (uint32_t)(r.w[5] / n) << 8 | (uint32_t)(r.w[4] / n) << 16 | 0xff000000u;
     return p;
+}
+
+// ---- composing voxel maps under rigid transforms ----
+// One coordinate of T * p, T a row of a row-major 3 x 4 fp64 transform: fp64 products and sums in exactly this order, one cast
+LMONO_VM_HD float vm_move_axis(const double *row, const VmPoint &p)
+{
+    return (float)(((row[0] * (double)p.x + row[1] * (double)p.y) + row[2] * (double)p.z) + row[3]);
+}
+
+// A voxel r (count c > 0) of a map with leaf leaf_src, moved by T into a map with inv = 1.0f / leaf: its output point goes where a point would, with
+// weight c.  add[0] = c, add[1..3] = c * q, add[4..6] = r's own colour sums (not c * the truncated mean: colour sums are conserved exactly).
+// false when the moved point is rejected (the voxel and its c points are counted, nothing is added).  The products pass 32 bits at c > 65536.
+LMONO_VM_HD bool vm_move(const VmRec &r, float leaf_src, const double *T, float inv, uint64_t &key, uint64_t add[7])
+{
+    const VmPoint p = vm_point(r, leaf_src);
+    int q[3];
+    if (!vm_cell(vm_move_axis(T, p), vm_move_axis(T + 4, p), vm_move_axis(T + 8, p), inv, key, q)) return false;
+    add[0] = r.w[0];
+    for (int a = 0; a < 3; a++) { add[1 + a] = r.w[0] * (uint64_t)q[a]; add[4 + a] = r.w[4 + a]; }
+    return true;
 }
 
 } // namespace lmono

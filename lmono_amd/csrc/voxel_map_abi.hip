@@ -25,6 +25,12 @@ struct lmono_voxel_map {
     VmJob *jobs = nullptr;
     int *results = nullptr;
     int jobs_cap = 0;
+    // per-call scratch of a compose into this map: one entry per source voxel, the source table, [4] 64-bit stats + [4] result ints
+    VmMoveEnt *mv_ent = nullptr;
+    int64_t mv_ent_cap = 0;
+    VmMoveSrc *mv_src = nullptr;
+    int64_t mv_src_cap = 0;
+    unsigned long long *mv_ctl = nullptr;
 };
 
 static constexpr int64_t kVmMaxCall = (int64_t)1 << 30;    // points of one insert
@@ -217,6 +223,72 @@ extern "C" int64_t lmono_voxel_map_read(lmono_ctx *c, lmono_voxel_map *m, lmono_
     HIP_TRY(c, hipMemcpyAsync(out_h, m->rd_pts, sizeof(PtRgb) * recs.size(), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     return m->n_vox;
+}
+
+// fold n_src maps, each moved by its transform, into dst: one k_vm_compact per non-empty source into that source's read buffer,
+// then two launches for all sources.  Ends synchronised.
+extern "C" int lmono_voxel_map_compose(lmono_ctx *c, lmono_voxel_map *dst, int n_src, lmono_voxel_map *const *srcs, const double *transforms, int64_t *stats)
+{
+    const char *who = "lmono_voxel_map_compose";
+    if (!c || !dst || dst->ctx != c || n_src < 0 || (n_src > 0 && (!srcs || !transforms))) return LMONO_EINVAL;
+    if (n_src > 65535) { c->err = std::string(who) + ": more than 65535 sources in one call"; return LMONO_EINVAL; }
+    int64_t total = 0;
+    for (int s = 0; s < n_src; s++) {
+        const int fault = batch_handle_fault(c, s, srcs);
+        if (fault == kHandleForeign) { c->err = std::string(who) + ": bad source handle"; return LMONO_EINVAL; }
+        if (fault == kHandleRepeated || srcs[s] == dst) { c->err = std::string(who) + ": the sources must be distinct, and none of them the destination"; return LMONO_EINVAL; }
+        total += srcs[s]->n_vox;
+    }
+    for (int64_t k = 0; k < 12 * (int64_t)n_src; k++)
+        if (!std::isfinite(transforms[k])) { c->err = std::string(who) + ": non-finite transform entry"; return LMONO_EINVAL; }
+    if (total > kVmMaxCall) { c->err = std::string(who) + ": more than 2^30 source voxels in one call"; return LMONO_EINVAL; }
+    if (dst->full) { c->err = std::string(who) + ": the map is full (an insert needed more than max_voxels voxels; clear it or create it larger)"; return LMONO_ECAPACITY; }
+    if (stats) { for (int k = 0; k < 5; k++) stats[k] = 0; stats[5] = dst->n_vox; }
+    if (total == 0) return LMONO_OK;                            // nothing to do: no launch
+    if (hipSetDevice(c->device) != hipSuccess) { c->err = "hipSetDevice failed"; return LMONO_ENODEV; }
+    // every compose ends synchronised, so nothing in flight reads an outgrown scratch (grow_replace)
+    if ((!dst->mv_ctl && !dst->mem.alloc(dst->mv_ctl, 6)) || !dst->mem.grow_replace(dst->mv_ent, dst->mv_ent_cap, (size_t)total, /*floor=*/1024) ||
+        !dst->mem.grow_replace(dst->mv_src, dst->mv_src_cap, (size_t)n_src, /*floor=*/1)) {
+        c->err = std::string(who) + ": scratch allocation failed"; return LMONO_ENOMEM;
+    }
+    std::vector<VmMoveSrc> tab((size_t)n_src);
+    int64_t off = 0, max_n = 0;
+    for (int s = 0; s < n_src; s++) {
+        lmono_voxel_map *m = srcs[s];
+        VmMoveSrc &t = tab[(size_t)s];
+        t.rec = nullptr; t.n = (unsigned)m->n_vox; t.leaf = m->leaf; t.ent_off = off;
+        for (int k = 0; k < 12; k++) t.T[k] = transforms[12 * (size_t)s + k];
+        if (m->n_vox == 0) continue;
+        if (!m->mem.grow_replace(m->rd_rec, m->rd_rec_cap, (size_t)m->n_vox, /*floor=*/1024)) { c->err = std::string(who) + ": read buffer allocation failed"; return LMONO_ENOMEM; }
+        HIP_TRY(c, hipMemsetAsync(m->ctl + 1, 0, sizeof(unsigned), c->stream));
+        k_vm_compact<<<(unsigned)((m->slots + kVmT - 1) / kVmT), kVmT, 0, c->stream>>>(m->rec, m->slots, m->rd_rec, (unsigned)m->n_vox, m->ctl + 1);
+        if (int rc = check_launch(c, "k_vm_compact")) return rc;
+        t.rec = m->rd_rec;
+        off += m->n_vox; max_n = std::max(max_n, m->n_vox);
+    }
+    VmJob j{};
+    j.rec = dst->rec; j.occ = dst->ctl; j.mask = (unsigned)(dst->slots - 1); j.max_voxels = (unsigned)dst->max_voxels; j.inv = dst->inv;
+    j.res = (int *)(dst->mv_ctl + 4);
+    HIP_TRY(c, hipMemcpyAsync(dst->mv_src, tab.data(), sizeof(VmMoveSrc) * tab.size(), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemsetAsync(dst->mv_ctl, 0, 6 * sizeof(unsigned long long), c->stream));
+    const dim3 grid((unsigned)((max_n + kVmTile - 1) / kVmTile), (unsigned)n_src);
+    k_vm_move_find<<<grid, kVmT, 0, c->stream>>>(j, dst->mv_src, dst->mv_ent, dst->mv_ctl);
+    if (int rc = check_launch(c, "k_vm_move_find")) return rc;
+    k_vm_move_accum<<<grid, kVmT, 0, c->stream>>>(j, dst->mv_src, dst->mv_ent);
+    if (int rc = check_launch(c, "k_vm_move_accum")) return rc;
+    unsigned long long ctl[6];
+    HIP_TRY(c, hipMemcpyAsync(ctl, dst->mv_ctl, sizeof ctl, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    int res[4];
+    std::memcpy(res, ctl + 4, sizeof res);
+    if (res[0]) {                                               // nothing of this call is in the map; keys it claimed stay with count 0, unseen
+        dst->full = true;
+        c->err = std::string(who) + ": the sources need more than max_voxels voxels; nothing was composed and the map is full until cleared";
+        return LMONO_ECAPACITY;
+    }
+    if (stats) { for (int k = 0; k < 4; k++) stats[k] = (int64_t)ctl[k]; stats[4] = (int64_t)(unsigned)res[3] - dst->n_vox; stats[5] = (int64_t)(unsigned)res[3]; }
+    dst->n_vox = (int64_t)(unsigned)res[3];
+    return LMONO_OK;
 }
 
 /* tile size of k_vm_find, for tests that place point counts around it */

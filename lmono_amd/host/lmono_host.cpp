@@ -1437,6 +1437,8 @@ int MapBuilder::associateToMap(const double Q[4], const double T[3], const float
     int n = 0;
     hip_.check(lmono_associate_to_map(hip_.get(), mb_, xyzi, n_points, M, frame, Q, T, &n), "lmono_associate_to_map");
     pending_ = true;
+    for (int k = 0; k < 3; k++) last_tq_[k] = T[k];                      // the pose the queued world cloud stands in (setSubmaps anchors)
+    for (int k = 0; k < 4; k++) last_tq_[3 + k] = Q[k];
     return n;
 }
 std::string MapBuilder::processMapping()

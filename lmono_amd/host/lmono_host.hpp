@@ -420,7 +420,15 @@ public:
     // The pcl::StatisticalOutlierRemoval the reference carries commented out in front of that grid (Map_Builder.cc:24-29), as this project
     // defines it: once set, the queued frame goes through the filter on the device and the voxel map takes the kept points.
     void setOutlierFilter(int mean_k, double stddev_mul, float cell = 0.1f, int max_rings = 8);
-    std::vector<uint8_t> depthMap();                         // filled depth map of the last frame (topic depth_map before COLORMAP_JET)
+    // Submaps, so that the map can follow a corrected trajectory (the reference's own map-to-map attempt is commented out,
+    // Map_Builder.cc:110-210).  After setVoxelMap: processMapping() folds the queued frame (through the outlier filter when one is set) into
+    // the current submap too -- a voxel map of leaf_sub that takes frames_per_submap frames and is anchored at the pose of its first one.
+    void setSubmaps(int frames_per_submap, float leaf_sub = 0.05f, int64_t max_voxels_sub = (int64_t)1 << 20);
+    // corrected poses, one per frame folded so far (x y z, qx qy qz qw; e.g. PoseGraph::optimize4DoF's output): every submap moved rigidly by
+    // T_corrected * T_inserted^-1 of its anchor frame and composed into a fresh map at the setVoxelMap leaf.  One point per voxel, ascending key order.
+    std::vector<lmono_point_rgb> composeMap(const std::vector<std::array<double, 7>> &corrected_tq);
+    static void poseDelta(const double inserted_tq[7], const double corrected_tq[7], double D[12]);   // that transform, row-major 3 x 4
+    std::vector<uint8_t> depthMap();                       // filled depth map of the last frame (topic depth_map before COLORMAP_JET)
     int map_index = 0;
 private:
     HipContext &hip_;
@@ -431,6 +439,18 @@ private:
     std::shared_ptr<lmono_voxel_map> vm_;
     std::shared_ptr<lmono_sor> sor_;
     std::function<void()> fold_;
+    struct Submaps {
+        int per = 0, frames = 0;                                  // frames per submap (0: not set), frames folded
+        float leaf = 0.0f;
+        int64_t max_voxels = 0;
+        std::vector<std::shared_ptr<lmono_voxel_map>> maps;
+        std::vector<int> anchor_frame;
+        std::vector<std::array<double, 7>> anchor_tq;
+    } sub_;
+    lmono_voxel_map *submapForFrame();                           // the submap the queued frame belongs to (opened when it is the first); null when not set
+    float vm_leaf_ = 0.0f;
+    int64_t vm_max_ = 0;
+    double last_tq_[7] = { 0, 0, 0, 0, 0, 0, 1 };
     lmono_camera cam_;
     bool save_map_, pending_ = false;
     std::string map_dir_;

@@ -4,10 +4,12 @@
 // -> MapBuilder::associateToMap -> processMapping; writes <out>/rgb_map<index>.ply every 10 frames and the timing log
 // <out>/mapping_recorder.txt, and dumps the products of the last frame (<out>/depth_last.u8, <out>/cloud_cam_last.bin,
 // <out>/cloud_world_last.bin) for inspection.
-//   map_build <sequence_dir> <trajectory.txt> <out_dir> [n_frames] [width height fx fy cx cy] [sor=K:MULT[:CELL:RINGS]] [voxel=LEAF[:MAX_VOXELS]]
+//   map_build <sequence_dir> <trajectory.txt> <out_dir> [n_frames] [width height fx fy cx cy] [submap=N:CORRECTED_TRAJECTORY[:LEAF_SUB]] [sor=K:MULT[:CELL:RINGS]] [voxel=LEAF[:MAX_VOXELS]]
 // With the trailing voxel= argument every frame is also folded into a voxel-grid map, written at the end as
 // <out>/rgb_map_voxel.ply; without it nothing changes.  With sor= in front of it every frame passes the statistical outlier removal
-// (CELL 0.1 and RINGS 8 unless given) on its way into that map.
+// (CELL 0.1 and RINGS 8 unless given) on its way into that map.  With submap= in front of those every N frames also go into a
+// submap of their own (LEAF_SUB 0.05 unless given), and at the end the submaps are composed under the poses of CORRECTED_TRAJECTORY (same format,
+// one line per frame: a loop-closed trajectory) into <out>/rgb_map_global.ply at the voxel= leaf.
 #include "kitti_io.hpp"
 #include "lmono_host.hpp"
 
@@ -55,7 +57,26 @@ int main(int argc, char **argv)
         if ((got != 2 && got != 4) || sor_k < 1 || !(voxel_leaf > 0.0f)) { std::fprintf(stderr, "map_build: sor=K:MULT[:CELL:RINGS] needs K >= 1 and a voxel= argument behind it\n"); return 2; }
         argc--;
     }
-    if (argc < 4) { std::fprintf(stderr, "usage: map_build <sequence_dir> <trajectory.txt> <out_dir> [n_frames] [width height fx fy cx cy] [sor=K:MULT[:CELL:RINGS]] [voxel=LEAF[:MAX_VOXELS]]\n"); return 2; }
+    int sub_n = 0;
+    float sub_leaf = 0.05f;
+    std::string sub_traj;
+    if (argc > 4 && std::strncmp(argv[argc - 1], "submap=", 7) == 0) {
+        char *end = nullptr;
+        sub_n = (int)std::strtol(argv[argc - 1] + 7, &end, 10);
+        if (sub_n < 1 || !end || *end != ':' || !(voxel_leaf > 0.0f)) { std::fprintf(stderr, "map_build: submap=N:CORRECTED_TRAJECTORY[:LEAF_SUB] needs N >= 1 and a voxel= argument behind it\n"); return 2; }
+        sub_traj = end + 1;
+        const size_t colon = sub_traj.rfind(':');
+        if (colon != std::string::npos && colon + 1 < sub_traj.size()) {      // a trailing :LEAF_SUB, when what follows the last colon is a number
+            char *e2 = nullptr;
+            const float v = std::strtof(sub_traj.c_str() + colon + 1, &e2);
+            if (e2 && *e2 == 0) {
+                if (!(v > 0.0f)) { std::fprintf(stderr, "map_build: submap= needs a LEAF_SUB > 0\n"); return 2; }
+                sub_leaf = v; sub_traj.resize(colon);
+            }
+        }
+        argc--;
+    }
+    if (argc < 4) { std::fprintf(stderr, "usage: map_build <sequence_dir> <trajectory.txt> <out_dir> [n_frames] [width height fx fy cx cy] [submap=N:CORRECTED_TRAJECTORY[:LEAF_SUB]] [sor=K:MULT[:CELL:RINGS]] [voxel=LEAF[:MAX_VOXELS]]\n"); return 2; }
     const std::string seq = argv[1], traj = argv[2], out = argv[3];
     int n_frames = argc > 4 ? std::atoi(argv[4]) : -1;
     lmono_camera cam = { 1241, 376, 718.856, 718.856, 607.1928, 185.2157, 0, 0, 0, 0, 5, 0, 0 };   // kitti00_cam.yaml, kitti_map_config_00.yaml
@@ -71,11 +92,21 @@ int main(int argc, char **argv)
         std::fclose(f);
     }
     if (n_frames < 0 || n_frames > (int)poses.size()) n_frames = (int)poses.size();
+    std::vector<std::array<double, 7>> corrected;
+    if (sub_n > 0) {
+        FILE *f = std::fopen(sub_traj.c_str(), "r");
+        if (!f) { std::fprintf(stderr, "cannot read %s\n", sub_traj.c_str()); return 1; }
+        std::array<double, 8> p;
+        while (std::fscanf(f, "%lf %lf %lf %lf %lf %lf %lf %lf", &p[0], &p[1], &p[2], &p[3], &p[4], &p[5], &p[6], &p[7]) == 8) corrected.push_back({ p[1], p[2], p[3], p[4], p[5], p[6], p[7] });
+        std::fclose(f);
+        if ((int)corrected.size() < n_frames) { std::fprintf(stderr, "map_build: %s has fewer poses than frames\n", sub_traj.c_str()); return 1; }
+    }
     try {
         HipContext hip(0);
         MapBuilder map_builder(hip, cam, true, out);
         if (voxel_leaf > 0.0f) map_builder.setVoxelMap(voxel_leaf, voxel_max);
         if (sor_k > 0) map_builder.setOutlierFilter(sor_k, sor_mul, sor_cell, sor_rings);
+        if (sub_n > 0) map_builder.setSubmaps(sub_n, sub_leaf);
         MappingLog recorder(out + "/mapping_recorder.txt");
         if (!recorder.ok()) { std::fprintf(stderr, "cannot write into %s\n", out.c_str()); return 1; }
         std::vector<uint8_t> image;
@@ -99,6 +130,11 @@ int main(int argc, char **argv)
         if (voxel_leaf > 0.0f) {
             const std::vector<lmono_point_rgb> v = map_builder.voxelMap();
             const std::string path = out + "/rgb_map_voxel.ply";
+            if (!write_ply_binary(path, reinterpret_cast<const PointRgb *>(v.data()), v.size())) { std::fprintf(stderr, "cannot write %s\n", path.c_str()); return 1; }
+        }
+        if (sub_n > 0) {
+            const std::vector<lmono_point_rgb> v = map_builder.composeMap(corrected);
+            const std::string path = out + "/rgb_map_global.ply";
             if (!write_ply_binary(path, reinterpret_cast<const PointRgb *>(v.data()), v.size())) { std::fprintf(stderr, "cannot write %s\n", path.c_str()); return 1; }
         }
     } catch (const std::exception &e) {

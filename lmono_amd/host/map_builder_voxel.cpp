@@ -2,6 +2,7 @@
 // pcl::VoxelGrid block the reference carries commented out, Map_Builder.cc:82-98) behind lmono_voxel_map_*.
 #include "lmono_host.hpp"
 
+#include <cmath>
 #include <stdexcept>
 
 namespace lmono_host {
@@ -11,15 +12,88 @@ void MapBuilder::setVoxelMap(float leaf, int64_t max_voxels)
     lmono_voxel_map *vm = lmono_voxel_map_create(hip_.get(), leaf, max_voxels);
     if (!vm) throw std::runtime_error(std::string("lmono_voxel_map_create: ") + lmono_last_error(hip_.get()));
     vm_ = std::shared_ptr<lmono_voxel_map>(vm, lmono_voxel_map_destroy);
+    vm_leaf_ = leaf; vm_max_ = max_voxels;
     fold_ = [this] {
         lmono_voxel_map *m = vm_.get();
+        lmono_voxel_map *sub = submapForFrame();                           // the same frame into its submap
         if (lmono_sor *f = sor_.get()) {                                   // :24-29 in front of :82-98
             hip_.check(lmono_sor_filter_frames(hip_.get(), 1, &f, &mb_, nullptr), "lmono_sor_filter_frames");
             hip_.check(lmono_voxel_map_insert_filtered(hip_.get(), 1, &m, &f, nullptr), "lmono_voxel_map_insert_filtered");
+            if (sub) hip_.check(lmono_voxel_map_insert_filtered(hip_.get(), 1, &sub, &f, nullptr), "lmono_voxel_map_insert_filtered");
             return;
         }
         hip_.check(lmono_voxel_map_insert_frames(hip_.get(), 1, &m, &mb_, nullptr), "lmono_voxel_map_insert_frames");
+        if (sub) hip_.check(lmono_voxel_map_insert_frames(hip_.get(), 1, &sub, &mb_, nullptr), "lmono_voxel_map_insert_frames");
     };
+}
+
+void MapBuilder::setSubmaps(int frames_per_submap, float leaf_sub, int64_t max_voxels_sub)
+{
+    if (!vm_) throw std::runtime_error("MapBuilder::setSubmaps: setVoxelMap first (composeMap writes at its leaf)");
+    if (frames_per_submap < 1 || !(leaf_sub > 0.0f) || max_voxels_sub < 1) throw std::runtime_error("MapBuilder::setSubmaps: frames_per_submap >= 1, leaf_sub > 0, max_voxels_sub >= 1");
+    sub_ = Submaps();
+    sub_.per = frames_per_submap; sub_.leaf = leaf_sub; sub_.max_voxels = max_voxels_sub;
+}
+
+lmono_voxel_map *MapBuilder::submapForFrame()
+{
+    if (sub_.per == 0) return nullptr;
+    if (sub_.frames % sub_.per == 0) {
+        lmono_voxel_map *m = lmono_voxel_map_create(hip_.get(), sub_.leaf, sub_.max_voxels);
+        if (!m) throw std::runtime_error(std::string("lmono_voxel_map_create: ") + lmono_last_error(hip_.get()));
+        sub_.maps.push_back(std::shared_ptr<lmono_voxel_map>(m, lmono_voxel_map_destroy));
+        sub_.anchor_frame.push_back(sub_.frames);
+        std::array<double, 7> a;
+        for (int k = 0; k < 7; k++) a[(size_t)k] = last_tq_[k];
+        sub_.anchor_tq.push_back(a);
+    }
+    sub_.frames++;
+    return sub_.maps.back().get();
+}
+
+// T_corrected * T_inserted^-1 (the formula of lmono_amd.pose_delta, operation for operation): with q / |q| = (x, y, z, w) and R(q) the usual
+// rotation matrix, D_R = R_c R_i^T and D_t = t_c - D_R t_i, every sum left to right
+static void pose_matrix(const double tq[7], double R[9])
+{
+    const double n = std::sqrt(((tq[3] * tq[3] + tq[4] * tq[4]) + tq[5] * tq[5]) + tq[6] * tq[6]);
+    const double x = tq[3] / n, y = tq[4] / n, z = tq[5] / n, w = tq[6] / n;
+    R[0] = 1.0 - 2.0 * (y * y + z * z); R[1] = 2.0 * (x * y - z * w); R[2] = 2.0 * (x * z + y * w);
+    R[3] = 2.0 * (x * y + z * w); R[4] = 1.0 - 2.0 * (x * x + z * z); R[5] = 2.0 * (y * z - x * w);
+    R[6] = 2.0 * (x * z - y * w); R[7] = 2.0 * (y * z + x * w); R[8] = 1.0 - 2.0 * (x * x + y * y);
+}
+
+void MapBuilder::poseDelta(const double inserted_tq[7], const double corrected_tq[7], double D[12])
+{
+    double Ri[9], Rc[9];
+    pose_matrix(inserted_tq, Ri);
+    pose_matrix(corrected_tq, Rc);
+    for (int a = 0; a < 3; a++) {
+        for (int b = 0; b < 3; b++) D[4 * a + b] = (Rc[3 * a] * Ri[3 * b] + Rc[3 * a + 1] * Ri[3 * b + 1]) + Rc[3 * a + 2] * Ri[3 * b + 2];
+        D[4 * a + 3] = corrected_tq[a] - ((D[4 * a] * inserted_tq[0] + D[4 * a + 1] * inserted_tq[1]) + D[4 * a + 2] * inserted_tq[2]);
+    }
+}
+
+std::vector<lmono_point_rgb> MapBuilder::composeMap(const std::vector<std::array<double, 7>> &corrected_tq)
+{
+    std::vector<lmono_point_rgb> out;
+    if (sub_.per == 0) throw std::runtime_error("MapBuilder::composeMap: setSubmaps first");
+    if ((int)corrected_tq.size() < sub_.frames) throw std::runtime_error("MapBuilder::composeMap: one corrected pose per frame folded");
+    const size_t n = sub_.maps.size();
+    std::vector<lmono_voxel_map *> srcs(n);
+    std::vector<double> T(12 * n);
+    for (size_t s = 0; s < n; s++) {
+        srcs[s] = sub_.maps[s].get();
+        poseDelta(sub_.anchor_tq[s].data(), corrected_tq[(size_t)sub_.anchor_frame[s]].data(), &T[12 * s]);
+    }
+    lmono_voxel_map *g = lmono_voxel_map_create(hip_.get(), vm_leaf_, vm_max_);
+    if (!g) throw std::runtime_error(std::string("lmono_voxel_map_create: ") + lmono_last_error(hip_.get()));
+    const std::shared_ptr<lmono_voxel_map> global(g, lmono_voxel_map_destroy);
+    hip_.check(lmono_voxel_map_compose(hip_.get(), g, (int)n, srcs.data(), T.data(), nullptr), "lmono_voxel_map_compose");
+    const int64_t m = lmono_voxel_map_read(hip_.get(), g, nullptr, 0);
+    hip_.check(m < 0 ? (int)m : 0, "lmono_voxel_map_read");
+    out.resize((size_t)m);
+    if (m > 0) hip_.check(lmono_voxel_map_read(hip_.get(), g, out.data(), m) < 0 ? -1 : 0, "lmono_voxel_map_read");
+    return out;
 }
 
 void MapBuilder::setOutlierFilter(int mean_k, double stddev_mul, float cell, int max_rings)

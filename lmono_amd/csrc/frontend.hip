@@ -16,6 +16,7 @@
 // Arithmetic is float/double exactly as the CPU restatement evaluates it (compiled with -ffp-contract=off).
 #include "batch.hpp"
 #include "ring_decide.hpp"
+#include "vox_runs.hpp"
 
 namespace lmono {
 
@@ -579,18 +580,24 @@ __global__ __launch_bounds__(256, 8) void k_select(BatchView b, int cap, int fro
 //
 // Layout: point i = tid + 256 m of the ring sits in register slot m of thread tid, so wave w of slot m holds 64
 // consecutive points and a ballot over the wave is a 64-bit piece of a per-ring bitmap (word i >> 6).  Segment heads,
-// their count and their positions come from ballots and a 32-entry prefix over (slot, wave); "point i continues the run
-// of point i - 1" is kept as a bitmap, which is all the accumulation needs to know about run lengths.
-// Sort: rings of <= 1024 segments (the usual case) use a bucket sort -- bucket = cell index shifted down to <= 4096 values,
-// histogram -> exclusive prefix -> cursors, keys scattered bucket by bucket in arrival order, then every key counts the
-// smaller keys of its bucket (typically 1-3 members) and takes that place: the exact (cell, first index) order whatever the
-// arrival order was.  Longer rings fall back to the register bitonic network.
+// their count and their positions come from ballots and a prefix over (slot, wave); "point i continues the run
+// of point i - 1" is kept as a bitmap, which is all the accumulation needs to know about run lengths: a run's length is a count
+// of trailing ones in a window of two of its words (vox_runs.hpp).
+// Sort: a bucket sort -- bucket = cell index shifted down to <= 2048 / 4096 values (monotone in the cell), histogram ->
+// exclusive prefix -> cursors, keys scattered bucket by bucket in arrival order, then every key counts the smaller keys of its
+// bucket and takes that place: the exact (cell, first index) order whatever the arrival order was.  A key mostly has 1-3
+// companions in its bucket, but a wave of 64 keys runs as long as its largest bucket, ~18 keys on an HDL-64 ring (a bucket spans
+// a few rows of x, and where the ring runs along x dozens of segments share one), so the small instantiation makes a trip one
+// LDS read of a one-word key and two compares, and finds the voxel starts in the same loop.  Rings the bucket sort does not
+// take fall back to the register bitonic network.
+// Accumulation: one voxel per thread and round; its segments are [vstart[v], vstart[v + 1]) of the sorted array, which holds
+// the first indices, so a segment costs one LDS read, the window and the loads of its points.
 //
-// Two instantiations run back to back: <9 slots, 2048 buckets> takes the rings of <= 2304 points (every HDL-64 ring: ~80 VGPRs,
-// 27 KB of LDS, 6 workgroups per CU) and appends a ring it cannot take (more points, or > 1024 segments: bitonic network) to a
-// work list; <16 slots, 4096 buckets> runs as a small fixed grid over that list (normally empty).
+// Two instantiations run back to back: <9 slots, 2048 buckets> takes the rings of <= 2304 points and <= 2^31 cells (every HDL-64
+// ring: 68 VGPRs, 24.5 KB of LDS, 6 workgroups per CU) and appends a ring it cannot take to a work list; <16 slots, 4096 buckets>
+// runs as a small fixed grid over that list (normally empty): bucket sort up to 1024 segments and 2^32 cells, bitonic network beyond.
 constexpr int kVoxBucketSegsBig = 1024;   // bucket-sort capacity (segments) of the big instantiation; the small one takes its whole ring
-constexpr int kVoxSmallSlots = 9, kVoxSmallBits = 10;
+constexpr int kVoxSmallSlots = 9, kVoxSmallBits = 11;
 constexpr int kVoxBigSlots = kRingCap / 256, kVoxBigBits = 12;
 constexpr int kVoxBigGrid = 512;    // workgroups of the second instantiation; each walks the work list with this stride
 // LDS: key region (sorted keys | scattered copy | bucket counters; the big variant: kRingCap keys for the bitonic fallback),
@@ -598,12 +605,15 @@ constexpr int kVoxBigGrid = 512;    // workgroups of the second instantiation; e
 template <int kSlots, int kBits, bool kSmall>
 struct VoxCfg {
     static constexpr int kSegCap = kSmall ? 256 * kSlots : kVoxBucketSegsBig;
-    // small: scattered keys as (cell u32 | first index u16) | sorted order as u16 positions into them | bucket counters, later
-    // the voxel starts (u16)
-    static constexpr int kHistBytes = (1 << kBits) * 4 > kSegCap * 2 ? (1 << kBits) * 4 : kSegCap * 2;
+    // small: scattered keys as (cell bits below the bucket << 12 | first index, u32) and their buckets (u16) | sorted segments as
+    // (voxel start << 15 | first index, u16) | bucket counters (u16, two per word), later the voxel starts (u16)
+    static constexpr int kHistBytes = (1 << kBits) * 2 > kSegCap * 2 ? (1 << kBits) * 2 : kSegCap * 2;
     static constexpr int kKeyBytes = kSmall ? kSegCap * 4 + kSegCap * 2 + kSegCap * 2 + kHistBytes : kRingCap * 8;
-    static constexpr int kLds = kKeyBytes + 1024 + kSlots * 4 * 8 + kSlots * 4 * 4;
+    // the continuation bitmap ends in two zero words (vox_runs.hpp)
+    static constexpr int kLds = kKeyBytes + 1024 + (kSlots * 4 + 2) * 8 + kSlots * 4 * 4;
 };
+static_assert(256 * kVoxSmallSlots <= 4096, "a first index of the small instantiation has 12 bits");
+static_assert((1 << kVoxSmallBits) == 2048, "the small instantiation's counters are one uint4 per thread");
 constexpr int kVoxLdsSmall = VoxCfg<kVoxSmallSlots, kVoxSmallBits, true>::kLds;
 constexpr int kVoxLdsBig = VoxCfg<kVoxBigSlots, kVoxBigBits, false>::kLds;
 static_assert(2 * kVoxBucketSegsBig * 8 + (1 << kVoxBigBits) * 4 <= kRingCap * 8, "bucket sort scratch must fit the key region");
@@ -613,16 +623,43 @@ static_assert(2 * kVoxBucketSegsBig * 8 + (1 << kVoxBigBits) * 4 <= kRingCap * 8
 #define VT(i)
 #endif
 
+// min / max over the wave with a wave-uniform result: the DPP stages of common.hpp's wave_min_u32_uniform (one VALU instruction each,
+// no LDS crossbar); a lane without a source takes the identity.  No input is a NaN here, so the order of the stages does not matter.
+template <int kCtrl, int kRowMask>
+__device__ __forceinline__ float dpp_mov_f32(float v, float ident)
+{
+    return __uint_as_float(dpp_mov_u32<kCtrl, kRowMask>(__float_as_uint(v), __float_as_uint(ident)));
+}
 __device__ __forceinline__ float wave_min_f(float v)
 {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o));
-    return v;
+    v = fminf(v, dpp_mov_f32<0x111, 0xf>(v, FLT_MAX));
+    v = fminf(v, dpp_mov_f32<0x112, 0xf>(v, FLT_MAX));
+    v = fminf(v, dpp_mov_f32<0x114, 0xf>(v, FLT_MAX));
+    v = fminf(v, dpp_mov_f32<0x118, 0xf>(v, FLT_MAX));
+    v = fminf(v, dpp_mov_f32<0x142, 0xa>(v, FLT_MAX));
+    v = fminf(v, dpp_mov_f32<0x143, 0xc>(v, FLT_MAX));
+    return __uint_as_float((unsigned int)__builtin_amdgcn_readlane((int)__float_as_uint(v), 63));
 }
 __device__ __forceinline__ float wave_max_f(float v)
 {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
+    v = fmaxf(v, dpp_mov_f32<0x111, 0xf>(v, -FLT_MAX));
+    v = fmaxf(v, dpp_mov_f32<0x112, 0xf>(v, -FLT_MAX));
+    v = fmaxf(v, dpp_mov_f32<0x114, 0xf>(v, -FLT_MAX));
+    v = fmaxf(v, dpp_mov_f32<0x118, 0xf>(v, -FLT_MAX));
+    v = fmaxf(v, dpp_mov_f32<0x142, 0xa>(v, -FLT_MAX));
+    v = fmaxf(v, dpp_mov_f32<0x143, 0xc>(v, -FLT_MAX));
+    return __uint_as_float((unsigned int)__builtin_amdgcn_readlane((int)__float_as_uint(v), 63));
+}
+// inclusive prefix sum across the wave in six DPP stages (the row_shr / row_bcast ladder of the reductions above, which leaves every
+// lane with the sum of the lanes up to it); a lane without a source adds 0
+__device__ __forceinline__ int wave_scan_incl_dpp(int v)
+{
+    v += (int)dpp_mov_u32<0x111, 0xf>((unsigned int)v, 0u);
+    v += (int)dpp_mov_u32<0x112, 0xf>((unsigned int)v, 0u);
+    v += (int)dpp_mov_u32<0x114, 0xf>((unsigned int)v, 0u);
+    v += (int)dpp_mov_u32<0x118, 0xf>((unsigned int)v, 0u);
+    v += (int)dpp_mov_u32<0x142, 0xa>((unsigned int)v, 0u);
+    v += (int)dpp_mov_u32<0x143, 0xc>((unsigned int)v, 0u);
     return v;
 }
 
@@ -670,8 +707,8 @@ __device__ __forceinline__ void voxel_ring(BatchView &b, int r, int s)
     extern __shared__ __align__(16) unsigned char smem[];
     unsigned long long *keys = (unsigned long long *)smem;                  // sorted segment keys (cell << 32 | first index)
     int *scr = (int *)(smem + kKeyBytes);                                   // 256 ints
-    unsigned long long *contw = (unsigned long long *)(smem + kKeyBytes + 1024);   // [kVoxSlots * 4] run-continuation bitmap
-    unsigned int *lastc = (unsigned int *)(contw + kVoxSlots * 4);          // [kVoxSlots * 4] cell of lane 63 of every (slot, wave)
+    unsigned long long *contw = (unsigned long long *)(smem + kKeyBytes + 1024);   // [kVoxSlots * 4 + 2] run-continuation bitmap, two zero words behind it
+    unsigned int *lastc = (unsigned int *)(contw + kVoxSlots * 4 + 2);      // [kVoxSlots * 4] cell of lane 63 of every (slot, wave)
     const signed char *label = (const signed char *)(b.label + off + rbeg);
     const float4 *cl = b.cloud + off + rbeg;
     const int c_lo = 5, c_hi = len - 7;   // sectors cover local [5, len-7]
@@ -750,17 +787,15 @@ __device__ __forceinline__ void voxel_ring(BatchView &b, int r, int s)
         cellr[m] = cell;
         if (lane == 63) lastc[m * 4 + wave] = cell;
     }
-    // small instantiation: the sorted order is a u16 index into the scattered keys (28 KB of LDS in all: 5 workgroups per CU;
-    // the kernel is bound by resident workgroups -- 3 per CU at 46 KB measured 6.2 ms, 2 per CU 8.8 ms)
+    // small instantiation: 8 bytes of LDS per segment (the kernel is bound by resident workgroups -- 3 per CU at 46 KB measured 6.2 ms,
+    // 2 per CU 8.8 ms).  A scattered key is one word, (cell & (2^bshift - 1)) << 12 | first index: inside a bucket the cell bits above
+    // bshift are equal, so this word orders a bucket's keys as (cell, first index) does, and the ranking compares words.  The sorted
+    // array holds what the accumulation reads, the first index, and bit 15 = "first segment of its voxel" (found while ranking).
     unsigned long long *tmp = keys + kVoxBucketSegs;                                        // big only: scattered keys
-    unsigned int *cellt = (unsigned int *)keys;                                             // small only: scattered (cell,
-    unsigned short *idxt = (unsigned short *)((unsigned char *)keys + kVoxBucketSegs * 4);  //             first index)
-    unsigned short *pos = (unsigned short *)((unsigned char *)keys + kVoxBucketSegs * 6);   // small only: sorted order
+    unsigned int *wsc = (unsigned int *)keys;                                               // small only: scattered key words
+    unsigned short *bkt = (unsigned short *)((unsigned char *)keys + kVoxBucketSegs * 4);   //             and their buckets
+    unsigned short *srt = (unsigned short *)((unsigned char *)keys + kVoxBucketSegs * 6);   // small only: sorted segments
     int *hist = kSmall ? (int *)((unsigned char *)keys + kVoxBucketSegs * 8) : (int *)(keys + 2 * kVoxBucketSegs);
-    auto skey = [&](int t) -> unsigned long long {
-        if (kSmall) { const int q = pos[t]; return ((unsigned long long)cellt[q] << 32) | idxt[q]; }
-        return keys[t];
-    };
     __syncthreads();            // fs / scr[32..35] are read, lastc is written
     VT(2)
     // ---- segment heads: a candidate whose predecessor in the ring is not a candidate of the same cell
@@ -777,27 +812,79 @@ __device__ __forceinline__ void voxel_ring(BatchView &b, int r, int s)
         if (lane == 0) { contw[m * 4 + wave] = cm; scr[64 + m * 4 + wave] = __popcll(hm); }
         if (head) head_mask |= 1u << m;
     }
+    if (tid < 2) contw[kVoxSlots * 4 + tid] = 0ull;
     __syncthreads();
     // position of a head in ring order = heads of the earlier (slot, wave) pairs + heads below it in its own ballot
-    int nseg = 0;
+    // (lane l of every wave scans the count of pair l; the big instantiation alone needs the bases, for its bitonic network)
+    const int wave_u = __builtin_amdgcn_readfirstlane(wave);
+    const int hc = lane < kVoxSlots * 4 ? scr[64 + lane] : 0;
+    const int hincl = wave_scan_incl_dpp(hc);
+    const int nseg = __builtin_amdgcn_readlane(hincl, 63);
     int hbase[kVoxSlots];
+    if (!kSmall) {
 #pragma unroll
-    for (int m = 0; m < kVoxSlots; m++) {
-#pragma unroll
-        for (int w = 0; w < 4; w++) {
-            const int c = scr[64 + m * 4 + w];
-            if (w == wave) hbase[m] = nseg;
-            nseg += c;
-        }
+        for (int m = 0; m < kVoxSlots; m++) hbase[m] = __builtin_amdgcn_readlane(hincl - hc, m * 4 + wave_u);
     }
     int np2 = next_pow2(nseg);
     if (np2 < 2) np2 = 2;
-    const bool bucket_path = nseg <= kVoxBucketSegs && ncell <= 0xffffffffull;
+    // the small instantiation's key word holds bshift + 12 <= 32 bits: up to 2^31 cells
+    const bool bucket_path = nseg <= kVoxBucketSegs && ncell <= (kSmall ? 0x80000000ull : 0xffffffffull);
     if (kSmall && !bucket_path) {
         if (tid == 0) b.vox_todo[1 + atomicAdd(&b.vox_todo[0], 1)] = (s << 6) | r;    // needs the bitonic network: big instantiation
         return;
     }
-    if (bucket_path) {
+    if (bucket_path && kSmall) {
+        // 2048 counters of 16 bits, two per word (a ring has at most 2304 segments, so neither a count nor a cursor carries into its
+        // neighbour): thread tid owns the 8 counters of words 4 tid .. 4 tid + 3
+        uint4 *hw4 = (uint4 *)hist;
+        unsigned int *hw = (unsigned int *)hist;
+        const unsigned short *h16 = (const unsigned short *)hist;
+        hw4[tid] = make_uint4(0u, 0u, 0u, 0u);
+        __syncthreads();
+#pragma unroll
+        for (int m = 0; m < kVoxSlots; m++)
+            if ((head_mask >> m) & 1u) { const unsigned int bk = cellr[m] >> bshift; atomicAdd(&hw[bk >> 1], 1u << ((bk & 1u) * 16u)); }
+        __syncthreads();
+        VT(3)
+        const uint4 cw = hw4[tid];
+        const unsigned int c0 = cw.x & 0xffffu, c1 = cw.x >> 16, c2 = cw.y & 0xffffu, c3 = cw.y >> 16;
+        const unsigned int c4 = cw.z & 0xffffu, c5 = cw.z >> 16, c6 = cw.w & 0xffffu, c7 = cw.w >> 16;
+        const int sum = (int)(c0 + c1 + c2 + c3 + c4 + c5 + c6 + c7);
+        const int incl_b = wave_scan_incl_dpp(sum);
+        if (lane == 63) scr[44 + wave] = incl_b;
+        __syncthreads();
+        unsigned int run = (unsigned int)(incl_b - sum);
+        for (int w = 0; w < wave; w++) run += (unsigned int)scr[44 + w];
+        uint4 ew;
+        { const unsigned int e0 = run, e1 = e0 + c0, e2 = e1 + c1, e3 = e2 + c2, e4 = e3 + c3, e5 = e4 + c4, e6 = e5 + c5, e7 = e6 + c6;
+          ew = make_uint4(e0 | (e1 << 16), e2 | (e3 << 16), e4 | (e5 << 16), e6 | (e7 << 16)); }
+        hw4[tid] = ew;
+        __syncthreads();
+        const unsigned int cmask = (1u << bshift) - 1u;
+#pragma unroll
+        for (int m = 0; m < kVoxSlots; m++)
+            if ((head_mask >> m) & 1u) {
+                const unsigned int bk = cellr[m] >> bshift, sh = (bk & 1u) * 16u;
+                const unsigned int q = (atomicAdd(&hw[bk >> 1], 1u << sh) >> sh) & 0xffffu;
+                wsc[q] = ((cellr[m] & cmask) << 12) | (unsigned int)(tid + 256 * m);
+                bkt[q] = (unsigned short)bk;
+            }
+        __syncthreads();
+        // a cursor is now the end of its bucket = the start of the next one.  Every key counts the smaller keys of its bucket and takes that
+        // place: the exact (cell, first index) order whatever the arrival order was.  A wave runs as long as its largest bucket (a bucket
+        // spans a few rows of x, so a ring that runs along x puts dozens of segments into one); a trip is one LDS read and two compares,
+        // the second of which counts the keys of smaller cells: a key that has only those below it starts a voxel.
+        for (int t = tid; t < nseg; t += 256) {
+            const unsigned int k = wsc[t], kc = k & ~0xfffu;
+            const int bk = bkt[t];
+            const int lo = bk > 0 ? h16[bk - 1] : 0, hi = h16[bk];
+            int less = 0, lessc = 0;
+            // (four keys a trip, read together and masked behind the bucket's end, measured slower: 3.05 against 2.99 ms)
+            for (int u = lo; u < hi; u++) { const unsigned int ku = wsc[u]; less += ku < k ? 1 : 0; lessc += ku < kc ? 1 : 0; }
+            srt[lo + less] = (unsigned short)((k & 0xfffu) | (less == lessc ? 0x8000u : 0u));
+        }
+        __syncthreads();
+    } else if (!kSmall && bucket_path) {
         for (int i = tid; i < kVoxBuckets; i += 256) hist[i] = 0;
         __syncthreads();
 #pragma unroll
@@ -809,7 +896,7 @@ __device__ __forceinline__ void voxel_ring(BatchView &b, int r, int s)
         int c[kPer], sum = 0;
 #pragma unroll
         for (int q = 0; q < kPer; q++) { c[q] = hist[tid * kPer + q]; sum += c[q]; }
-        const int incl_b = wave_scan_incl(sum);
+        const int incl_b = wave_scan_incl_dpp(sum);
         if (lane == 63) scr[44 + wave] = incl_b;
         __syncthreads();
         int run = incl_b - sum;
@@ -819,21 +906,19 @@ __device__ __forceinline__ void voxel_ring(BatchView &b, int r, int s)
         __syncthreads();
 #pragma unroll
         for (int m = 0; m < kVoxSlots; m++)
-            if ((head_mask >> m) & 1u)
-            {
+            if ((head_mask >> m) & 1u) {
                 const int q = atomicAdd(&hist[cellr[m] >> bshift], 1);
-                if (kSmall) { cellt[q] = cellr[m]; idxt[q] = (unsigned short)(tid + 256 * m); }
-                else tmp[q] = ((unsigned long long)cellr[m] << 32) | (unsigned int)(tid + 256 * m);
+                tmp[q] = ((unsigned long long)cellr[m] << 32) | (unsigned int)(tid + 256 * m);
             }
         __syncthreads();
-        // a cursor is now the end of its bucket = the start of the next one
+        // a cursor is now the end of its bucket = the start of the next one; ranking as above, on the whole 64-bit keys
         for (int t = tid; t < nseg; t += 256) {
-            const unsigned long long k = kSmall ? (((unsigned long long)cellt[t] << 32) | idxt[t]) : tmp[t];
+            const unsigned long long k = tmp[t];
             const int bk = (int)((unsigned int)(k >> 32) >> bshift);
             const int lo = bk > 0 ? hist[bk - 1] : 0, hi = hist[bk];
             int less = 0;
-            for (int u = lo; u < hi; u++) less += (kSmall ? (((unsigned long long)cellt[u] << 32) | idxt[u]) : tmp[u]) < k ? 1 : 0;
-            if (kSmall) pos[lo + less] = (unsigned short)t; else keys[lo + less] = k;
+            for (int u = lo; u < hi; u++) less += tmp[u] < k ? 1 : 0;
+            keys[lo + less] = k;
         }
         __syncthreads();
     } else if (!kSmall) {
@@ -853,57 +938,61 @@ __device__ __forceinline__ void voxel_ring(BatchView &b, int r, int s)
     int *vstart = bucket_path && !kSmall ? (int *)(keys + kVoxBucketSegs) : nullptr;   // big: the scattered copy is dead now
     unsigned short *vstart16 = (unsigned short *)hist;                                 // small: the bucket counters are dead after the ranking
     constexpr int kRounds = (kVoxBucketSegs + 255) / 256;
-    int n_out = 0, obase[kRounds];
-    {
-        const int rounds = (nseg + 255) / 256;
+    const int rounds = (nseg + 255) / 256;
+    int n_out = 0;
+    unsigned int st_mask = 0;          // bit j: sorted segment tid + 256 j starts a voxel (computed once, used by both passes)
+    if (bucket_path) {
         // voxel starts per round and wave -> prefix in sorted order (round, wave, lane)
         for (int j = 0; j < rounds; j++) {
             const int t = tid + 256 * j;
-            const bool st = t < nseg && (t == 0 || (unsigned int)(skey(t) >> 32) != (unsigned int)(skey(t - 1) >> 32));
+            bool st;
+            if (kSmall) st = t < nseg && (srt[t] & 0x8000u) != 0u;
+            else st = t < nseg && (t == 0 || (unsigned int)(keys[t] >> 32) != (unsigned int)(keys[t - 1] >> 32));
             const unsigned long long sm = __ballot(st);
-            if (lane == 0) scr[128 + ((j * 4 + wave) & 127)] = __popcll(sm);
+            if (lane == 0) scr[128 + j * 4 + wave] = __popcll(sm);
+            if (st) st_mask |= 1u << j;
         }
     }
     __syncthreads();
     float4 *outp = b.lf_tmp + off + rbeg;
+    // one segment's points, added one after the other in index order (four requested at a time)
+    auto add_run = [&](int i0, float &sx, float &sy, float &sz, float &si, int &cnt) {
+        const int rl = vox_run_length(contw, i0);
+        for (int b4 = 0; b4 < rl; b4 += 4) {
+            float4 q4[4];
+#pragma unroll
+            for (int k = 0; k < 4; k++) q4[k] = b4 + k < rl ? cl[i0 + b4 + k] : make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+            for (int k = 0; k < 4; k++) if (b4 + k < rl) { sx += q4[k].x; sy += q4[k].y; sz += q4[k].z; si += q4[k].w; }
+        }
+        cnt += rl;
+    };
     VT(5)
     if (bucket_path) {
-        const int rounds = (nseg + 255) / 256;
-        int total = 0;
-#pragma unroll
-        for (int j = 0; j < kRounds; j++)
-            for (int w = 0; w < 4; w++) { if (j < rounds) { if (w == wave) obase[j] = total; total += scr[128 + j * 4 + w]; } }
-        n_out = total;
+        // (lane l of every wave scans the count of pair l, as for the heads)
+        const int oc = lane < rounds * 4 ? scr[128 + lane] : 0;
+        const int oincl = wave_scan_incl_dpp(oc);
+        n_out = __builtin_amdgcn_readlane(oincl, 63);
 #pragma unroll
         for (int j = 0; j < kRounds; j++) {
             if (j >= rounds) break;
             const int t = tid + 256 * j;
-            const bool st = t < nseg && (t == 0 || (unsigned int)(skey(t) >> 32) != (unsigned int)(skey(t - 1) >> 32));
+            const bool st = (st_mask >> j) & 1u;
+            const int obase = __builtin_amdgcn_readlane(oincl - oc, j * 4 + wave_u);
             const unsigned long long sm = __ballot(st);
-            if (st) { const int o = obase[j] + __popcll(sm & ((1ull << lane) - 1ull)); if (kSmall) vstart16[o] = (unsigned short)t; else vstart[o] = t; }
+            if (st) { const int o = obase + __popcll(sm & ((1ull << lane) - 1ull)); if (kSmall) vstart16[o] = (unsigned short)t; else vstart[o] = t; }
         }
         __syncthreads();
-        // one voxel per thread and round: its segments in sorted order, every segment's points in index order
+        // one voxel per thread and round: its segments [vstart[v], vstart[v + 1]) in sorted order, every segment's points in index order
         for (int v = tid; v < n_out; v += 256) {
-            const int t = kSmall ? (int)vstart16[v] : vstart[v];
-            const unsigned int c = (unsigned int)(skey(t) >> 32);
+            int t0, t1;
+            if (kSmall) { t0 = vstart16[v]; t1 = v + 1 < n_out ? (int)vstart16[v + 1] : nseg; }
+            else { t0 = vstart[v]; t1 = v + 1 < n_out ? vstart[v + 1] : nseg; }
             float sx = 0.f, sy = 0.f, sz = 0.f, si = 0.f;
             int cnt = 0;
-            for (int u = t; u < nseg; u++) {
-                const unsigned long long ku = skey(u);
-                if ((unsigned int)(ku >> 32) != c) break;
-                const int i0 = (int)(ku & 0xffffffffull);
-                // run length from the continuation bitmap: points i0+1 .. while their bit is set
-                int rl = 1;
-                while (i0 + rl < len && ((contw[(i0 + rl) >> 6] >> ((i0 + rl) & 63)) & 1ull)) rl++;
-                for (int b4 = 0; b4 < rl; b4 += 4) {
-                    float4 q4[4];
-#pragma unroll
-                    for (int k = 0; k < 4; k++) q4[k] = b4 + k < rl ? cl[i0 + b4 + k] : make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-                    for (int k = 0; k < 4; k++) if (b4 + k < rl) { sx += q4[k].x; sy += q4[k].y; sz += q4[k].z; si += q4[k].w; }
-                }
-                cnt += rl;
+            for (int u = t0; u < t1; u++) {
+                const int i0 = kSmall ? (int)(srt[u] & 0xfffu) : (int)(keys[u] & 0xffffffffull);
+                add_run(i0, sx, sy, sz, si, cnt);
             }
             const float fc = (float)cnt;
             outp[v] = make_float4(sx / fc, sy / fc, sz / fc, si / fc);
@@ -931,17 +1020,7 @@ __device__ __forceinline__ void voxel_ring(BatchView &b, int r, int s)
                 float sx = 0.f, sy = 0.f, sz = 0.f, si = 0.f;
                 int cnt = 0;
                 for (int u = t; u < nseg && (unsigned int)(keys[u] >> 32) == c; u++) {
-                    const int i0 = (int)(keys[u] & 0xffffffffull);
-                    int rl = 1;
-                    while (i0 + rl < len && ((contw[(i0 + rl) >> 6] >> ((i0 + rl) & 63)) & 1ull)) rl++;
-                    for (int b4 = 0; b4 < rl; b4 += 4) {
-                        float4 q4[4];
-#pragma unroll
-                        for (int k = 0; k < 4; k++) q4[k] = b4 + k < rl ? cl[i0 + b4 + k] : make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-                        for (int k = 0; k < 4; k++) if (b4 + k < rl) { sx += q4[k].x; sy += q4[k].y; sz += q4[k].z; si += q4[k].w; }
-                    }
-                    cnt += rl;
+                    add_run((int)(keys[u] & 0xffffffffull), sx, sy, sz, si, cnt);
                 }
                 const float fc = (float)cnt;
                 outp[o++] = make_float4(sx / fc, sy / fc, sz / fc, si / fc);

@@ -5,36 +5,16 @@ import weakref
 
 import numpy as np
 
+from ._abi import PROTOTYPES
+from .brief_tools import (_VOC_KEYS, _voc_arrays, check_brief_vocabulary, load_brief_pattern, load_brief_vocabulary,  # noqa: F401
+                          save_brief_vocabulary, train_brief_vocabulary)
+from .errors import LmonoError
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 MAX_QUERIES = 64 * 6 * 2 + 64 * 6 * 4
 
 # every symbol include/lmono_hip.h declares (checked by tests/test_abi.py)
-SYMBOLS = [
-    "lmono_create", "lmono_destroy", "lmono_last_error", "lmono_set_stream", "lmono_use_own_stream", "lmono_set_option", "lmono_get_option", "lmono_synchronize", "lmono_version",
-    "lmono_batch_create", "lmono_batch_destroy", "lmono_scanreg_batch", "lmono_scanreg_batch_h", "lmono_host_alloc", "lmono_host_free", "lmono_batch_stage_h", "lmono_scanreg_batch_staged", "lmono_batch_counts", "lmono_batch_get_cloud",
-    "lmono_batch_get_curvature", "lmono_odom_batch", "lmono_odom_batch_d", "lmono_odom_shard_d", "lmono_odom_shard_main_d", "lmono_odom_shard_validate", "lmono_odom_boundary_report", "lmono_odom_stream_create", "lmono_odom_stream_destroy", "lmono_odom_step", "lmono_odom_stream_scan", "lmono_odom_correspond", "lmono_timing_reset", "lmono_timing_read",
-    "lmono_pose_prefix_d", "lmono_pose_rebase_d", "lmono_map_refine", "lmono_voxel_filter", "lmono_mapper_create", "lmono_mapper_destroy", "lmono_mapper_reset", "lmono_mapper_process", "lmono_mapper_process_batch", "lmono_mapper_cube",
-    "lmono_map_builder_create", "lmono_map_builder_destroy", "lmono_associate_to_map", "lmono_associate_to_map_batch", "lmono_map_builder_depth",
-    "lmono_map_builder_cloud", "lmono_map_builder_map", "lmono_map_builder_clear",
-    "lmono_voxel_map_create", "lmono_voxel_map_destroy", "lmono_voxel_map_clear", "lmono_voxel_map_insert", "lmono_voxel_map_insert_d", "lmono_voxel_map_insert_frames",
-    "lmono_voxel_map_size", "lmono_voxel_map_read", "lmono_voxel_map_cells", "lmono_voxel_map_tile", "lmono_voxel_map_compose",
-    "lmono_sor_create", "lmono_sor_destroy", "lmono_sor_filter", "lmono_sor_filter_d", "lmono_sor_filter_frames", "lmono_sor_cloud", "lmono_sor_scores",
-    "lmono_sor_threshold", "lmono_sor_diag", "lmono_voxel_map_insert_filtered",
-    "lmono_tracker_create", "lmono_tracker_destroy", "lmono_tracker_reset", "lmono_tracker_track", "lmono_tracker_track_batch", "lmono_tracker_pyramid",
-    "lmono_tracker_response", "lmono_tracker_lk", "lmono_tracker_set_reject_f", "lmono_tracker_reject_stats", "lmono_tracker_reject_f",
-    "lmono_keyframes_create", "lmono_keyframes_destroy", "lmono_keyframes_clear", "lmono_keyframes_size", "lmono_keyframes_add", "lmono_keyframes_add_batch",
-    "lmono_keyframes_load", "lmono_keyframes_match", "lmono_keyframes_images", "lmono_keyframes_get", "lmono_keyframes_verify", "lmono_pnp_ransac",
-    "lmono_brief_vocabulary_create", "lmono_brief_vocabulary_destroy", "lmono_brief_vocabulary_transform", "lmono_keyframes_set_vocabulary", "lmono_keyframes_bow",
-    "lmono_keyframes_query", "lmono_keyframes_detect_loop", "lmono_keyframes_detect_loop_batch",
-    "lmono_excalib_create", "lmono_excalib_destroy", "lmono_excalib_reset", "lmono_relative_rotation", "lmono_excalib_push", "lmono_excalib_step", "lmono_excalib_state",
-    "lmono_pose_graph_create", "lmono_pose_graph_destroy", "lmono_pose_graph_reset", "lmono_pose_graph_info", "lmono_pose_graph_order", "lmono_pose_graph_reduce_buffer", "lmono_pose_graph_set_reduce_buffer", "lmono_pose_graph_linearise",
-    "lmono_pose_graph_step", "lmono_pose_graph_optimize", "lmono_pose_graph_result", "lmono_factor_eval", "lmono_factor_eval_d", "lmono_factor_eval_blocks", "lmono_factor_eval_blocks_d",
-    "lmono_triangulate", "lmono_outlier_scores", "lmono_shift_depth", "lmono_shift_depth_batch", "lmono_marginalize", "lmono_marg_evaluate", "lmono_marg_second_new", "lmono_ba_batch_create", "lmono_ba_batch_update", "lmono_ba_batch_destroy", "lmono_ba_solve", "lmono_ba_batch_reset", "lmono_ba_batch_read", "lmono_debug_bounds",
-]
-
-
-class LmonoError(RuntimeError):
-    pass
+SYMBOLS = list(PROTOTYPES)
 
 
 def lib_path():
@@ -53,66 +33,13 @@ def load_library():
     if not os.path.exists(p):
         raise LmonoError("HIP library %s is missing: run `python -c 'import __graft_entry__ as g; g.build()'`" % p)
     L = C.CDLL(p)
-    L.lmono_create.restype = C.c_void_p
-    L.lmono_create.argtypes = [C.c_int]
-    L.lmono_destroy.argtypes = [C.c_void_p]
-    L.lmono_last_error.restype = C.c_char_p
-    L.lmono_last_error.argtypes = [C.c_void_p]
-    L.lmono_version.restype = C.c_char_p
-    L.lmono_set_stream.argtypes = [C.c_void_p, C.c_void_p]
-    L.lmono_use_own_stream.argtypes = [C.c_void_p]
-    L.lmono_synchronize.argtypes = [C.c_void_p]
-    L.lmono_set_option.argtypes = [C.c_void_p, C.c_int, C.c_int]
-    L.lmono_get_option.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
-    L.lmono_batch_create.restype = C.c_void_p
-    L.lmono_batch_create.argtypes = [C.c_void_p, C.c_int, C.c_int64]
-    L.lmono_batch_destroy.argtypes = [C.c_void_p]
-    L.lmono_scanreg_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float]
-    L.lmono_scanreg_batch_h.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float]
-    L.lmono_host_alloc.restype = C.c_void_p
-    L.lmono_host_alloc.argtypes = [C.c_void_p, C.c_size_t]
-    L.lmono_host_free.argtypes = [C.c_void_p, C.c_void_p]
-    L.lmono_batch_stage_h.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
-    L.lmono_scanreg_batch_staged.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float]
-    L.lmono_batch_counts.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-    L.lmono_batch_get_cloud.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int]
-    L.lmono_batch_get_curvature.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
-    L.lmono_odom_batch.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
-    L.lmono_odom_batch_d.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
-    L.lmono_odom_shard_d.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
-    L.lmono_odom_shard_main_d.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]
-    L.lmono_odom_shard_validate.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.lmono_odom_boundary_report.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
-    L.lmono_odom_stream_create.restype = C.c_void_p
-    L.lmono_odom_stream_create.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_int]
-    L.lmono_odom_stream_destroy.argtypes = [C.c_void_p]
-    L.lmono_odom_step.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 5
-    L.lmono_odom_stream_scan.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-    L.lmono_odom_correspond.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
-    L.lmono_timing_reset.argtypes = [C.c_void_p]
-    L.lmono_triangulate.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 9 + [C.c_int, C.c_int, C.c_double, C.c_int]
-    L.lmono_outlier_scores.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 8 + [C.c_int, C.c_double, C.c_void_p]
-    L.lmono_shift_depth.argtypes = [C.c_void_p] * 6 + [C.c_int] + [C.c_void_p] * 3
-    L.lmono_shift_depth_batch.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 5
-    L.lmono_marginalize.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 14
-    L.lmono_marg_evaluate.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 5
-    L.lmono_marg_second_new.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 7
-    L.lmono_ba_batch_create.restype = C.c_void_p
-    L.lmono_ba_batch_create.argtypes = [C.c_void_p, C.c_void_p]
-    L.lmono_ba_batch_destroy.argtypes = [C.c_void_p]
-    L.lmono_ba_batch_update.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-    L.lmono_ba_solve.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
-    L.lmono_ba_batch_reset.argtypes = [C.c_void_p, C.c_void_p]
-    L.lmono_ba_batch_read.argtypes = [C.c_void_p] * 6
-    L.lmono_debug_bounds.argtypes = [C.c_void_p, C.c_void_p]
-    L.lmono_factor_eval.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 5
-    L.lmono_factor_eval_d.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 5
-    L.lmono_factor_eval_blocks.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 6
-    L.lmono_factor_eval_blocks_d.argtypes = [C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 6
-    L.lmono_pose_prefix_d.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p]
-    L.lmono_pose_rebase_d.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int]
-    L.lmono_timing_read.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
-    L.lmono_pnp_ransac.argtypes = [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 8
+    for name, (restype, argtypes) in PROTOTYPES.items():
+        try:
+            fn = getattr(L, name)
+        except AttributeError:
+            raise LmonoError("HIP library %s does not export %s" % (p, name)) from None
+        fn.restype = restype
+        fn.argtypes = argtypes
     _lib = L
     return L
 
@@ -130,18 +57,17 @@ class Context:
         if not self.h:
             raise LmonoError("lmono_create(%d) failed: no usable HIP device" % device)
         self.device = device
-        if os.environ.get("LMONO_CORR_TILE") is not None:       # A/B switches for measurements
-            self.L.lmono_set_option(self.h, 0, int(os.environ["LMONO_CORR_TILE"]))
-        if os.environ.get("LMONO_LEAD_FULL") is not None:
-            self.L.lmono_set_option(self.h, 3, int(os.environ["LMONO_LEAD_FULL"]))
-        if os.environ.get("LMONO_ODOM_STREAMS") is not None:
-            self.L.lmono_set_option(self.h, 2, int(os.environ["LMONO_ODOM_STREAMS"]))
-        if os.environ.get("LMONO_BOUNDARY_TOL") is not None:
-            self.L.lmono_set_option(self.h, 4, int(os.environ["LMONO_BOUNDARY_TOL"]))
+        for env, key in (("LMONO_CORR_TILE", self.OPT_CORR_TILE), ("LMONO_LEAD_FULL", self.OPT_LEAD_FULL),       # A/B switches for measurements
+                         ("LMONO_ODOM_STREAMS", self.OPT_ODOM_STREAMS), ("LMONO_BOUNDARY_TOL", self.OPT_BOUNDARY_TOL)):
+            if os.environ.get(env) is not None:
+                self.L.lmono_set_option(self.h, key, int(os.environ[env]))
 
     def check(self, rc):
+        """rc of a library call, or an LmonoError with the library's message and the C return value in .code."""
         if rc < 0:
-            raise LmonoError("lmono error %d: %s" % (rc, self.L.lmono_last_error(self.h).decode()))
+            e = LmonoError("lmono error %d: %s" % (rc, self.last_error()))
+            e.code = int(rc)
+            raise e
         return rc
 
     def last_error(self):
@@ -340,20 +266,6 @@ class Context:
     def pose_rebase_d(self, bases_ptr, n_bases, poses_ptr, n):
         self.check(self.L.lmono_pose_rebase_d(self.h, C.c_void_p(bases_ptr or 0), n_bases, C.c_void_p(poses_ptr), n))
 
-    def close(self):
-        if getattr(self, "h", None):
-            for child in list(self._children):
-                child.close()
-            self.L.lmono_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
     def voxel_filter(self, clouds, leafs):
         """pcl::VoxelGrid on a list of [n,4] float32 clouds (one leaf size each): list of filtered clouds."""
         arrs = [np.ascontiguousarray(a, np.float32).reshape(-1, 4) for a in clouds]
@@ -363,7 +275,6 @@ class Context:
         leaf = np.ascontiguousarray(leafs, np.float32)
         out = np.zeros_like(cat) if len(cat) else np.zeros((1, 4), np.float32)
         oo = np.zeros(len(arrs) + 1, np.int64)
-        self.L.lmono_voxel_filter.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 5
         self.check(self.L.lmono_voxel_filter(self.h, len(arrs), cat.ctypes.data, off.ctypes.data, leaf.ctypes.data, out.ctypes.data, oo.ctypes.data))
         return [out[oo[k]:oo[k + 1]].copy() for k in range(len(arrs))]
 
@@ -382,21 +293,62 @@ class Context:
         poses = np.ascontiguousarray(poses_qt, np.float64).reshape(ns, 7).copy()
         stats = np.zeros((ns, 8), np.int32)
         nn = np.zeros((int(cso[-1] + sso[-1]), 5), np.int32) if want_nn else None
-        self.L.lmono_map_refine.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 11
         self.check(self.L.lmono_map_refine(self.h, ns, cm.ctypes.data, cmo.ctypes.data, sm.ctypes.data, smo.ctypes.data,
                                            cs.ctypes.data, cso.ctypes.data, ss.ctypes.data, sso.ctypes.data,
                                            poses.ctypes.data, stats.ctypes.data, nn.ctypes.data if want_nn else None))
         return poses, stats, nn
 
-class OdomStream:
+    def close(self):
+        if getattr(self, "h", None):
+            for child in list(self._children):
+                child.close()
+            self.L.lmono_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class _Handle:
+    """Base of the wrappers that own one library object: registered with the context, which closes its children before itself
+    (their destroy calls touch the context's stream); close() is idempotent and safe on a half-constructed object."""
+
+    _destroy = None       # name of the C function that frees the handle
+
+    def __init__(self, ctx):
+        self.ctx = ctx
+        self.h = None
+        ctx._children.add(self)
+
+    def _create(self, fn, *args):
+        """self.h = fn(ctx, *args); a null handle raises with the library's reason."""
+        self.h = getattr(self.ctx.L, fn)(self.ctx.h, *args)
+        if not self.h:
+            raise LmonoError("%s failed: %s" % (fn, self.ctx.last_error()))
+
+    def close(self):
+        if getattr(self, "h", None):
+            getattr(self.ctx.L, self._destroy)(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class OdomStream(_Handle):
     """Online laserOdometry (lmono_odom_stream): one scan per step(), the previous scan's features stay on the device."""
 
+    _destroy = "lmono_odom_stream_destroy"
+
     def __init__(self, ctx, max_points, n_lines=64, min_range=5.0, history=8):
-        self.ctx = ctx
-        ctx._children.add(self)
-        self.h = ctx.L.lmono_odom_stream_create(ctx.h, int(max_points), int(n_lines), float(min_range), int(history))
-        if not self.h:
-            raise LmonoError("lmono_odom_stream_create failed: %s" % ctx.L.lmono_last_error(ctx.h).decode())
+        super().__init__(ctx)
+        self._create("lmono_odom_stream_create", int(max_points), int(n_lines), float(min_range), int(history))
 
     def step(self, xyzi=None, dev_ptr=None, n_points=None, warm_start=None):
         """xyzi: [n,4] float32 host array, or dev_ptr + n_points for a scan resident in HBM.  Returns (incr [7] = q_last_curr xyzw +
@@ -426,17 +378,6 @@ class OdomStream:
         n = self.ctx.check(self.ctx.L.lmono_batch_get_cloud(self.ctx.h, C.c_void_p(bh), sc, which, out.ctypes.data, cap))
         return out[:n]
 
-    def close(self):
-        if getattr(self, "h", None):
-            self.ctx.L.lmono_odom_stream_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 class BoundaryReport(C.Structure):
     """lmono_boundary_report (include/lmono_hip.h)"""
@@ -444,15 +385,14 @@ class BoundaryReport(C.Structure):
                 ("unresolved", C.c_int), ("tol", C.c_double), ("max_resid", C.c_double), ("repair_ms", C.c_double)]
 
 
-class ScanBatch:
+class ScanBatch(_Handle):
     """Device-resident working set of a batch of scans (lmono_scan_batch)."""
 
+    _destroy = "lmono_batch_destroy"
+
     def __init__(self, ctx, n_scans_cap, total_points_cap):
-        self.ctx = ctx
-        ctx._children.add(self)
-        self.h = ctx.L.lmono_batch_create(ctx.h, int(n_scans_cap), int(total_points_cap))
-        if not self.h:
-            raise LmonoError("lmono_batch_create failed: %s" % ctx.L.lmono_last_error(ctx.h).decode())
+        super().__init__(ctx)
+        self._create("lmono_batch_create", int(n_scans_cap), int(total_points_cap))
         self.n_scans = 0
         self._keep = None
 
@@ -543,17 +483,6 @@ class ScanBatch:
         n = self.ctx.check(self.ctx.L.lmono_odom_correspond(self.ctx.h, self.h, scan, q.ctypes.data, t.ctypes.data, out.ctypes.data, MAX_QUERIES))
         return out[:n]
 
-    def close(self):
-        if getattr(self, "h", None):
-            self.ctx.L.lmono_batch_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 class BaDesc(C.Structure):
     _fields_ = [("n_windows", C.c_int), ("feat_off", C.c_void_p), ("obs_off", C.c_void_p), ("flags", C.c_void_p),
@@ -562,17 +491,16 @@ class BaDesc(C.Structure):
                 ("prior_T", C.c_void_p), ("laser_info", C.c_void_p), ("mono_info", C.c_void_p), ("prior_w", C.c_void_p)]
 
 
-class BaBatch:
+class BaBatch(_Handle):
     """Batch of independent BA windows resident in HBM (lmono_ba_batch).  `windows`: list of dicts with the keys of
     tests/ba_cases.make_window (poses [n,7], ex, inv_depth, obs_feat/obs_i/obs_j, obs_pts, laser_consts, prior_T, flags)."""
 
+    _destroy = "lmono_ba_batch_destroy"
+
     def __init__(self, ctx, windows):
-        self.ctx = ctx
-        ctx._children.add(self)
+        super().__init__(ctx)
         d = self._desc(windows)
-        self.h = ctx.L.lmono_ba_batch_create(ctx.h, C.byref(d))
-        if not self.h:
-            raise LmonoError("lmono_ba_batch_create failed: %s" % ctx.L.lmono_last_error(ctx.h).decode())
+        self._create("lmono_ba_batch_create", C.byref(d))
 
     def update(self, windows):
         """Load another set of windows into the same device arrays (lmono_ba_batch_update)."""
@@ -616,33 +544,15 @@ class BaBatch:
         self.ctx.check(self.ctx.L.lmono_ba_batch_read(self.ctx.h, self.h, poses.ctypes.data, ex.ctypes.data, invd.ctypes.data, sm.ctypes.data))
         return poses, ex, invd, sm
 
-    def close(self):
-        if getattr(self, "h", None):
-            self.ctx.L.lmono_ba_batch_destroy(self.h)
-            self.h = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class Mapper:
+class Mapper(_Handle):
     """laserMapping with a device-resident cube map (lmono_mapper_*): process(batch, scan, q_wodom, t_wodom) per frame."""
 
+    _destroy = "lmono_mapper_destroy"
+
     def __init__(self, ctx, line_res=0.4, plane_res=0.8):
-        self.ctx = ctx
-        ctx._children.add(self)
-        L = ctx.L
-        L.lmono_mapper_create.restype = C.c_void_p
-        L.lmono_mapper_create.argtypes = [C.c_void_p, C.c_float, C.c_float]
-        L.lmono_mapper_destroy.argtypes = [C.c_void_p]
-        L.lmono_mapper_process.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 5
-        L.lmono_mapper_cube.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int]
-        self.h = L.lmono_mapper_create(ctx.h, line_res, plane_res)
-        if not self.h:
-            raise LmonoError("lmono_mapper_create failed: " + ctx.last_error())
+        super().__init__(ctx)
+        self._create("lmono_mapper_create", line_res, plane_res)
 
     def process(self, batch, scan, q_wodom, t_wodom):
         q = np.ascontiguousarray(q_wodom, np.float64); t = np.ascontiguousarray(t_wodom, np.float64)
@@ -652,7 +562,6 @@ class Mapper:
         return qo, to, st
 
     def reset(self):
-        self.ctx.L.lmono_mapper_reset.argtypes = [C.c_void_p, C.c_void_p]
         self.ctx.check(self.ctx.L.lmono_mapper_reset(self.ctx.h, self.h))
 
     @staticmethod
@@ -664,7 +573,6 @@ class Mapper:
         sc = np.ascontiguousarray(scans, np.int32)
         q = np.ascontiguousarray(q_wodom, np.float64).reshape(n, 4); t = np.ascontiguousarray(t_wodom, np.float64).reshape(n, 3)
         qo = np.zeros((n, 4)); to = np.zeros((n, 3)); st = np.zeros((n, 8), np.int32)
-        ctx.L.lmono_mapper_process_batch.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 8
         ctx.check(ctx.L.lmono_mapper_process_batch(ctx.h, n, mh, bh, sc.ctypes.data, q.ctypes.data, t.ctypes.data, qo.ctypes.data, to.ctypes.data, st.ctypes.data))
         return qo, to, st
 
@@ -675,18 +583,6 @@ class Mapper:
         if n > 0:
             self.ctx.check(min(self.ctx.L.lmono_mapper_cube(self.ctx.h, self.h, which, i, j, k, out.ctypes.data, n), 0))
         return out[:n]
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.ctx.L.lmono_mapper_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 
 class Camera(C.Structure):
@@ -709,29 +605,17 @@ def lidar_to_camera(rlc, tlc):
     return M
 
 
-class MapBuilder:
+class MapBuilder(_Handle):
     """MapBuilder::associateToMap / depthFill / rgb_map accumulation on the device (lmono_map_builder_*)."""
 
+    _destroy = "lmono_map_builder_destroy"
+
     def __init__(self, ctx, camera, max_cloud_points=1 << 18, map_capacity_points=None):
-        self.ctx = ctx
-        ctx._children.add(self)
+        super().__init__(ctx)
         self.cam = camera
-        L = ctx.L
-        L.lmono_map_builder_create.restype = C.c_void_p
-        L.lmono_map_builder_create.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int64]
-        L.lmono_map_builder_destroy.argtypes = [C.c_void_p]
-        L.lmono_associate_to_map.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 5
-        L.lmono_associate_to_map_batch.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 8
-        L.lmono_map_builder_depth.argtypes = [C.c_void_p] * 3
-        L.lmono_map_builder_cloud.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int]
-        L.lmono_map_builder_map.restype = C.c_int64
-        L.lmono_map_builder_map.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
-        L.lmono_map_builder_clear.argtypes = [C.c_void_p, C.c_void_p]
         if map_capacity_points is None:
             map_capacity_points = 10 * camera.width * camera.height      # processMapping flushes every 10 frames
-        self.h = L.lmono_map_builder_create(ctx.h, C.byref(camera), int(max_cloud_points), int(map_capacity_points))
-        if not self.h:
-            raise LmonoError("lmono_map_builder_create failed: " + ctx.last_error())
+        self._create("lmono_map_builder_create", C.byref(camera), int(max_cloud_points), int(map_capacity_points))
 
     def associate(self, xyzi, transform, bgr, q_wc, t_wc):
         """One associateToMap on host buffers; returns the size of the coloured cloud."""
@@ -780,58 +664,20 @@ class MapBuilder:
     def clear(self):
         self.ctx.check(self.ctx.L.lmono_map_builder_clear(self.ctx.h, self.h))
 
-    def close(self):
-        if getattr(self, "h", None):
-            self.ctx.L.lmono_map_builder_destroy(self.h)
-            self.h = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-def _voxel_map_prototypes(L):
-    L.lmono_voxel_map_create.restype = C.c_void_p
-    L.lmono_voxel_map_create.argtypes = [C.c_void_p, C.c_float, C.c_int64]
-    L.lmono_voxel_map_destroy.argtypes = [C.c_void_p]
-    L.lmono_voxel_map_clear.argtypes = [C.c_void_p, C.c_void_p]
-    L.lmono_voxel_map_insert.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
-    L.lmono_voxel_map_insert_d.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
-    L.lmono_voxel_map_insert_frames.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.lmono_voxel_map_size.restype = C.c_int64
-    L.lmono_voxel_map_size.argtypes = [C.c_void_p, C.c_void_p]
-    L.lmono_voxel_map_read.restype = C.c_int64
-    L.lmono_voxel_map_read.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
-    L.lmono_voxel_map_cells.restype = C.c_int64
-    L.lmono_voxel_map_cells.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
-    L.lmono_voxel_map_tile.restype = C.c_int
-    L.lmono_voxel_map_compose.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-
-
-class VoxelMap:
+class VoxelMap(_Handle):
     """The voxel-grid global colour map on the device (lmono_voxel_map_*): clouds of POINT_RGB folded in frame by frame,
     bounded by the number of occupied voxels, the same bytes for every insertion order.  insert* return the call's stats
     [points inserted, points rejected, voxels new, voxels afterwards]; an LmonoError carries the C return value in .code."""
 
+    _destroy = "lmono_voxel_map_destroy"
+
     def __init__(self, ctx, leaf=0.1, max_voxels=1 << 22):
-        self.ctx = ctx
-        ctx._children.add(self)
-        _voxel_map_prototypes(ctx.L)
+        super().__init__(ctx)
         self.leaf = float(np.float32(leaf))
         self.max_voxels = int(max_voxels)
         self.TILE = int(ctx.L.lmono_voxel_map_tile())       # points a workgroup of the insert sums on chip
-        self.h = ctx.L.lmono_voxel_map_create(ctx.h, C.c_float(leaf), int(max_voxels))
-        if not self.h:
-            raise LmonoError("lmono_voxel_map_create failed: " + ctx.last_error())
-
-    def _check(self, rc):
-        if rc < 0:
-            e = LmonoError("lmono error %d: %s" % (rc, self.ctx.last_error()))
-            e.code = int(rc)
-            raise e
-        return rc
+        self._create("lmono_voxel_map_create", C.c_float(leaf), int(max_voxels))
 
     def insert(self, points, bgra=None):
         """points: a POINT_RGB array, or xyz [n][3] float32 with bgra [n] uint32."""
@@ -844,13 +690,13 @@ class VoxelMap:
             if p.dtype != POINT_RGB:
                 raise LmonoError("points must be a POINT_RGB array (or xyz float32 with bgra uint32)")
         stats = np.zeros(4, np.int64)
-        self._check(self.ctx.L.lmono_voxel_map_insert(self.ctx.h, self.h, p.ctypes.data if len(p) else None, len(p), stats.ctypes.data))
+        self.ctx.check(self.ctx.L.lmono_voxel_map_insert(self.ctx.h, self.h, p.ctypes.data if len(p) else None, len(p), stats.ctypes.data))
         return stats
 
     def insert_d(self, ptr, n):
         """n lmono_point_rgb records in device memory."""
         stats = np.zeros(4, np.int64)
-        self._check(self.ctx.L.lmono_voxel_map_insert_d(self.ctx.h, self.h, C.c_void_p(int(ptr)), int(n), stats.ctypes.data))
+        self.ctx.check(self.ctx.L.lmono_voxel_map_insert_d(self.ctx.h, self.h, C.c_void_p(int(ptr)), int(n), stats.ctypes.data))
         return stats
 
     def insert_frame(self, builder):
@@ -865,29 +711,25 @@ class VoxelMap:
             raise LmonoError("one builder per map")
         mh = (C.c_void_p * n)(*[m.h for m in maps]); bh = (C.c_void_p * n)(*[b.h for b in builders])
         stats = np.zeros((n, 4), np.int64)
-        rc = ctx.L.lmono_voxel_map_insert_frames(ctx.h, n, mh, bh, stats.ctypes.data)
-        if rc < 0:
-            e = LmonoError("lmono error %d: %s" % (rc, ctx.last_error()))
-            e.code = int(rc)
-            raise e
+        ctx.check(ctx.L.lmono_voxel_map_insert_frames(ctx.h, n, mh, bh, stats.ctypes.data))
         return stats
 
     @property
     def size(self):
-        return int(self._check(self.ctx.L.lmono_voxel_map_size(self.ctx.h, self.h)))
+        return int(self.ctx.check(self.ctx.L.lmono_voxel_map_size(self.ctx.h, self.h)))
 
     def read(self):
         """One POINT_RGB per voxel, ascending key order (z-major, then y, then x)."""
         n = self.size
         out = np.zeros(max(n, 1), POINT_RGB)
-        self._check(self.ctx.L.lmono_voxel_map_read(self.ctx.h, self.h, out.ctypes.data, n))
+        self.ctx.check(self.ctx.L.lmono_voxel_map_read(self.ctx.h, self.h, out.ctypes.data, n))
         return out[:n]
 
     def cells(self):
         """Diagnostic view: keys [n] uint64 ascending, counts [n] uint32, sums [n][6] uint64 (offsets x y z, colour r g b)."""
         n = self.size
         keys = np.zeros(max(n, 1), np.uint64); counts = np.zeros(max(n, 1), np.uint32); sums = np.zeros((max(n, 1), 6), np.uint64)
-        self._check(self.ctx.L.lmono_voxel_map_cells(self.ctx.h, self.h, keys.ctypes.data, counts.ctypes.data, sums.ctypes.data, n))
+        self.ctx.check(self.ctx.L.lmono_voxel_map_cells(self.ctx.h, self.h, keys.ctypes.data, counts.ctypes.data, sums.ctypes.data, n))
         return keys[:n], counts[:n], sums[:n]
 
     @staticmethod
@@ -898,10 +740,9 @@ class VoxelMap:
         if n == 0 or len(filters) != n:
             raise LmonoError("one filter per map")
         ctx = maps[0].ctx
-        _sor_prototypes(ctx.L)
         mh = (C.c_void_p * n)(*[m.h for m in maps]); fh = (C.c_void_p * n)(*[f.h for f in filters])
         stats = np.zeros((n, 4), np.int64)
-        _raise_coded(ctx, ctx.L.lmono_voxel_map_insert_filtered(ctx.h, n, mh, fh, stats.ctypes.data))
+        ctx.check(ctx.L.lmono_voxel_map_insert_filtered(ctx.h, n, mh, fh, stats.ctypes.data))
         return stats
 
     def compose(self, sources, transforms, stats=False):
@@ -915,22 +756,11 @@ class VoxelMap:
             raise LmonoError("one 3 x 4 transform per source")
         sh = (C.c_void_p * max(n, 1))(*[s.h for s in sources])
         st = np.zeros(6, np.int64)
-        self._check(self.ctx.L.lmono_voxel_map_compose(self.ctx.h, self.h, n, sh, t.ctypes.data if n else None, st.ctypes.data))
+        self.ctx.check(self.ctx.L.lmono_voxel_map_compose(self.ctx.h, self.h, n, sh, t.ctypes.data if n else None, st.ctypes.data))
         return st if stats else None
 
     def clear(self):
-        self._check(self.ctx.L.lmono_voxel_map_clear(self.ctx.h, self.h))
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.ctx.L.lmono_voxel_map_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self.ctx.check(self.ctx.L.lmono_voxel_map_clear(self.ctx.h, self.h))
 
 
 def _pose_matrix(tq):
@@ -1020,44 +850,18 @@ class SubmapAtlas:
             pass
 
 
-def _raise_coded(ctx, rc):
-    if rc < 0:
-        e = LmonoError("lmono error %d: %s" % (rc, ctx.last_error()))
-        e.code = int(rc)
-        raise e
-    return rc
-
-
-def _sor_prototypes(L):
-    L.lmono_sor_create.restype = C.c_void_p
-    L.lmono_sor_create.argtypes = [C.c_void_p, C.c_int64, C.c_int, C.c_double, C.c_float, C.c_int]
-    L.lmono_sor_destroy.argtypes = [C.c_void_p]
-    L.lmono_sor_filter.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
-    L.lmono_sor_filter_d.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
-    L.lmono_sor_filter_frames.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.lmono_sor_cloud.restype = C.c_int64
-    L.lmono_sor_cloud.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
-    L.lmono_sor_scores.restype = C.c_int64
-    L.lmono_sor_scores.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64]
-    L.lmono_sor_threshold.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-    L.lmono_sor_diag.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-    L.lmono_voxel_map_insert_filtered.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-
-
-class OutlierFilter:
+class OutlierFilter(_Handle):
     """Statistical outlier removal on the device, between MapBuilder and VoxelMap (lmono_sor_*).  filter* return the call's
     stats [points in, rejected, isolated, scored, kept, A, Bhi, Blo]; the kept points stay on the device for VoxelMap.insert_filtered and
     come to the host with cloud().  An LmonoError carries the C return value in .code."""
 
+    _destroy = "lmono_sor_destroy"
+
     def __init__(self, ctx, max_points, mean_k=100, stddev_mul=1.0, cell=0.1, max_rings=8):
-        self.ctx = ctx
-        ctx._children.add(self)
-        _sor_prototypes(ctx.L)
+        super().__init__(ctx)
         self.max_points = int(max_points)
         self.stats = np.zeros(8, np.int64)
-        self.h = ctx.L.lmono_sor_create(ctx.h, int(max_points), int(mean_k), C.c_double(stddev_mul), C.c_float(cell), int(max_rings))
-        if not self.h:
-            raise LmonoError("lmono_sor_create failed: " + ctx.last_error())
+        self._create("lmono_sor_create", int(max_points), int(mean_k), C.c_double(stddev_mul), C.c_float(cell), int(max_rings))
 
     def filter(self, points):
         """points: a POINT_RGB array on the host."""
@@ -1065,14 +869,14 @@ class OutlierFilter:
         if p.dtype != POINT_RGB:
             raise LmonoError("points must be a POINT_RGB array")
         stats = np.zeros(8, np.int64)
-        _raise_coded(self.ctx, self.ctx.L.lmono_sor_filter(self.ctx.h, self.h, p.ctypes.data if len(p) else None, len(p), stats.ctypes.data))
+        self.ctx.check(self.ctx.L.lmono_sor_filter(self.ctx.h, self.h, p.ctypes.data if len(p) else None, len(p), stats.ctypes.data))
         self.stats = stats
         return stats
 
     def filter_d(self, ptr, n):
         """n lmono_point_rgb records in device memory."""
         stats = np.zeros(8, np.int64)
-        _raise_coded(self.ctx, self.ctx.L.lmono_sor_filter_d(self.ctx.h, self.h, C.c_void_p(int(ptr)), int(n), stats.ctypes.data))
+        self.ctx.check(self.ctx.L.lmono_sor_filter_d(self.ctx.h, self.h, C.c_void_p(int(ptr)), int(n), stats.ctypes.data))
         self.stats = stats
         return stats
 
@@ -1085,67 +889,41 @@ class OutlierFilter:
         ctx = filters[0].ctx
         fh = (C.c_void_p * n)(*[f.h for f in filters]); bh = (C.c_void_p * n)(*[b.h for b in builders])
         stats = np.zeros((n, 8), np.int64)
-        _raise_coded(ctx, ctx.L.lmono_sor_filter_frames(ctx.h, n, fh, bh, stats.ctypes.data))
+        ctx.check(ctx.L.lmono_sor_filter_frames(ctx.h, n, fh, bh, stats.ctypes.data))
         for f, s in zip(filters, stats):
             f.stats = s.copy()
         return stats
 
     def cloud(self):
         """The kept points of the last call, in input order."""
-        n = int(_raise_coded(self.ctx, self.ctx.L.lmono_sor_cloud(self.ctx.h, self.h, None, 0)))
+        n = int(self.ctx.check(self.ctx.L.lmono_sor_cloud(self.ctx.h, self.h, None, 0)))
         out = np.zeros(max(n, 1), POINT_RGB)
-        _raise_coded(self.ctx, self.ctx.L.lmono_sor_cloud(self.ctx.h, self.h, out.ctypes.data, n))
+        self.ctx.check(self.ctx.L.lmono_sor_cloud(self.ctx.h, self.h, out.ctypes.data, n))
         return out[:n]
 
     def scores(self):
         """Diagnostic view of the last call, per input point: keep [n] uint8 and v [n] uint32 (0xffffffff: isolated or rejected)."""
-        n = int(_raise_coded(self.ctx, self.ctx.L.lmono_sor_scores(self.ctx.h, self.h, None, None, 0)))
+        n = int(self.ctx.check(self.ctx.L.lmono_sor_scores(self.ctx.h, self.h, None, None, 0)))
         keep = np.zeros(max(n, 1), np.uint8); v = np.zeros(max(n, 1), np.uint32)
-        _raise_coded(self.ctx, self.ctx.L.lmono_sor_scores(self.ctx.h, self.h, keep.ctypes.data, v.ctypes.data, n))
+        self.ctx.check(self.ctx.L.lmono_sor_scores(self.ctx.h, self.h, keep.ctypes.data, v.ctypes.data, n))
         return keep[:n], v[:n]
 
     def threshold(self):
         """mean, sqrt(var), thr of the last call in v units (2^-16 m, summed over the mean_k distances)."""
         out = np.zeros(3, np.float64)
-        _raise_coded(self.ctx, self.ctx.L.lmono_sor_threshold(self.ctx.h, self.h, out.ctypes.data))
+        self.ctx.check(self.ctx.L.lmono_sor_threshold(self.ctx.h, self.h, out.ctypes.data))
         return out
 
     def diag(self):
         """Measurement view of the last call: rings scanned summed over the valid points, points scored by the radix select."""
         out = np.zeros(2, np.int64)
-        _raise_coded(self.ctx, self.ctx.L.lmono_sor_diag(self.ctx.h, self.h, out.ctypes.data))
+        self.ctx.check(self.ctx.L.lmono_sor_diag(self.ctx.h, self.h, out.ctypes.data))
         return out
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.ctx.L.lmono_sor_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 TRACK_RECORD = np.dtype([("id", np.int32), ("x_n", np.float32), ("y_n", np.float32), ("u", np.float32), ("v", np.float32),
                          ("vx", np.float32), ("vy", np.float32), ("track_cnt", np.int32)])
 TRACK_MAX_POINTS = 512
-
-
-def _tracker_prototypes(L):
-    L.lmono_tracker_create.restype = C.c_void_p
-    L.lmono_tracker_create.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int]
-    L.lmono_tracker_destroy.argtypes = [C.c_void_p]
-    L.lmono_tracker_reset.argtypes = [C.c_void_p, C.c_void_p]
-    L.lmono_tracker_track.argtypes = [C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
-    L.lmono_tracker_track_batch.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.lmono_tracker_pyramid.argtypes = [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 5
-    L.lmono_tracker_response.argtypes = [C.c_void_p] * 3
-    L.lmono_tracker_lk.argtypes = [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 4
-    L.lmono_tracker_set_reject_f.argtypes = [C.c_void_p] * 3
-    L.lmono_tracker_reject_stats.argtypes = [C.c_void_p] * 4
-    L.lmono_tracker_reject_f.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
 
 
 class RejectF(C.Structure):
@@ -1158,19 +936,17 @@ def feature_frame(records):
     return {int(r["id"]): [(0, np.array([r["x_n"], r["y_n"], r["u"], r["v"], r["vx"], r["vy"]], np.float64))] for r in records}
 
 
-class FeatureTracker:
+class FeatureTracker(_Handle):
     """FeatureTracker::trackImage of the mono path on the device (lmono_tracker_*): pyramidal KLT with forward-backward check,
     setMask, goodFeaturesToTrack, liftProjective and velocities.  track() returns the frame's TRACK_RECORD array."""
 
+    _destroy = "lmono_tracker_destroy"
+
     def __init__(self, ctx, camera, max_cnt=150, min_dist=30, flags=0):
-        self.ctx = ctx
-        ctx._children.add(self)
+        super().__init__(ctx)
         self.cam = camera
         self.max_cnt = int(max_cnt)
-        _tracker_prototypes(ctx.L)
-        self.h = ctx.L.lmono_tracker_create(ctx.h, C.byref(camera), int(max_cnt), int(min_dist), int(flags))
-        if not self.h:
-            raise LmonoError("lmono_tracker_create failed: " + ctx.last_error())
+        self._create("lmono_tracker_create", C.byref(camera), int(max_cnt), int(min_dist), int(flags))
 
     def _format(self, image):
         if image.shape == (self.cam.height, self.cam.width):
@@ -1247,17 +1023,6 @@ class FeatureTracker:
                                                          st.ctypes.data, stats.ctypes.data, F.ctypes.data))
         return st[:len(a)], stats, F
 
-    def close(self):
-        if getattr(self, "h", None):
-            self.ctx.L.lmono_tracker_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
 
 class FeatureTrackerBatch:
     """N independent FeatureTrackers advanced by one frame per call, every phase one launch (lmono_tracker_track_batch).
@@ -1313,35 +1078,6 @@ class BriefPattern(C.Structure):
     _fields_ = [("x1", C.c_int8 * 256), ("y1", C.c_int8 * 256), ("x2", C.c_int8 * 256), ("y2", C.c_int8 * 256)]
 
 
-def load_brief_pattern(path):
-    """Read an OpenCV-YAML pattern file in the list layout of the reference's brief_pattern.yml (a line `x1:` followed by one
-    `- <integer>` line per entry, likewise y1, x2, y2) -> int32 [4, 256] in the order x1, y1, x2, y2.  No YAML library."""
-    keys = ("x1", "y1", "x2", "y2")
-    got = {}
-    cur = None
-    with open(path) as f:
-        for no, raw in enumerate(f, 1):
-            line = raw.split("#")[0].strip() if not raw.startswith("%") else ""
-            if not line or line == "---":
-                continue
-            if line.endswith(":") and line[:-1].strip() in keys:
-                cur = line[:-1].strip()
-                if cur in got:
-                    raise LmonoError("%s:%d: key %s appears twice" % (path, no, cur))
-                got[cur] = []
-            elif line.startswith("-") and cur is not None:
-                try:
-                    got[cur].append(int(line[1:].strip()))
-                except ValueError:
-                    raise LmonoError("%s:%d: not an integer entry: %r" % (path, no, raw.rstrip())) from None
-            else:
-                raise LmonoError("%s:%d: not a line of a BRIEF pattern list: %r" % (path, no, raw.rstrip()))
-    for k in keys:
-        if len(got.get(k, ())) != 256:
-            raise LmonoError("%s: key %s has %d entries, a BRIEF pattern needs exactly 256" % (path, k, len(got.get(k, ()))))
-    return np.array([got[k] for k in keys], np.int32)
-
-
 def _brief_pattern_struct(pattern):
     p = np.asarray(pattern)
     if p.shape != (4, 256):
@@ -1354,242 +1090,19 @@ def _brief_pattern_struct(pattern):
     return s
 
 
-def _keyframes_prototypes(L):
-    L.lmono_keyframes_create.restype = C.c_void_p
-    L.lmono_keyframes_create.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int]
-    L.lmono_keyframes_destroy.argtypes = [C.c_void_p]
-    L.lmono_keyframes_clear.argtypes = [C.c_void_p, C.c_void_p]
-    L.lmono_keyframes_size.argtypes = [C.c_void_p, C.c_void_p]
-    L.lmono_keyframes_add.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.lmono_keyframes_add_batch.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 4
-    L.lmono_keyframes_load.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.lmono_keyframes_match.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 7
-    L.lmono_keyframes_images.argtypes = [C.c_void_p] * 4
-    L.lmono_keyframes_get.argtypes = [C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 7
-    L.lmono_keyframes_verify.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 16
-    L.lmono_brief_vocabulary_create.restype = C.c_void_p
-    L.lmono_brief_vocabulary_create.argtypes = [C.c_void_p] + [C.c_int] * 5 + [C.c_void_p] * 4 + [C.c_int, C.c_void_p, C.c_void_p]
-    L.lmono_brief_vocabulary_destroy.restype = None
-    L.lmono_brief_vocabulary_destroy.argtypes = [C.c_void_p]
-    L.lmono_brief_vocabulary_transform.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.lmono_keyframes_set_vocabulary.argtypes = [C.c_void_p] * 3
-    L.lmono_keyframes_bow.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.lmono_keyframes_query.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.lmono_keyframes_detect_loop.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int] + [C.c_void_p] * 4
-    L.lmono_keyframes_detect_loop_batch.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int] + [C.c_void_p] * 4
-
-
-# ---- BRIEF vocabulary: the file layout of the reference's VocabularyBinary.hpp, the checks, a trainer
-_VOC_NODE = np.dtype([("node_id", "<i4"), ("parent_id", "<i4"), ("weight", "<f8"), ("descriptor", "<u4", (8,))])      # 48 B: 4 x uint64 little-endian = 8 x uint32
-_VOC_WORD = np.dtype([("node_id", "<i4"), ("word_id", "<i4")])
-_VOC_KEYS = ("k", "L", "scoring", "weighting", "node_id", "parent_id", "weight", "descriptors", "word_node_id", "word_id")
-_POP8 = np.array([bin(i).count("1") for i in range(256)], np.int32)
-
-
-def _voc_arrays(voc):
-    """The arrays of a vocabulary dict in the types the C ABI reads."""
-    return (np.ascontiguousarray(voc["node_id"], np.int32).reshape(-1), np.ascontiguousarray(voc["parent_id"], np.int32).reshape(-1),
-            np.ascontiguousarray(voc["weight"], np.float64).reshape(-1), np.ascontiguousarray(voc["descriptors"], np.uint32).reshape(-1, 8),
-            np.ascontiguousarray(voc["word_node_id"], np.int32).reshape(-1), np.ascontiguousarray(voc["word_id"], np.int32).reshape(-1))
-
-
-def check_brief_vocabulary(voc):
-    """The checks lmono_brief_vocabulary_create makes on the host, in its order and words -> None for a well-formed vocabulary, else the
-    reason.  voc: dict with k, L, scoring, weighting (ints), node_id, parent_id, weight [nNodes], descriptors [nNodes, 8] uint32,
-    word_node_id, word_id [nWords]; node 0 is the root and has no record."""
-    k, L = int(voc["k"]), int(voc["L"])
-    nid, par, wt, de, wn, wi = _voc_arrays(voc)
-    n, nw = len(nid), len(wn)
-    if k < 2 or k > 64:
-        return "brief vocabulary: k outside 2..64"
-    if L < 1 or L > 10:
-        return "brief vocabulary: L outside 1..10"
-    if int(voc["scoring"]) != 0 or int(voc["weighting"]) != 0:
-        return "brief vocabulary: only L1_NORM scoring (0) with TF_IDF weighting (0) is built"
-    if n < 1 or n > 16777215:
-        return "brief vocabulary: nNodes outside 1..16777215"
-    if nw < 1 or nw > n:
-        return "brief vocabulary: nWords outside 1..nNodes"
-    if not (len(par) == len(wt) == len(de) == n) or len(wi) != nw:
-        return "brief vocabulary: a null array"
-    if not np.array_equal(np.sort(nid), np.arange(1, n + 1)):
-        return "brief vocabulary: nodeIds are not exactly 1..nNodes, each once"
-    if ((par < 0) | (par > n) | (par == nid)).any():
-        return "brief vocabulary: a parentId outside 0..nNodes or equal to its own nodeId"
-    if not (np.isfinite(wt) & (wt >= 0)).all():
-        return "brief vocabulary: a weight that is negative or not finite"
-    n_children = np.bincount(par, minlength=n + 1)
-    if n_children.max() > k:
-        return "brief vocabulary: an inner node with more than k children"
-    depth = np.full(n + 1, -1, np.int64)
-    depth[0] = 0
-    level = np.array([0])
-    for lv in range(1, L + 1):
-        level = nid[np.isin(par, level)]
-        depth[level] = lv
-    if (depth < 0).any():
-        return "brief vocabulary: a node unreachable from the root, or deeper than L"
-    bad = "brief vocabulary: the words are not a bijection between 0..nWords-1 and the leaves"
-    if int((n_children == 0).sum()) != nw or not np.array_equal(np.sort(wi), np.arange(nw)):
-        return bad
-    if ((wn < 1) | (wn > n)).any() or len(np.unique(wn)) != nw or (n_children[wn] != 0).any():
-        return bad
-    return None
-
-
-def load_brief_vocabulary(path):
-    """A vocabulary file in the layout of VocabularyBinary.hpp (6 int32 k, L, scoringType, weightingType, nNodes, nWords; nNodes records of
-    48 B; nWords records of 8 B) -> dict of plain arrays (see check_brief_vocabulary).  The bytes are not judged here."""
-    with open(path, "rb") as f:
-        raw = f.read()
-    if len(raw) < 24:
-        raise LmonoError("%s: shorter than the header of a vocabulary file" % path)
-    k, L, scoring, weighting, n, nw = (int(v) for v in np.frombuffer(raw, "<i4", 6))
-    if n < 0 or nw < 0 or len(raw) != 24 + 48 * n + 8 * nw:
-        raise LmonoError("%s: %d bytes, but the header (nNodes %d, nWords %d) asks for %d" % (path, len(raw), n, nw, 24 + 48 * n + 8 * nw))
-    nodes = np.frombuffer(raw, _VOC_NODE, n, 24)
-    words = np.frombuffer(raw, _VOC_WORD, nw, 24 + 48 * n)
-    return {"k": k, "L": L, "scoring": scoring, "weighting": weighting, "node_id": nodes["node_id"].astype(np.int32), "parent_id": nodes["parent_id"].astype(np.int32),
-            "weight": nodes["weight"].astype(np.float64), "descriptors": nodes["descriptor"].astype(np.uint32), "word_node_id": words["node_id"].astype(np.int32),
-            "word_id": words["word_id"].astype(np.int32)}
-
-
-def save_brief_vocabulary(path, voc):
-    """The inverse of load_brief_vocabulary: 24 + 48 nNodes + 8 nWords bytes."""
-    nid, par, wt, de, wn, wi = _voc_arrays(voc)
-    nodes = np.zeros(len(nid), _VOC_NODE)
-    nodes["node_id"] = nid; nodes["parent_id"] = par; nodes["weight"] = wt; nodes["descriptor"] = de
-    words = np.zeros(len(wn), _VOC_WORD)
-    words["node_id"] = wn; words["word_id"] = wi
-    with open(path, "wb") as f:
-        f.write(np.array([voc["k"], voc["L"], voc["scoring"], voc["weighting"], len(nid), len(wn)], "<i4").tobytes())
-        f.write(nodes.tobytes())
-        f.write(words.tobytes())
-
-
-def _mix32(x):
-    """The hash of DESIGN.md 6e (item 4a.2) on uint32."""
-    x &= 0xFFFFFFFF
-    x ^= x >> 16; x = (x * 0x7feb352d) & 0xFFFFFFFF
-    x ^= x >> 15; x = (x * 0x846ca68b) & 0xFFFFFFFF
-    x ^= x >> 16
-    return x
-
-
-def _hamming_to(desc, centre):
-    """[n, 8] uint32 x [8] uint32 -> int32 [n]."""
-    return _POP8[(desc ^ centre[None, :]).view(np.uint8)].sum(1).astype(np.int32)
-
-
-def _voc_words_of(voc, desc):
-    """The word of every descriptor by the descent of 6h (the nearest child, ties to the first in file order) -> int32 [n]."""
-    nid, par, wt, de, wn, wi = _voc_arrays(voc)
-    kids = {}
-    for r in range(len(nid)):
-        kids.setdefault(int(par[r]), []).append(r)
-    word_of = {int(a): int(b) for a, b in zip(wn, wi)}
-    out = np.zeros(len(desc), np.int32)
-    for i, d in enumerate(desc):
-        node = 0
-        while node in kids:
-            rows = kids[node]
-            node = int(nid[rows[int(np.argmin(_hamming_to(de[rows], d)))]])         # argmin: the first of equal distances
-        out[i] = word_of[node]
-    return out
-
-
-def train_brief_vocabulary(descriptor_sets, k, L, seed=0):
-    """A vocabulary from this project's own descriptors: hierarchical k-majority clustering of DESIGN.md 6h (a definition of this project,
-    deterministic in seed; offline tooling, plain numpy).  descriptor_sets: a list of [n_i, 8] uint32 arrays (one per image) -> dict."""
-    sets = [np.ascontiguousarray(s, np.uint32).reshape(-1, 8) for s in descriptor_sets]
-    if not (2 <= int(k) <= 64) or not (1 <= int(L) <= 10):
-        raise LmonoError("train_brief_vocabulary: k in 2..64 and L in 1..10")
-    desc = np.concatenate(sets) if sets else np.zeros((0, 8), np.uint32)
-    if len(desc) == 0:
-        raise LmonoError("train_brief_vocabulary: no descriptors")
-    nodes = []                       # (parent id, descriptor); node id = position + 1
-
-    def new_node(parent, d):
-        nodes.append((parent, np.array(d, np.uint32)))
-        return len(nodes)
-
-    def distinct(idx):
-        seen, out = set(), []
-        for i in idx:
-            key = desc[i].tobytes()
-            if key not in seen:
-                seen.add(key); out.append(i)
-        return out
-
-    def split(node, idx, level):
-        """The children of `node` (at `level`) over the descriptors idx."""
-        if len(idx) <= k:
-            for i in distinct(idx):
-                new_node(node, desc[i])
-            return
-        d = desc[idx]
-        first = _mix32(int(seed) ^ node) % len(idx)
-        centres = [d[first].copy()]
-        nearest = _hamming_to(d, centres[0])
-        while len(centres) < k:
-            far = int(np.argmax(nearest))                  # the farthest from its nearest centre, ties to the lowest index
-            if nearest[far] == 0:
-                break
-            centres.append(d[far].copy())
-            nearest = np.minimum(nearest, _hamming_to(d, centres[-1]))
-        centres = np.stack(centres)
-        bits = np.unpackbits(d.view(np.uint8), axis=1, bitorder="little")
-        assign = None
-        for _ in range(10):
-            dist = np.stack([_hamming_to(d, c) for c in centres], 1)
-            now = np.argmin(dist, 1)                       # ties to the lowest centre
-            if assign is not None and np.array_equal(now, assign):
-                break
-            assign = now
-            for c in range(len(centres)):
-                members = bits[assign == c]
-                if len(members):                           # an empty cluster keeps its centre
-                    vote = (2 * members.sum(0) > len(members)).astype(np.uint8)      # a tie gives bit 0
-                    centres[c] = np.packbits(vote, bitorder="little").view(np.uint32)
-        groups = [(c, [idx[i] for i in np.nonzero(assign == c)[0]]) for c in range(len(centres))]
-        groups = [(new_node(node, centres[c]), g) for c, g in groups if g]
-        if level + 1 < L:
-            for child, g in groups:
-                if len(g) > 1:
-                    split(child, g, level + 1)
-
-    split(0, list(range(len(desc))), 0)
-    parent = np.array([p for p, _ in nodes], np.int32)
-    node_id = np.arange(1, len(nodes) + 1, dtype=np.int32)
-    leaves = node_id[~np.isin(node_id, parent)]
-    voc = {"k": int(k), "L": int(L), "scoring": 0, "weighting": 0, "node_id": node_id, "parent_id": parent, "weight": np.zeros(len(nodes)),
-           "descriptors": np.stack([d for _, d in nodes]), "word_node_id": leaves.astype(np.int32), "word_id": np.arange(len(leaves), dtype=np.int32)}
-    # setNodeWeights (TemplatedVocabulary.h:942-): idf over the descriptor sets, by the words the finished tree gives them
-    n_i = np.zeros(len(leaves), np.int64)
-    for s in sets:
-        n_i[np.unique(_voc_words_of(voc, s))] += 1
-    weight = np.zeros(len(nodes))
-    for w, leaf in enumerate(leaves):
-        weight[leaf - 1] = float(np.log(len(sets) / n_i[w])) if n_i[w] > 0 else 0.0
-    voc["weight"] = weight
-    return voc
-
-
-class BriefVocabulary:
+class BriefVocabulary(_Handle):
     """A BRIEF vocabulary tree on the device (lmono_brief_vocabulary_*).  voc: the dict of load_brief_vocabulary /
-    train_brief_vocabulary; a malformed one is refused by the library with its reason."""
+    train_brief_vocabulary (brief_tools.py); a malformed one is refused by the library with its reason."""
+
+    _destroy = "lmono_brief_vocabulary_destroy"
 
     def __init__(self, ctx, voc):
-        self.ctx = ctx
-        ctx._children.add(self)
-        _keyframes_prototypes(ctx.L)
+        super().__init__(ctx)
         nid, par, wt, de, wn, wi = _voc_arrays(voc)
         if not (len(par) == len(wt) == len(de) == len(nid)) or len(wi) != len(wn):
             raise LmonoError("BriefVocabulary: the node arrays (and the word arrays) differ in length")
-        self.h = ctx.L.lmono_brief_vocabulary_create(ctx.h, int(voc["k"]), int(voc["L"]), int(voc["scoring"]), int(voc["weighting"]), len(nid), nid.ctypes.data,
-                                                     par.ctypes.data, wt.ctypes.data, de.ctypes.data, len(wn), wn.ctypes.data, wi.ctypes.data)
-        if not self.h:
-            raise LmonoError("lmono_brief_vocabulary_create failed: " + ctx.last_error())
+        self._create("lmono_brief_vocabulary_create", int(voc["k"]), int(voc["L"]), int(voc["scoring"]), int(voc["weighting"]), len(nid), nid.ctypes.data,
+                     par.ctypes.data, wt.ctypes.data, de.ctypes.data, len(wn), wn.ctypes.data, wi.ctypes.data)
 
     def transform(self, descriptors):
         """-> (word int32 [n], weight float64 [n]) of descriptors [n, 8] uint32."""
@@ -1597,17 +1110,6 @@ class BriefVocabulary:
         word = np.full(len(de), -1, np.int32); weight = np.zeros(len(de))
         self.ctx.check(self.ctx.L.lmono_brief_vocabulary_transform(self.ctx.h, self.h, len(de), de.ctypes.data, word.ctypes.data, weight.ctypes.data))
         return word, weight
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.ctx.L.lmono_brief_vocabulary_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 class PnPParams(C.Structure):
@@ -1639,20 +1141,6 @@ def pnp_ransac(ctx, points_3d, points_2d, guess_tq, keys=None, params=None):
     return [st[off[i]:off[i + 1]].copy() for i in range(n)], pose, stats
 
 
-def _excalib_prototypes(L):
-    if getattr(L, "_excalib_ready", False):
-        return
-    L.lmono_excalib_create.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
-    L.lmono_excalib_destroy.argtypes = [C.c_void_p]
-    L.lmono_excalib_destroy.restype = None
-    L.lmono_excalib_reset.argtypes = [C.c_void_p, C.c_int]
-    L.lmono_relative_rotation.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 4
-    L.lmono_excalib_push.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 3 + [C.c_int] + [C.c_void_p] * 4
-    L.lmono_excalib_step.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 4 + [C.c_int] + [C.c_void_p] * 6
-    L.lmono_excalib_state.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 3
-    L._excalib_ready = True
-
-
 def _pairs_arrays(pairs_list):
     """A list of [m, 4] arrays -> (m int32 [n], the rows concatenated, with one spare row so that the pointer is never null)."""
     ps = [np.ascontiguousarray(a, np.float64).reshape(-1, 4) for a in pairs_list]
@@ -1664,7 +1152,6 @@ def relative_rotation(ctx, pairs_list):
     """The camera's rotation increment of each problem from its pairs of normalised image points (lmono_relative_rotation, DESIGN.md 6i:
     essential matrix over all pairs, decomposition, cheirality vote), all problems in one launch.  pairs_list: a list of [m, 4] arrays
     (prev x, prev y, cur x, cur y; m <= 512) -> (R [n, 3, 3], stats [n, 6] = pairs used, the four front counts, the winner)."""
-    _excalib_prototypes(ctx.L)
     m, flat = _pairs_arrays(pairs_list)
     n = len(m)
     R = np.zeros((n, 3, 3)); stats = np.zeros((n, 6), np.int32)
@@ -1672,17 +1159,16 @@ def relative_rotation(ctx, pairs_list):
     return R, stats
 
 
-class ExtrinsicCalibrator:
+class ExtrinsicCalibrator(_Handle):
     """The camera-LiDAR rotation calibration of ESTIMATE_LASER == 2 for n_streams independent streams (lmono_excalib_*).
     Quaternions are x y z w.  `streams`: the stream index of each entry of a call (default 0 .. n-1); a stream may be named once per call."""
 
+    _destroy = "lmono_excalib_destroy"
+
     def __init__(self, ctx, n_streams=1, count=10):
-        self.ctx = ctx
-        ctx._children.add(self)
-        _excalib_prototypes(ctx.L)
+        super().__init__(ctx)
         self.n_streams, self.count = int(n_streams), int(count)
         h = C.c_void_p()
-        self.h = None
         ctx.check(ctx.L.lmono_excalib_create(ctx.h, self.n_streams, C.byref(h)))
         self.h = h.value
 
@@ -1727,31 +1213,18 @@ class ExtrinsicCalibrator:
     def reset(self, s=None):
         self.ctx.check(self.ctx.L.lmono_excalib_reset(self.h, -1 if s is None else int(s)))
 
-    def close(self):
-        if getattr(self, "h", None):
-            self.ctx.L.lmono_excalib_destroy(self.h)
-            self.h = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class KeyFrames:
+class KeyFrames(_Handle):
     """A device-resident store of keyframes (lmono_keyframes_*): FAST corners, BRIEF descriptors of the corners and of
     the window points, and the exhaustive Hamming search of KeyFrame::searchByBRIEFDes.  pattern: [4][256] (load_brief_pattern)."""
 
+    _destroy = "lmono_keyframes_destroy"
+
     def __init__(self, ctx, camera, pattern, max_keyframes=64, max_keypoints=4096, fast_threshold=0):
-        self.ctx = ctx
-        ctx._children.add(self)
+        super().__init__(ctx)
         self.cam = camera
-        _keyframes_prototypes(ctx.L)
         pat = _brief_pattern_struct(pattern)
-        self.h = ctx.L.lmono_keyframes_create(ctx.h, C.byref(camera), C.byref(pat), int(max_keyframes), int(max_keypoints), int(fast_threshold))
-        if not self.h:
-            raise LmonoError("lmono_keyframes_create failed: " + ctx.last_error())
+        self._create("lmono_keyframes_create", C.byref(camera), C.byref(pat), int(max_keyframes), int(max_keypoints), int(fast_threshold))
         self.last_n_keypoints = 0
 
     def _format(self, image):
@@ -1908,57 +1381,33 @@ class KeyFrames:
     def clear(self):
         self.ctx.check(self.ctx.L.lmono_keyframes_clear(self.ctx.h, self.h))
 
-    def close(self):
-        if getattr(self, "h", None):
-            self.ctx.L.lmono_keyframes_destroy(self.h)
-            self.h = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class PoseGraph:
+class PoseGraph(_Handle):
     """Loop-closure pose graph (lmono_pose_graph_*; a new feature): 4-DoF keyframe graph over odometry poses and
     loop_info records.  optimize() on one GPU; linearise() / reduce_buffer / step() for the multi-GPU round (sharding.py)."""
 
+    _destroy = "lmono_pose_graph_destroy"
+
     def __init__(self, ctx, poses_tq, loops, loop_info):
-        self.ctx = ctx
-        ctx._children.add(self)
+        super().__init__(ctx)
         L = ctx.L
-        L.lmono_pose_graph_create.restype = C.c_void_p
-        L.lmono_pose_graph_create.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
-        L.lmono_pose_graph_destroy.argtypes = [C.c_void_p]
-        L.lmono_pose_graph_info.argtypes = [C.c_void_p] * 4
-        L.lmono_pose_graph_reduce_buffer.restype = C.c_void_p
-        L.lmono_pose_graph_reduce_buffer.argtypes = [C.c_void_p]
-        L.lmono_pose_graph_linearise.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int]
-        L.lmono_pose_graph_step.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
-        L.lmono_pose_graph_optimize.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
-        L.lmono_pose_graph_result.argtypes = [C.c_void_p] * 4
         P = np.ascontiguousarray(poses_tq, np.float64).reshape(-1, 7)
         lp = np.ascontiguousarray(loops, np.int32).reshape(-1, 2); li = np.ascontiguousarray(loop_info, np.float64).reshape(-1, 8)
         if len(lp) != len(li):
             raise LmonoError("loops and loop_info differ in length")
         self.n = len(P)
-        self.h = L.lmono_pose_graph_create(ctx.h, self.n, P.ctypes.data, len(lp), lp.ctypes.data, li.ctypes.data)
-        if not self.h:
-            raise LmonoError("lmono_pose_graph_create failed: " + ctx.last_error())
+        self._create("lmono_pose_graph_create", self.n, P.ctypes.data, len(lp), lp.ctypes.data, li.ctypes.data)
         rc = C.c_int64(0); bw = C.c_int(0); ne = C.c_int(0)
         L.lmono_pose_graph_info(self.h, C.addressof(rc), C.addressof(bw), C.addressof(ne))
         self.reduce_count, self.bandwidth, self.n_edges = rc.value, bw.value, ne.value
         self.reduce_ptr = L.lmono_pose_graph_reduce_buffer(self.h)
 
     def reset(self):
-        self.ctx.L.lmono_pose_graph_reset.argtypes = [C.c_void_p, C.c_void_p]
         self.ctx.check(self.ctx.L.lmono_pose_graph_reset(self.ctx.h, self.h))
 
     def order(self):
         """Elimination position of every keyframe: the order H, g and cost are stored in inside the reduce buffer."""
         pos = np.zeros(self.n, np.int32)
-        self.ctx.L.lmono_pose_graph_order.argtypes = [C.c_void_p, C.c_void_p]
         self.ctx.check(self.ctx.L.lmono_pose_graph_order(self.h, pos.ctypes.data))
         return pos
 
@@ -1967,7 +1416,6 @@ class PoseGraph:
         reads (the tensor handed to torch.distributed.all_reduce)."""
         if tensor.numel() != self.reduce_count or tensor.element_size() != 8 or not tensor.is_contiguous():
             raise LmonoError("reduce tensor must be contiguous fp64 with %d elements" % self.reduce_count)
-        self.ctx.L.lmono_pose_graph_set_reduce_buffer.argtypes = [C.c_void_p, C.c_void_p]
         self.ctx.check(self.ctx.L.lmono_pose_graph_set_reduce_buffer(self.h, tensor.data_ptr()))
         self.reduce_tensor = tensor
         self.reduce_ptr = tensor.data_ptr()
@@ -1988,14 +1436,3 @@ class PoseGraph:
         out = np.zeros((self.n, 7)); st = np.zeros(6)
         self.ctx.check(self.ctx.L.lmono_pose_graph_result(self.ctx.h, self.h, out.ctypes.data, st.ctypes.data))
         return out, dict(iterations=int(st[0]), initial_cost=st[1], final_cost=st[2], bandwidth=int(st[3]), accepted=int(st[4]), rejected=int(st[5]))
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.ctx.L.lmono_pose_graph_destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

@@ -31,6 +31,60 @@ def test_every_declared_symbol_is_exported():
     assert b"gfx950" in ctypes.cast(lib.lmono_version, ctypes.CFUNCTYPE(ctypes.c_char_p))()
 
 
+_SCALARS = {"int": ctypes.c_int, "int32_t": ctypes.c_int, "uint32_t": ctypes.c_uint32, "int64_t": ctypes.c_int64, "size_t": ctypes.c_size_t,
+            "float": ctypes.c_float, "double": ctypes.c_double}
+
+
+def _header_prototypes():
+    """include/lmono_hip.h -> {name: (restype, [argtypes])} by the conventions of lmono_amd/_abi.py: every pointer or array parameter and
+    every pointer return is c_void_p, except a `const char *` return, which is c_char_p; a void return is None."""
+    txt = open(os.path.join(ROOT, "include", "lmono_hip.h")).read()
+    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
+    txt = "\n".join(line for line in txt.split("\n") if not line.lstrip().startswith("#"))
+
+    def scalar(words, what):
+        words = [w for w in words if w != "const"]
+        assert words and words[0] in _SCALARS, "unknown C type in %r" % what
+        return _SCALARS[words[0]]                          # a parameter's name, if any, follows the type
+
+    out = {}
+    for ret, name, args in re.findall(r"([A-Za-z_][A-Za-z_0-9 ]*?[ *]+)(lmono_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", txt):
+        assert name not in out, "declared twice: " + name
+        if "*" in ret:
+            restype = ctypes.c_char_p if ret.replace("*", " * ").split() == ["const", "char", "*"] else ctypes.c_void_p
+        else:
+            restype = None if ret.split() == ["void"] else scalar(ret.split(), ret + name)
+        args = args.strip()
+        argtypes = [] if args in ("", "void") else [ctypes.c_void_p if "*" in a or "[" in a else scalar(a.split(), a) for a in args.split(",")]
+        out[name] = (restype, argtypes)
+    return out
+
+
+def test_prototypes_match_header():
+    """The prototype table agrees with the header in every function's return type, arity and every argument; no function is left out."""
+    from lmono_amd import _abi
+    hdr = _header_prototypes()
+    assert sorted(hdr) == _declared()                      # a declaration the parser cannot read fails here
+    assert sorted(_abi.PROTOTYPES) == sorted(hdr)
+    for name, (restype, argtypes) in hdr.items():
+        got_res, got_args = _abi.PROTOTYPES[name]
+        assert got_res is restype, (name, got_res, restype)
+        assert len(got_args) == len(argtypes), (name, len(got_args), len(argtypes))
+        for k, (a, b) in enumerate(zip(got_args, argtypes)):
+            assert a is b, (name, k, a, b)
+
+
+def test_prototypes_applied_at_load():
+    """load_library() alone gives every function its prototype: no wrapper object has to be built first."""
+    import lmono_amd
+    from lmono_amd import _abi
+    lib = lmono_amd.load_library()
+    for name, (restype, argtypes) in _abi.PROTOTYPES.items():
+        fn = getattr(lib, name)
+        assert fn.restype is restype, (name, fn.restype, restype)
+        assert fn.argtypes is not None and list(fn.argtypes) == list(argtypes), (name, fn.argtypes, argtypes)
+
+
 def test_no_cpu_fallback_without_gpu():
     """The product path fails loudly when no GPU is present: lmono_create returns NULL -> LmonoError."""
     import pytest

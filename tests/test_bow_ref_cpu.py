@@ -1,6 +1,6 @@
 """The restatement tests/bow_ref.py of the loop detector's database pinned against things that are not the restatement: a
 literal inverted-file statement of DBoW2's query, exact rational arithmetic, a brute-force descent; the vocabulary file layout, the
-validator and the trainer of lmono_amd/capi.py; and lmono_amd/host/bow_test, the kernel bodies of lmono_amd/csrc/bow.hip run as plain
+validator and the trainer of lmono_amd/brief_tools.py; and lmono_amd/host/bow_test, the kernel bodies of lmono_amd/csrc/bow.hip run as plain
 C++.  No GPU."""
 import math
 import os

@@ -6,8 +6,10 @@
 //                offsets, scatter); every wave owns a 1024-point segment in both passes, no barriers inside the passes; the tag
 //                pass decides ring and half sweep without an arctangent (ring_decide.hpp), fp64 forms inside the guard bands
 //   k_curvature  one workgroup per 1024-point tile: LDS tile with +-5 halo, curvature and neighbour-gap flags
-//   k_select     one wave per (scan, ring): per-sector edge/planar selection as repeated 64-lane arg-max/arg-min (DPP
-//                reductions) over register-resident (curvature, index) keys with neighbour suppression (no sort needed);
+//   k_select     one wave per (scan, ring), a lane holds 5 / 6 / 11 consecutive points of a sector in registers: the <= 20 edge picks are
+//                the head of an independent set that parallel rounds settle (sel_rounds.hpp: winners against the ten neighbours in the
+//                lane's and the next lanes' registers, DPP wave shifts), ranked one member per lane; the <= 4 planar picks are repeated
+//                64-lane arg-min reductions (DPP) with neighbour suppression; no sort needed;
 //                rings longer than the small LDS slice go through a work list to a second launch
 //   k_voxel      one workgroup per (scan, ring): voxel-grid down-sampling of the less-flat points (run-length segments from
 //                ballots, bucket sort of the segment keys in LDS; <9 slots> / <16 slots> instantiations + work list)
@@ -16,6 +18,7 @@
 // Arithmetic is float/double exactly as the CPU restatement evaluates it (compiled with -ffp-contract=off).
 #include "batch.hpp"
 #include "ring_decide.hpp"
+#include "sel_rounds.hpp"
 #include "vox_runs.hpp"
 
 namespace lmono {
@@ -336,6 +339,9 @@ __global__ __launch_bounds__(256) void k_curvature(BatchView b)
 // extremum of the not-yet-suppressed points visit the same points in the same order, so no sort is needed: each lane
 // keeps its sector elements (curvature, suppressed flag) in registers and a pick is one 64-lane arg-max / arg-min
 // over the packed key (curvature bits, index), which also reproduces the (curvature, index) tie order of the sort.
+// The flat picks run exactly so.  The sharp picks do not take 21 reductions one after the other: the points that such a
+// walk takes are the 20 of highest key of an independent set that parallel rounds find (sel_rounds.hpp, two rounds for
+// most sectors), and they are ranked one per lane afterwards.
 constexpr int kSelMaxPerLane = (kRingCap / 6 + 1 + 63) / 64;   // 11 elements per lane for the largest legal sector
 
 // key of a sector element: hi = curvature bits, lo = (index << 8 | suppression reach).  Ordering by (hi, lo) = ordering by
@@ -344,8 +350,13 @@ constexpr int kSelMaxPerLane = (kRingCap / 6 + 1 + 63) / 64;   // 11 elements pe
 // extremum (the rule: equal curvatures in two lanes are rare), a second reduction over the low words settles the ties otherwise.
 __device__ __forceinline__ unsigned int select_lo(int idx, unsigned int reach) { return ((unsigned int)idx << 8) | reach; }
 
-// one sector of one ring, M register slots per lane (element m of a lane is ring-local index sp + lane + 64 m)
-constexpr int kSelScratch = 64 * 8;      // per wave: one (curvature bits, index | reach) pair per lane, the compacted candidates of a sector
+// whole-wave shifts by one lane (DPP wave_shr:1 / wave_shl:1): the value of the lane before / behind; 0 where the wave ends (bound_ctrl)
+__device__ __forceinline__ unsigned int lane_before(unsigned int v) { return (unsigned int)__builtin_amdgcn_update_dpp(0, (int)v, 0x138, 0xf, 0xf, true); }
+__device__ __forceinline__ unsigned int lane_behind(unsigned int v) { return (unsigned int)__builtin_amdgcn_update_dpp(0, (int)v, 0x130, 0xf, 0xf, true); }
+
+// one sector of one ring, M consecutive elements per lane (element m of a lane is ring-local index sp + lane M + m): the ten
+// neighbours that a round of the sharp picks compares an element with are registers of the lane or of the two lanes next to it
+constexpr int kSelScratch = 64 * 8;      // per wave: one (curvature bits, index | reach) pair per lane, the members of a sector for ranking
 
 template <int M>
 __device__ __forceinline__ void select_sector(int lane, int j, int sp, int slen, int rbeg, const float *curv, unsigned char *picked,
@@ -354,71 +365,107 @@ __device__ __forceinline__ void select_sector(int lane, int j, int sp, int slen,
 {
     unsigned int kh[M], kl[M];
     unsigned int dead = 0, big = 0, small = 0;     // bit m: suppressed / out of range; curvature > 0.1; < 0.1
-    int n_big = 0;                                 // live points with c > 0.1 (wave-uniform), compacted into `scratch` as they are loaded
+    const int e0 = lane * M;
+    // gap flags around the lane's elements, one window per lane: bit k = gap flag of point sp + e0 - 5 + k, k < M + 10 (two 8-byte LDS
+    // reads; sp >= 5, and a lane that holds an element reads inside the ring's words)
+    // A lane behind the sector's end reads the sector's last point instead and keeps nothing of it: no branch around the loads.
+    unsigned int gwin;
+    {
+        const int jw = sp + min(e0, slen - 1) - 5;
+        const unsigned long long wa = gap[jw >> 6], wb = gap[(jw >> 6) + 1];
+        const int sh = jw & 63;
+        gwin = (unsigned int)((wa >> sh) | (sh ? wb << (64 - sh) : 0ull));
+    }
+    // (double)c > 0.1 and (double)c < 0.1 as float compares: 0.1f is the smallest float above the double 0.1, so c > 0.1 iff c >= 0.1f and
+    // c < 0.1 iff c < 0.1f, for every float c (a NaN fails both either way)
 #pragma unroll
     for (int m = 0; m < M; m++) {
-        const int e = lane + 64 * m;
-        kh[m] = 0u; kl[m] = 0u;
-        bool cand = false;
-        if (e < slen) {
-            const int i = sp + e;
-            const float c = curv[i];
-            // suppression reach: the neighbour walk marks l = 1..5 forward while the gap before point i+l is short, and the same backward --
-            // the zero runs above / below bit i of the ring's gap BIT mask (two independent 8-byte LDS reads; as bytes the two walks were up to
-            // ten dependent single-byte reads per element, the latency that bound the kernel).  i >= 5 inside a sector.
-            const int jw = i - 5;
-            const unsigned long long wa = gap[jw >> 6], wb = gap[(jw >> 6) + 1];
-            const int sh = jw & 63;
-            const unsigned int win = (unsigned int)((wa >> sh) | (sh ? wb << (64 - sh) : 0ull));      // bit k = gap flag of point i - 5 + k
-            const int lf = min(5, __ffs((int)((win >> 5) | 32u)) - 1);
-            const int lb = min(5, __clz((int)((win & 31u) << 27)));
-            kh[m] = __float_as_uint(c); kl[m] = select_lo(i, (unsigned int)(lf | (lb << 4)));
-            const bool pk = picked[i] != 0;
-            if (pk) dead |= 1u << m;
-            if ((double)c > 0.1) { big |= 1u << m; cand = !pk; }
-            if ((double)c < 0.1) small |= 1u << m;
-        } else dead |= 1u << m;
-        {
-            const unsigned long long mk = __ballot(cand);
-            const int pos = n_big + __popcll(mk & ((1ull << lane) - 1ull));
-            if (cand && pos < 64) { scratch[2 * pos] = kh[m]; scratch[2 * pos + 1] = kl[m]; }
-            n_big += __popcll(mk);
-        }
+        const int e = e0 + m;
+        const bool in = e < slen;
+        const int i = sp + min(e, slen - 1);
+        const float c = curv[i];
+        // suppression reach: the neighbour walk marks l = 1..5 forward while the gap before point i+l is short, and the same backward --
+        // the zero runs above / below bit i of the ring's gap BIT mask
+        const unsigned int win = gwin >> m;                                                       // bit k = gap flag of point i - 5 + k
+        const int lf = min(5, __ffs((int)((win >> 5) | 32u)) - 1);
+        const int lb = min(5, __clz((int)((win & 31u) << 27)));
+        kh[m] = in ? __float_as_uint(c) : 0u; kl[m] = in ? select_lo(i, (unsigned int)(lf | (lb << 4))) : 0u;
+        dead |= (unsigned int)(!in | (picked[i] != 0)) << m;
+        big |= (unsigned int)(in & (c >= 0.1f)) << m;
+        small |= (unsigned int)(in & (c < 0.1f)) << m;
     }
     // ---- largest curvature first: <= 2 sharp, <= 20 less sharp
+    // The picks are the 20 members of highest key of the lexicographically first independent set of the live candidates (sel_rounds.hpp),
+    // which parallel rounds settle: winners join, what lies within a winner's reach dies, until nothing is live -- two rounds for most
+    // sectors, one per step for a staircase of curvatures.
     int largest = 0;
-    // Only the points with c > 0.1 that are not suppressed yet can be picked here -- a few dozen of a sector's ~300.  When they fit one per lane
-    // they are compacted (ballot ranks, through 512 B of LDS): a pick then costs one comparison per lane + the wave reduction instead of a pass
-    // over the lane's M slots.  Same live set, same (curvature, index) order: the same picks.  The slot bitmask `dead` is kept up to date for the
-    // flat picks below.
-    const bool compact = n_big <= 64;
-    if (compact) {
-        __builtin_amdgcn_wave_barrier();           // one wave: its LDS operations execute in order; the barrier keeps the compiler from reordering them
-        unsigned int ch = 0u, cl = 0u;
-        if (lane < n_big) { ch = scratch[2 * lane]; cl = scratch[2 * lane + 1]; }
-        __builtin_amdgcn_wave_barrier();           // the next sector's writes stay behind these reads
-        while (true) {
-            const unsigned int mh = wave_max_u32_uniform(ch);
-            if (mh == 0u) break;
-            const unsigned long long who = __ballot(ch == mh);
-            unsigned int lo;
-            if ((who & (who - 1ull)) == 0ull) lo = (unsigned int)__builtin_amdgcn_readlane((int)cl, __ffsll((long long)who) - 1);
-            else lo = wave_max_u32_uniform(ch == mh ? cl : 0u);
-            const int pind = (int)(lo >> 8), lf = (int)(lo & 15u), lb = (int)((lo >> 4) & 15u);
-            largest++;
-            if (largest > 20) break;
-            if (lane == 0) { sel_sh[j * 20 + largest - 1] = rbeg + pind; label[pind] = largest <= 2 ? 2 : 1; }
-            if (lane <= lf + lb) picked[pind - lb + lane] = 1;
-            // the compacted candidate of this lane is suppressed iff its index lies in [pind - lb, pind + lf]
-            if ((unsigned int)((int)(cl >> 8) - (pind - lb)) <= (unsigned int)(lb + lf)) ch = 0u;
-            {
-                const int a = pind - lb - sp - lane;                 // slot m is hit iff a <= 64 m <= a + lb + lf
-                const int m0 = (a + 63) >> 6;
-                if (m0 >= 0 && m0 < M && 64 * m0 <= a + lb + lf) dead |= 1u << m0;
+    unsigned int members = 0u;
+    {
+        unsigned int live = big & ~dead;
+        while (__ballot(live != 0u)) {
+            unsigned int x[M + 2 * kSelReach];
+#pragma unroll
+            for (int m = 0; m < M; m++) x[m + kSelReach] = kh[m] & (unsigned int)((int)(live << (31 - m)) >> 31);
+#pragma unroll
+            for (int d = 0; d < kSelReach; d++) {
+                x[d] = lane_before(x[M + d]);                            // element M - 5 + d of the lane before
+                x[M + kSelReach + d] = lane_behind(x[kSelReach + d]);     // element d of the lane behind
             }
+            const unsigned int w = sel_winners<M>(x, gwin);
+            members |= w;
+            live &= ~sel_deaths<M>(sel_window<M>(lane_before(w), w, lane_behind(w)), gwin);
         }
     }
-    while (!compact) {
+    int n_mem = 0;
+#pragma unroll
+    for (int m = 0; m < M; m++) n_mem += __popcll(__ballot((members >> m) & 1u));
+    // More than 64 members (15 % of the sectors of the headline world, 80 % of the cluttered one: profiles/r17/NOTES.md): the members below the 20th largest of the lanes' best curvatures
+    // cannot be among the 20 picks (sel_rounds.hpp) and are left out of the ranking.
+    unsigned int top = members;
+    if (n_mem > 64) {
+        const unsigned int best = sel_lane_best<M>(members, kh);
+        int above = 0;
+        for (int t = 0; t < 64; t++) above += (unsigned int)__builtin_amdgcn_readlane((int)best, t) > best ? 1 : 0;
+        top = sel_keep_from<M>(members, kh, wave_min_u32_uniform(above < kSelSharpMax ? best : ~0u));
+    }
+    // the members to rank one per lane (ballot ranks, through 512 B of LDS)
+    int n_top = 0;
+#pragma unroll
+    for (int m = 0; m < M; m++) {
+        const bool is = (top >> m) & 1u;
+        const unsigned long long mk = __ballot(is);
+        const int pos = n_top + __popcll(mk & ((1ull << lane) - 1ull));
+        if (is && pos < 64) { scratch[2 * pos] = kh[m]; scratch[2 * pos + 1] = kl[m]; }
+        n_top += __popcll(mk);
+    }
+    const bool ranked = n_top <= 64;
+    if (ranked) {
+        __builtin_amdgcn_wave_barrier();           // one wave: its LDS operations execute in order; the barrier keeps the compiler from reordering them
+        unsigned int ch = 0u, cl = 0u;
+        if (lane < n_top) { ch = scratch[2 * lane]; cl = scratch[2 * lane + 1]; }
+        __builtin_amdgcn_wave_barrier();           // the next sector's writes stay behind these reads
+        // rank = members of a larger key; the 20 first are the picks, and only they leave marks
+        int rank = 0;
+        for (int t = 0; t < n_top; t++) {
+            const unsigned int th = (unsigned int)__builtin_amdgcn_readlane((int)ch, t), tl = (unsigned int)__builtin_amdgcn_readlane((int)cl, t);
+            rank += sel_key_above(th, tl, ch, cl) ? 1 : 0;
+        }
+        if (lane < n_top && rank < kSelSharpMax) {
+            const int pind = (int)(cl >> 8), lf = sel_lf(cl), lb = sel_lb(cl);
+            sel_sh[j * 20 + rank] = rbeg + pind; label[pind] = rank < 2 ? 2 : 1;
+#pragma unroll
+            for (int o = 0; o <= 2 * kSelReach; o++) picked[pind - lb + min(o, lf + lb)] = 1;      // (a short reach writes its last byte again)
+        }
+        largest = n_mem;
+        __builtin_amdgcn_wave_barrier();
+        // what the picks suppressed, for the flat picks: the picked bytes of the lane's elements
+#pragma unroll
+        for (int m = 0; m < M; m++) dead |= (unsigned int)(picked[sp + min(e0 + m, slen - 1)] != 0) << m;     // (behind the end: dead already)
+    }
+    // more than 64 left to rank (equal curvatures in more than 64 members, or members in fewer than 20 lanes): one pick after the other, the
+    // wave-wide arg-max of what is live.  The walk starts again from the `dead` of the load: what the rounds, the bound and the compaction
+    // found is not used (a rare path; nothing has been written to `picked`, the labels or `sel_sharp` yet).
+    while (!ranked) {
         const unsigned int live = big & ~dead;
         // the lane's own best: slots ascend in index, so ">=" keeps the larger index among equal curvatures (live curvatures are > 0.1: 0 = none)
         unsigned int bh = 0u, bl = 0u;
@@ -439,12 +486,7 @@ __device__ __forceinline__ void select_sector(int lane, int j, int sp, int slen,
         if (largest > 20) break;
         if (lane == 0) { sel_sh[j * 20 + largest - 1] = rbeg + pind; label[pind] = largest <= 2 ? 2 : 1; }
         if (lane <= lf + lb) picked[pind - lb + lane] = 1;
-        {
-            // the suppressed range [pind - lb, pind + lf] is shorter than 64, so it meets at most one slot of this lane
-            const int a = pind - lb - sp - lane;                 // slot m is hit iff a <= 64 m <= a + lb + lf
-            const int m0 = (a + 63) >> 6;
-            if (m0 >= 0 && m0 < M && 64 * m0 <= a + lb + lf) dead |= 1u << m0;
-        }
+        dead |= sel_hit_bits<M>(pind - lb - sp - e0, lb + lf);      // the lane's elements inside the suppressed range [pind - lb, pind + lf]
     }
     if (lane == 0) sel_sh_n[j] = largest > 20 ? 20 : largest;
     // ---- smallest curvature first: <= 4 flat
@@ -470,14 +512,18 @@ __device__ __forceinline__ void select_sector(int lane, int j, int sp, int slen,
         smallest++;
         if (smallest >= 4) break;
         if (lane <= lf + lb) picked[pind - lb + lane] = 1;
-        {
-            // the suppressed range [pind - lb, pind + lf] is shorter than 64, so it meets at most one slot of this lane
-            const int a = pind - lb - sp - lane;                 // slot m is hit iff a <= 64 m <= a + lb + lf
-            const int m0 = (a + 63) >> 6;
-            if (m0 >= 0 && m0 < M && 64 * m0 <= a + lb + lf) dead |= 1u << m0;
-        }
+        dead |= sel_hit_bits<M>(pind - lb - sp - e0, lb + lf);      // the lane's elements inside the suppressed range [pind - lb, pind + lf]
     }
     if (lane == 0) sel_fl_n[j] = smallest;
+}
+
+// The 11-element instantiation (rings of the second launch) as a function of its own: its registers and spills stay out of the code
+// of the 5- and 6-element sectors that every HDL-64 ring runs.
+__device__ __noinline__ void select_sector_wide(int lane, int j, int sp, int slen, int rbeg, const float *curv, unsigned char *picked,
+                                                signed char *label, const unsigned long long *gap, int *sel_sh, int *sel_sh_n, int *sel_fl, int *sel_fl_n,
+                                                unsigned int *scratch)
+{
+    select_sector<kSelMaxPerLane>(lane, j, sp, slen, rbeg, curv, picked, label, gap, sel_sh, sel_sh_n, sel_fl, sel_fl_n, scratch);
 }
 
 // wave-uniform values as scalars (the compiler cannot prove uniformity of what is loaded through a per-wave index)
@@ -543,7 +589,7 @@ __device__ __forceinline__ void select_ring(BatchView &b, int r, int s, int lane
         // HDL-64-sized sectors (<= 320 / <= 384 points) take the 5- / 6-slot instantiations, longer rings the full one
         if (slen <= 5 * 64) select_sector<5>(lane, j, sp, slen, rbeg, curv, picked, label, gap, sel_sh, sel_sh_n, sel_fl, sel_fl_n, scratch);
         else if (slen <= 6 * 64) select_sector<6>(lane, j, sp, slen, rbeg, curv, picked, label, gap, sel_sh, sel_sh_n, sel_fl, sel_fl_n, scratch);
-        else select_sector<kSelMaxPerLane>(lane, j, sp, slen, rbeg, curv, picked, label, gap, sel_sh, sel_sh_n, sel_fl, sel_fl_n, scratch);
+        else select_sector_wide(lane, j, sp, slen, rbeg, curv, picked, label, gap, sel_sh, sel_sh_n, sel_fl, sel_fl_n, scratch);
     }
 }
 

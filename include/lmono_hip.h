@@ -429,7 +429,9 @@ int lmono_map_builder_clear(lmono_ctx *, lmono_map_builder *);                  
  * rejected, voxels new in this call, voxels in the map afterwards.  An insert that needs more than max_voxels voxels returns
  * LMONO_ECAPACITY and leaves nothing of that call in the map; from then on the map is full: every insert returns LMONO_ECAPACITY
  * until lmono_voxel_map_clear (size / read / cells keep working), an insert of n == 0 points included: the full map wins.  At most
- * 2^30 points per call; on a map that is not full n == 0 is a successful no-op with no launch. */
+ * 2^30 points per call; on a map that is not full n == 0 is a successful no-op with no launch.  A map keeps this fixed size unless it
+ * is told to grow (lmono_voxel_map_set_growth) or is rebuilt (lmono_voxel_map_reserve, which also makes a full map usable again without
+ * losing its content); both are below. */
 typedef struct lmono_voxel_map lmono_voxel_map;
 lmono_voxel_map *lmono_voxel_map_create(lmono_ctx *, float leaf, int64_t max_voxels);
 void             lmono_voxel_map_destroy(lmono_voxel_map *);
@@ -461,6 +463,27 @@ int              lmono_voxel_map_tile(void);   /* points a workgroup of the inse
  * or only empty sources: a successful no-op with no launch, unless dst is full (LMONO_ECAPACITY: the full map wins). */
 int              lmono_voxel_map_compose(lmono_ctx *, lmono_voxel_map *dst, int n_src, lmono_voxel_map *const *srcs,
                                          const double *transforms /* [n_src][12] */, int64_t *stats /* optional [6] */);
+/* A live map changes size.  reserve rebuilds map s of n distinct maps for max_voxels[s] voxels -- more, fewer or as many
+ * as it has room for now, max(size, 1) <= max_voxels[s] <= 2^30 -- with its content unchanged, byte for byte: all new tables are
+ * allocated first, then one clear launch and one launch that moves the occupied records serve all n maps (an empty map needs no move),
+ * and the old tables are released only when every new one has been checked; ends synchronised.  While it runs the old and the new tables
+ * exist side by side: that sum is the call's high-water mark.  A map that was full is no longer: what refused calls left behind is
+ * dropped, so exactly max_voxels[s] voxels fit again; reserve with the current max_voxels is the way on after a refused insert without
+ * clear.  LMONO_EINVAL before any launch or allocation, no map changed: n <= 0, a NULL or foreign handle, a map named twice, a value
+ * below the map's size (or 1) or above 2^30.  LMONO_ENOMEM when a new table cannot be allocated, LMONO_ENODEV when a rebuilt table does
+ * not hold exactly the map's voxels (table inconsistent): no map changed either.
+ * set_growth: limit_voxels == 0 (the default) keeps the size fixed; otherwise max_voxels <= limit_voxels <= 2^30 (else LMONO_EINVAL),
+ * and insert, insert_d, insert_frames, insert_filtered and compose (its dst) grow the map instead of refusing: the maps of the refused
+ * streams are rebuilt for min(limit, 2 * max_voxels) as by reserve and the call is repeated for those streams only, until each fits or
+ * stands at its limit.  The content and the stats are those of a fixed map that was large enough, and the capacity afterwards is the
+ * smallest of max_voxels, min(limit, 2 max_voxels), min(limit, 4 max_voxels), ... that holds the voxels.  A stream that does not fit at
+ * the limit is refused as above (LMONO_ECAPACITY, nothing inserted, map full at the limit); if a new table cannot be allocated the call
+ * returns LMONO_ENOMEM with that map full, and a later reserve repairs it.  The limit bounds this automatic growth only: reserve may go
+ * above it, and the map then never grows by itself.
+ * capacity: out = max_voxels, slots of the table (64 B each), growth limit (0: fixed), tables replaced so far (by reserve or growth). */
+int              lmono_voxel_map_reserve(lmono_ctx *, int n, lmono_voxel_map *const *maps, const int64_t *max_voxels);
+int              lmono_voxel_map_set_growth(lmono_ctx *, lmono_voxel_map *, int64_t limit_voxels);
+int              lmono_voxel_map_capacity(lmono_ctx *, lmono_voxel_map *, int64_t out[4]);
 
 /* ---- statistical outlier removal in front of the voxel map ---------------------------------------------------
  * The pcl::StatisticalOutlierRemoval<pcl::PointXYZRGB> with setMeanK(100) / setStddevMulThresh(1.0) that MapBuilder::processMapping

@@ -1,4 +1,5 @@
 """ctypes binding of include/lmono_hip.h (the drop-in C ABI).  Fails loudly when the library is absent."""
+import collections
 import ctypes as C
 import os
 import weakref
@@ -665,19 +666,58 @@ class MapBuilder(_Handle):
         self.ctx.check(self.ctx.L.lmono_map_builder_clear(self.ctx.h, self.h))
 
 
+VoxelCapacity = collections.namedtuple("VoxelCapacity", "max_voxels slots grow_limit rehashes")
+
+
 class VoxelMap(_Handle):
     """The voxel-grid global colour map on the device (lmono_voxel_map_*): clouds of POINT_RGB folded in frame by frame,
     bounded by the number of occupied voxels, the same bytes for every insertion order.  insert* return the call's stats
-    [points inserted, points rejected, voxels new, voxels afterwards]; an LmonoError carries the C return value in .code."""
+    [points inserted, points rejected, voxels new, voxels afterwards]; an LmonoError carries the C return value in .code.
+    The size is fixed at max_voxels unless grow_limit (> 0) lets refused inserts double it up to that limit; reserve / shrink_to_fit
+    rebuild the table for another size with the content unchanged, and make a full map usable again."""
 
     _destroy = "lmono_voxel_map_destroy"
 
-    def __init__(self, ctx, leaf=0.1, max_voxels=1 << 22):
+    def __init__(self, ctx, leaf=0.1, max_voxels=1 << 22, grow_limit=0):
         super().__init__(ctx)
         self.leaf = float(np.float32(leaf))
-        self.max_voxels = int(max_voxels)
         self.TILE = int(ctx.L.lmono_voxel_map_tile())       # points a workgroup of the insert sums on chip
         self._create("lmono_voxel_map_create", C.c_float(leaf), int(max_voxels))
+        if grow_limit:
+            self.set_growth(grow_limit)
+
+    @property
+    def capacity(self):
+        """max_voxels, slots (64 B each), grow_limit (0: fixed size), rehashes (tables replaced so far)."""
+        out = np.zeros(4, np.int64)
+        self.ctx.check(self.ctx.L.lmono_voxel_map_capacity(self.ctx.h, self.h, out.ctypes.data))
+        return VoxelCapacity(*(int(v) for v in out))
+
+    @property
+    def max_voxels(self):
+        return self.capacity.max_voxels
+
+    def set_growth(self, limit):
+        """limit 0: fixed size; else refused inserts and composes rebuild the map for min(limit, 2 * max_voxels) and go in again."""
+        self.ctx.check(self.ctx.L.lmono_voxel_map_set_growth(self.ctx.h, self.h, int(limit)))
+
+    def reserve(self, max_voxels):
+        """Rebuild the table for max_voxels (>= size) voxels, content unchanged; a full map is usable again."""
+        VoxelMap.reserve_batch([self], [max_voxels])
+
+    @staticmethod
+    def reserve_batch(maps, max_voxels):
+        """reserve for several maps: one clear launch and one rehash launch in all."""
+        n = len(maps)
+        if n == 0 or len(max_voxels) != n:
+            raise LmonoError("one max_voxels per map")
+        ctx = maps[0].ctx
+        mh = (C.c_void_p * n)(*[m.h for m in maps])
+        mv = np.array([int(v) for v in max_voxels], np.int64)
+        ctx.check(ctx.L.lmono_voxel_map_reserve(ctx.h, n, mh, mv.ctypes.data))
+
+    def shrink_to_fit(self):
+        self.reserve(max(self.size, 1))
 
     def insert(self, points, bgra=None):
         """points: a POINT_RGB array, or xyz [n][3] float32 with bgra [n] uint32."""
@@ -793,15 +833,20 @@ def pose_delta(inserted_tq, corrected_tq):
 class SubmapAtlas:
     """A sequence as submaps, so that the global map can follow a corrected trajectory: every `frames_per_submap` frames go
     into a voxel map of their own (leaf_sub), anchored at the pose of its first frame.  compose(dst, corrected poses) moves every submap
-    rigidly by pose_delta(anchor pose, corrected anchor pose) and folds them into dst in one lmono_voxel_map_compose call."""
+    rigidly by pose_delta(anchor pose, corrected anchor pose) and folds them into dst in one lmono_voxel_map_compose call.
+    With grow_limit_sub the submaps start at max_voxels_sub and grow up to that limit; with compact_closed a submap is shrunk to what it holds
+    when the next one is opened (the last one at compose), so a closed submap's table is as small as its content allows."""
 
-    def __init__(self, ctx, frames_per_submap, leaf_sub=0.05, max_voxels_sub=1 << 20):
+    def __init__(self, ctx, frames_per_submap, leaf_sub=0.05, max_voxels_sub=1 << 20, grow_limit_sub=0, compact_closed=False):
         if int(frames_per_submap) < 1:
             raise LmonoError("frames_per_submap must be >= 1")
         self.ctx = ctx
         self.frames_per_submap = int(frames_per_submap)
         self.leaf_sub = float(leaf_sub)
         self.max_voxels_sub = int(max_voxels_sub)
+        self.grow_limit_sub = int(grow_limit_sub)
+        self.compact_closed = bool(compact_closed)
+        self._compacted = 0                                  # submaps[:_compacted] have been shrunk to fit
         self.submaps = []
         self.anchor_frames = []
         self.anchor_poses = []
@@ -817,7 +862,8 @@ class SubmapAtlas:
         OutlierFilter, or a POINT_RGB array.  Returns the insert's stats."""
         pose = np.asarray(pose_tq, np.float64).reshape(7)
         if self.n_frames % self.frames_per_submap == 0:
-            self.submaps.append(VoxelMap(self.ctx, leaf=self.leaf_sub, max_voxels=self.max_voxels_sub))
+            self._compact()
+            self.submaps.append(VoxelMap(self.ctx, leaf=self.leaf_sub, max_voxels=self.max_voxels_sub, grow_limit=self.grow_limit_sub))
             self.anchor_frames.append(self.n_frames)
             self.anchor_poses.append(pose.copy())
         sub = self.submaps[-1]
@@ -828,6 +874,13 @@ class SubmapAtlas:
             return VoxelMap.insert_filtered([sub], [source])[0]
         return sub.insert(source)
 
+    def _compact(self):
+        """Shrink the submaps not yet shrunk (all are closed when this is called) to what they hold: one batched reserve."""
+        todo = self.submaps[self._compacted:] if self.compact_closed else []
+        if todo:
+            VoxelMap.reserve_batch(todo, [max(m.size, 1) for m in todo])
+            self._compacted = len(self.submaps)
+
     def compose(self, dst, corrected_poses_tq, stats=False):
         """corrected_poses_tq: one pose per anchor, or one per frame (the anchors' are taken).  dst: a VoxelMap, usually fresh."""
         P = np.asarray(corrected_poses_tq, np.float64).reshape(-1, 7)
@@ -836,12 +889,14 @@ class SubmapAtlas:
         if len(P) != len(self.submaps):
             raise LmonoError("corrected poses: one per anchor (%d) or one per frame (%d)" % (len(self.submaps), self.n_frames))
         T = np.array([pose_delta(a, p) for a, p in zip(self.anchor_poses, P)], np.float64).reshape(-1, 12)
+        self._compact()
         return dst.compose(self.submaps, T, stats=stats)
 
     def close(self):
         for s in self.submaps:
             s.close()
         self.submaps = []
+        self._compacted = 0
 
     def __del__(self):
         try:

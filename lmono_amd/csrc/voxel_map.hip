@@ -16,6 +16,7 @@
 // 3.3 for 64 first frames, profiles/r11.)  Once the failure word is set, or the counter has reached max_voxels, no further slot is claimed, and every
 // probe loop ends after `slots` steps: no wave waits on the table, whatever is in it.
 // Sums are integers, so the content is the same bytes for every insertion order, split, batch and launch geometry.
+// A live table changes size by k_vm_clear_jobs / k_vm_rehash below: fresh tables for any number of maps, the occupied records moved into them.
 // Whole maps are folded into another one, each under a rigid transform and every voxel with its weight, by k_vm_move_find / k_vm_move_accum below
 // (DESIGN.md 6c-4): the same claim, ticket and refusal rules, 64-bit entries.
 #pragma once
@@ -29,6 +30,8 @@ constexpr int kVmT = 256;                 // threads of every kernel here
 constexpr int kVmTile = 512;              // points per workgroup of k_vm_find
 constexpr int kVmLds = 2 * kVmTile;      // slots of the workgroup's LDS table (load <= 1/2)
 constexpr unsigned kVmNoSlot = 0xffffffffu;
+constexpr int kVmRehashU = 4;              // records a group of eight lanes of k_vm_rehash has in flight
+static_assert(kVmTile * 8 / kVmT % kVmRehashU == 0, "k_vm_rehash unroll");
 
 struct VmEnt { unsigned slot, w[7]; };    // sums of one distinct key of a tile (or of one point), on their way to record `slot`
 
@@ -169,6 +172,85 @@ __global__ __launch_bounds__(kVmT) void k_vm_clear(VmRec *rec, unsigned long lon
     const unsigned long long i = (unsigned long long)blockIdx.x * kVmT + threadIdx.x;
     if (i >= slots * 8) return;
     ((uint64_t *)rec)[i] = (i & 7) == 0 ? kVmEmpty : 0ull;
+}
+
+// ---- a live table changes size: fresh tables cleared, then the old tables' records moved into them; blockIdx.y = map ----
+// A table is slots records and one more 64-B row behind them that holds the map's counters (lmono_voxel_map::ctl), so a table and its occupancy
+// counter are replaced together and the old pair stands untouched until the new one has been checked.
+struct VmGrowJob {
+    const VmRec *src;                      // the old table; src_slots == 0: nothing to move (an empty map)
+    unsigned long long src_slots;
+    VmRec *dst;                            // the fresh table: dst_slots records + the counter row
+    unsigned long long dst_slots;
+    int *res;                              // [0] failure word, [1] records moved
+};
+
+__global__ __launch_bounds__(kVmT) void k_vm_clear_jobs(const VmGrowJob *jobs)
+{
+    const VmGrowJob &j = jobs[blockIdx.y];
+    const unsigned long long i = (unsigned long long)blockIdx.x * kVmT + threadIdx.x;
+    if (i >= (j.dst_slots + 1) * 8) return;
+    ((uint64_t *)j.dst)[i] = (i & 7) == 0 && i < j.dst_slots * 8 ? kVmEmpty : 0ull;     // the counter row is all zero
+}
+
+// Eight lanes per record, lane w word w, on both sides: the old table is read once in whole 64-B rows, a record with a key and count > 0 is
+// moved (count 0: the ghost claim of a refused call, dropped).  Lane 0 of the group claims the slot -- keys of one table are distinct, so no
+// other mover looks for this key and a compare-and-swap on an empty key is the whole probe -- and the seven words go in as plain stores: the table
+// was cleared and nobody else touches that record.  The probe ends after dst_slots steps with the failure word set; it cannot legitimately run out.
+__global__ __launch_bounds__(kVmT) void k_vm_rehash(const VmGrowJob *jobs)
+{
+    const VmGrowJob &j = jobs[blockIdx.y];
+    const unsigned long long base = (unsigned long long)blockIdx.x * kVmTile;
+    if (base >= j.src_slots) return;
+    __shared__ unsigned l_moved;
+    if (threadIdx.x == 0) l_moved = 0;
+    __syncthreads();
+    const int w = threadIdx.x & 7, lead = threadIdx.x & 63 & ~7;         // lead: lane 0 of this group of eight
+    const unsigned mask = (unsigned)(j.dst_slots - 1);
+    unsigned moved = 0;
+    // kVmRehashU records per group at a time: their loads are issued together, then their first compare-and-swaps, so a workgroup has
+    // kVmRehashU times the bytes in flight of one record at a time (measured: profiles/r18)
+    for (int r0 = 0; r0 < kVmTile * 8 / kVmT; r0 += kVmRehashU) {
+        unsigned long long v[kVmRehashU], key[kVmRehashU], got[kVmRehashU];
+        unsigned h[kVmRehashU];
+        bool mover[kVmRehashU];
+#pragma unroll
+        for (int u = 0; u < kVmRehashU; u++) {
+            const unsigned long long rec = base + (unsigned long long)((r0 + u) * (kVmT / 8)) + (threadIdx.x >> 3);
+            v[u] = rec < j.src_slots ? ((const uint64_t *)j.src)[rec * 8 + w] : (w == 0 ? kVmEmpty : 0ull);
+        }
+#pragma unroll
+        for (int u = 0; u < kVmRehashU; u++) {
+            key[u] = __shfl(v[u], lead);
+            const unsigned long long count = __shfl(v[u], lead + 1);
+            mover[u] = w == 0 && key[u] != kVmEmpty && count != 0;
+            h[u] = (unsigned)vm_mix(key[u]) & mask;
+            got[u] = 0;
+        }
+#pragma unroll
+        for (int u = 0; u < kVmRehashU; u++)
+            if (mover[u]) got[u] = atomicCAS((unsigned long long *)&j.dst[h[u]].key, (unsigned long long)kVmEmpty, key[u]);
+#pragma unroll
+        for (int u = 0; u < kVmRehashU; u++) {
+            unsigned slot = kVmNoSlot;
+            if (mover[u]) {
+                if (got[u] == kVmEmpty) slot = h[u];
+                else                                                        // the first slot was taken: the other dst_slots - 1, one by one
+                    for (unsigned probe = 0, at = (h[u] + 1) & mask; probe < mask; probe++, at = (at + 1) & mask)
+                        if (atomicCAS((unsigned long long *)&j.dst[at].key, (unsigned long long)kVmEmpty, key[u]) == kVmEmpty) { slot = at; break; }
+                if (slot == kVmNoSlot) atomicExch(j.res, 1);
+                else moved++;
+            }
+            slot = __shfl(slot, lead);
+            if (slot != kVmNoSlot && w != 0) j.dst[slot].w[w - 1] = v[u];
+        }
+    }
+    if (moved) atomicAdd(&l_moved, moved);
+    __syncthreads();
+    if (threadIdx.x == 0 && l_moved) {
+        atomicAdd((unsigned *)(j.dst + j.dst_slots), l_moved);      // the new table's occupancy counter
+        atomicAdd(j.res + 1, (int)l_moved);
+    }
 }
 
 // records with count > 0, in no order, into out[cap]; n counts them all

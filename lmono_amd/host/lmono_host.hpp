@@ -415,7 +415,8 @@ public:
     std::vector<lmono_point_rgb> rgbMap();                   // rgb_map
     // The pcl::VoxelGrid the reference carries commented out in processMapping (Map_Builder.cc:82-98), as this project defines it (DESIGN.md
     // 6c-2): once set, processMapping() also folds the queued frame into a device-resident voxel map, before the every-tenth-frame clear.
-    void setVoxelMap(float leaf, int64_t max_voxels);
+    // With a grow_limit the map starts at max_voxels and grows on the device up to that limit instead of refusing a frame (0: fixed size).
+    void setVoxelMap(float leaf, int64_t max_voxels, int64_t grow_limit = 0);
     std::vector<lmono_point_rgb> voxelMap();                 // one point per voxel, ascending key order (empty when not set)
     // The pcl::StatisticalOutlierRemoval the reference carries commented out in front of that grid (Map_Builder.cc:24-29), as this project
     // defines it: once set, the queued frame goes through the filter on the device and the voxel map takes the kept points.
@@ -423,7 +424,10 @@ public:
     // Submaps, so that the map can follow a corrected trajectory (the reference's own map-to-map attempt is commented out,
     // Map_Builder.cc:110-210).  After setVoxelMap: processMapping() folds the queued frame (through the outlier filter when one is set) into
     // the current submap too -- a voxel map of leaf_sub that takes frames_per_submap frames and is anchored at the pose of its first one.
-    void setSubmaps(int frames_per_submap, float leaf_sub = 0.05f, int64_t max_voxels_sub = (int64_t)1 << 20);
+    // With grow_limit_sub the submaps grow like the map above; with compact_closed a submap is shrunk to what it holds when the next one is
+    // opened (the last one in composeMap).
+    void setSubmaps(int frames_per_submap, float leaf_sub = 0.05f, int64_t max_voxels_sub = (int64_t)1 << 20, int64_t grow_limit_sub = 0,
+                    bool compact_closed = false);
     // corrected poses, one per frame folded so far (x y z, qx qy qz qw; e.g. PoseGraph::optimize4DoF's output): every submap moved rigidly by
     // T_corrected * T_inserted^-1 of its anchor frame and composed into a fresh map at the setVoxelMap leaf.  One point per voxel, ascending key order.
     std::vector<lmono_point_rgb> composeMap(const std::vector<std::array<double, 7>> &corrected_tq);
@@ -442,14 +446,18 @@ private:
     struct Submaps {
         int per = 0, frames = 0;                                  // frames per submap (0: not set), frames folded
         float leaf = 0.0f;
-        int64_t max_voxels = 0;
+        int64_t max_voxels = 0, grow_limit = 0;
+        bool compact_closed = false;
+        size_t compacted = 0;                                     // maps[0 .. compacted) have been shrunk to fit
         std::vector<std::shared_ptr<lmono_voxel_map>> maps;
         std::vector<int> anchor_frame;
         std::vector<std::array<double, 7>> anchor_tq;
     } sub_;
     lmono_voxel_map *submapForFrame();                           // the submap the queued frame belongs to (opened when it is the first); null when not set
+    std::shared_ptr<lmono_voxel_map> newVoxelMap(float leaf, int64_t max_voxels, int64_t grow_limit);
+    void compactSubmaps();
     float vm_leaf_ = 0.0f;
-    int64_t vm_max_ = 0;
+    int64_t vm_max_ = 0, vm_grow_ = 0;
     double last_tq_[7] = { 0, 0, 0, 0, 0, 0, 1 };
     lmono_camera cam_;
     bool save_map_, pending_ = false;

@@ -4,9 +4,10 @@
 // -> MapBuilder::associateToMap -> processMapping; writes <out>/rgb_map<index>.ply every 10 frames and the timing log
 // <out>/mapping_recorder.txt, and dumps the products of the last frame (<out>/depth_last.u8, <out>/cloud_cam_last.bin,
 // <out>/cloud_world_last.bin) for inspection.
-//   map_build <sequence_dir> <trajectory.txt> <out_dir> [n_frames] [width height fx fy cx cy] [submap=N:CORRECTED_TRAJECTORY[:LEAF_SUB]] [sor=K:MULT[:CELL:RINGS]] [voxel=LEAF[:MAX_VOXELS]]
+//   map_build <sequence_dir> <trajectory.txt> <out_dir> [n_frames] [width height fx fy cx cy] [submap=N:CORRECTED_TRAJECTORY[:LEAF_SUB]] [sor=K:MULT[:CELL:RINGS]] [voxel=LEAF[:MAX_VOXELS[:GROW_LIMIT]]]
 // With the trailing voxel= argument every frame is also folded into a voxel-grid map, written at the end as
-// <out>/rgb_map_voxel.ply; without it nothing changes.  With sor= in front of it every frame passes the statistical outlier removal
+// <out>/rgb_map_voxel.ply; without it nothing changes.  With a GROW_LIMIT the map starts at MAX_VOXELS and grows on the device up to that limit, and so
+// do the composed map and the submaps (each from MAX_VOXELS), whose tables are shrunk to their content once closed.  With sor= in front of it every frame passes the statistical outlier removal
 // (CELL 0.1 and RINGS 8 unless given) on its way into that map.  With submap= in front of those every N frames also go into a
 // submap of their own (LEAF_SUB 0.05 unless given), and at the end the submaps are composed under the poses of CORRECTED_TRAJECTORY (same format,
 // one line per frame: a loop-closed trajectory) into <out>/rgb_map_global.ply at the voxel= leaf.
@@ -41,12 +42,15 @@ template <typename T> static bool dump(const std::string &path, const std::vecto
 int main(int argc, char **argv)
 {
     float voxel_leaf = 0.0f;
-    long long voxel_max = 1 << 22;
+    long long voxel_max = 1 << 22, voxel_grow = 0;
     if (argc > 4 && std::strncmp(argv[argc - 1], "voxel=", 6) == 0) {
         char *end = nullptr;
         voxel_leaf = std::strtof(argv[argc - 1] + 6, &end);
-        if (end && *end == ':') voxel_max = std::atoll(end + 1);
-        if (!(voxel_leaf > 0.0f)) { std::fprintf(stderr, "map_build: voxel=LEAF[:MAX_VOXELS] needs a leaf > 0\n"); return 2; }
+        if (end && *end == ':') {
+            voxel_max = std::strtoll(end + 1, &end, 10);
+            if (end && *end == ':') voxel_grow = std::atoll(end + 1);
+        }
+        if (!(voxel_leaf > 0.0f)) { std::fprintf(stderr, "map_build: voxel=LEAF[:MAX_VOXELS[:GROW_LIMIT]] needs a leaf > 0\n"); return 2; }
         argc--;
     }
     int sor_k = 0, sor_rings = 8;
@@ -76,7 +80,7 @@ int main(int argc, char **argv)
         }
         argc--;
     }
-    if (argc < 4) { std::fprintf(stderr, "usage: map_build <sequence_dir> <trajectory.txt> <out_dir> [n_frames] [width height fx fy cx cy] [submap=N:CORRECTED_TRAJECTORY[:LEAF_SUB]] [sor=K:MULT[:CELL:RINGS]] [voxel=LEAF[:MAX_VOXELS]]\n"); return 2; }
+    if (argc < 4) { std::fprintf(stderr, "usage: map_build <sequence_dir> <trajectory.txt> <out_dir> [n_frames] [width height fx fy cx cy] [submap=N:CORRECTED_TRAJECTORY[:LEAF_SUB]] [sor=K:MULT[:CELL:RINGS]] [voxel=LEAF[:MAX_VOXELS[:GROW_LIMIT]]]\n"); return 2; }
     const std::string seq = argv[1], traj = argv[2], out = argv[3];
     int n_frames = argc > 4 ? std::atoi(argv[4]) : -1;
     lmono_camera cam = { 1241, 376, 718.856, 718.856, 607.1928, 185.2157, 0, 0, 0, 0, 5, 0, 0 };   // kitti00_cam.yaml, kitti_map_config_00.yaml
@@ -104,9 +108,10 @@ int main(int argc, char **argv)
     try {
         HipContext hip(0);
         MapBuilder map_builder(hip, cam, true, out);
-        if (voxel_leaf > 0.0f) map_builder.setVoxelMap(voxel_leaf, voxel_max);
+        if (voxel_leaf > 0.0f) map_builder.setVoxelMap(voxel_leaf, voxel_max, voxel_grow);
         if (sor_k > 0) map_builder.setOutlierFilter(sor_k, sor_mul, sor_cell, sor_rings);
-        if (sub_n > 0) map_builder.setSubmaps(sub_n, sub_leaf);
+        if (sub_n > 0 && voxel_grow > 0) map_builder.setSubmaps(sub_n, sub_leaf, voxel_max, voxel_grow, /*compact_closed=*/true);
+        else if (sub_n > 0) map_builder.setSubmaps(sub_n, sub_leaf);
         MappingLog recorder(out + "/mapping_recorder.txt");
         if (!recorder.ok()) { std::fprintf(stderr, "cannot write into %s\n", out.c_str()); return 1; }
         std::vector<uint8_t> image;

@@ -7,12 +7,20 @@
 
 namespace lmono_host {
 
-void MapBuilder::setVoxelMap(float leaf, int64_t max_voxels)
+// a voxel map of max_voxels that grows up to grow_limit (0: fixed size)
+std::shared_ptr<lmono_voxel_map> MapBuilder::newVoxelMap(float leaf, int64_t max_voxels, int64_t grow_limit)
 {
     lmono_voxel_map *vm = lmono_voxel_map_create(hip_.get(), leaf, max_voxels);
     if (!vm) throw std::runtime_error(std::string("lmono_voxel_map_create: ") + lmono_last_error(hip_.get()));
-    vm_ = std::shared_ptr<lmono_voxel_map>(vm, lmono_voxel_map_destroy);
-    vm_leaf_ = leaf; vm_max_ = max_voxels;
+    std::shared_ptr<lmono_voxel_map> p(vm, lmono_voxel_map_destroy);
+    if (grow_limit) hip_.check(lmono_voxel_map_set_growth(hip_.get(), vm, grow_limit), "lmono_voxel_map_set_growth");
+    return p;
+}
+
+void MapBuilder::setVoxelMap(float leaf, int64_t max_voxels, int64_t grow_limit)
+{
+    vm_ = newVoxelMap(leaf, max_voxels, grow_limit);
+    vm_leaf_ = leaf; vm_max_ = max_voxels; vm_grow_ = grow_limit;
     fold_ = [this] {
         lmono_voxel_map *m = vm_.get();
         lmono_voxel_map *sub = submapForFrame();                           // the same frame into its submap
@@ -27,21 +35,37 @@ void MapBuilder::setVoxelMap(float leaf, int64_t max_voxels)
     };
 }
 
-void MapBuilder::setSubmaps(int frames_per_submap, float leaf_sub, int64_t max_voxels_sub)
+void MapBuilder::setSubmaps(int frames_per_submap, float leaf_sub, int64_t max_voxels_sub, int64_t grow_limit_sub, bool compact_closed)
 {
     if (!vm_) throw std::runtime_error("MapBuilder::setSubmaps: setVoxelMap first (composeMap writes at its leaf)");
     if (frames_per_submap < 1 || !(leaf_sub > 0.0f) || max_voxels_sub < 1) throw std::runtime_error("MapBuilder::setSubmaps: frames_per_submap >= 1, leaf_sub > 0, max_voxels_sub >= 1");
     sub_ = Submaps();
     sub_.per = frames_per_submap; sub_.leaf = leaf_sub; sub_.max_voxels = max_voxels_sub;
+    sub_.grow_limit = grow_limit_sub; sub_.compact_closed = compact_closed;
+}
+
+// shrink the submaps not yet shrunk (all closed when this is called) to what they hold: one batched reserve
+void MapBuilder::compactSubmaps()
+{
+    if (!sub_.compact_closed || sub_.compacted == sub_.maps.size()) return;
+    std::vector<lmono_voxel_map *> maps;
+    std::vector<int64_t> sizes;
+    for (size_t s = sub_.compacted; s < sub_.maps.size(); s++) {
+        const int64_t n = lmono_voxel_map_size(hip_.get(), sub_.maps[s].get());
+        hip_.check(n < 0 ? (int)n : 0, "lmono_voxel_map_size");
+        maps.push_back(sub_.maps[s].get());
+        sizes.push_back(n > 1 ? n : 1);
+    }
+    hip_.check(lmono_voxel_map_reserve(hip_.get(), (int)maps.size(), maps.data(), sizes.data()), "lmono_voxel_map_reserve");
+    sub_.compacted = sub_.maps.size();
 }
 
 lmono_voxel_map *MapBuilder::submapForFrame()
 {
     if (sub_.per == 0) return nullptr;
     if (sub_.frames % sub_.per == 0) {
-        lmono_voxel_map *m = lmono_voxel_map_create(hip_.get(), sub_.leaf, sub_.max_voxels);
-        if (!m) throw std::runtime_error(std::string("lmono_voxel_map_create: ") + lmono_last_error(hip_.get()));
-        sub_.maps.push_back(std::shared_ptr<lmono_voxel_map>(m, lmono_voxel_map_destroy));
+        compactSubmaps();
+        sub_.maps.push_back(newVoxelMap(sub_.leaf, sub_.max_voxels, sub_.grow_limit));
         sub_.anchor_frame.push_back(sub_.frames);
         std::array<double, 7> a;
         for (int k = 0; k < 7; k++) a[(size_t)k] = last_tq_[k];
@@ -85,9 +109,9 @@ std::vector<lmono_point_rgb> MapBuilder::composeMap(const std::vector<std::array
         srcs[s] = sub_.maps[s].get();
         poseDelta(sub_.anchor_tq[s].data(), corrected_tq[(size_t)sub_.anchor_frame[s]].data(), &T[12 * s]);
     }
-    lmono_voxel_map *g = lmono_voxel_map_create(hip_.get(), vm_leaf_, vm_max_);
-    if (!g) throw std::runtime_error(std::string("lmono_voxel_map_create: ") + lmono_last_error(hip_.get()));
-    const std::shared_ptr<lmono_voxel_map> global(g, lmono_voxel_map_destroy);
+    compactSubmaps();
+    const std::shared_ptr<lmono_voxel_map> global = newVoxelMap(vm_leaf_, vm_max_, vm_grow_);
+    lmono_voxel_map *g = global.get();
     hip_.check(lmono_voxel_map_compose(hip_.get(), g, (int)n, srcs.data(), T.data(), nullptr), "lmono_voxel_map_compose");
     const int64_t m = lmono_voxel_map_read(hip_.get(), g, nullptr, 0);
     hip_.check(m < 0 ? (int)m : 0, "lmono_voxel_map_read");

@@ -4,9 +4,11 @@ rigid correction into a cleared 0.1 m map in ONE call, against the route the par
 to the host and insert() its points (which also loses the weights: every voxel counts as one point).  Whole calls timed on the host, median
 of --calls after --warmup.  Also reports the distinct-key ratio: voxels new in the cleared destination / source voxels moved -- the share of
 entries a workgroup table could NOT have merged even if it saw the whole call at once (an upper bound on the merging per 512-record tile).
+With --compact every submap is shrunk to what it holds (shrink_to_fit) before the composes, as SubmapAtlas(compact_closed=True) leaves closed
+submaps: the compose then scans tables of that size.  "submap_table_bytes" is the device memory of the submaps' tables either way.
 Prints one JSON line.  One process; run it under `timeout`.
 
-  timeout 600 python scripts/voxel_compose_bench.py [--submaps 1,16,64] [--calls 5] [--warmup 1]"""
+  timeout 600 python scripts/voxel_compose_bench.py [--submaps 1,16,64] [--calls 5] [--warmup 1] [--compact]"""
 import argparse
 import json
 import os
@@ -24,6 +26,7 @@ def main():
     ap.add_argument("--submaps", default="1,16,64")
     ap.add_argument("--calls", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--compact", action="store_true")
     a = ap.parse_args()
     import lmono_amd
     from tests import colour_cases as CC
@@ -33,7 +36,7 @@ def main():
     M = CC.lidar_to_camera()
     cloud = CC.s1_scan(); image = CC.noise_image(h, w)
     mb = lmono_amd.MapBuilder(ctx, cam, max_cloud_points=len(cloud), map_capacity_points=w * h)
-    out = {"image": [w, h], "leaf_sub": 0.05, "leaf": 0.1, "runs": []}
+    out = {"image": [w, h], "leaf_sub": 0.05, "leaf": 0.1, "compact": a.compact, "runs": []}
     for n in [int(v) for v in a.submaps.split(",")]:
         subs, T = [], []
         for s in range(n):
@@ -47,6 +50,8 @@ def main():
             inserted = np.concatenate([t, q])
             corrected = np.concatenate([t + np.array([0.05 * s, -0.02 * s, 0.0]), q])
             T.append(lmono_amd.pose_delta(inserted, corrected))
+        if a.compact:
+            lmono_amd.VoxelMap.reserve_batch(subs, [max(sub.size, 1) for sub in subs])
         dst = lmono_amd.VoxelMap(ctx, leaf=0.1, max_voxels=1 << 22)
         compose, route, st = [], [], None
         for c in range(a.warmup + a.calls):
@@ -65,7 +70,8 @@ def main():
             t1 = time.perf_counter()
             if c >= a.warmup:
                 route.append((t1 - t0) * 1e3)
-        run = {"submaps": n, "source_voxels": int(st[0] + st[1]), "points": int(st[2] + st[3]), "voxels_composed": int(composed_voxels), "voxels_read_insert_untransformed": int(dst.size),
+        run = {"submaps": n, "submap_table_bytes": 64 * sum(sub.capacity.slots for sub in subs),
+               "source_voxels": int(st[0] + st[1]), "points": int(st[2] + st[3]), "voxels_composed": int(composed_voxels), "voxels_read_insert_untransformed": int(dst.size),
                "distinct_key_ratio": float(st[4]) / max(float(st[0]), 1.0),
                "compose": {"ms_per_call_median": float(np.median(compose)), "ms_per_call_min": float(np.min(compose))},
                "read_insert": {"ms_per_call_median": float(np.median(route)), "ms_per_call_min": float(np.min(route))}}

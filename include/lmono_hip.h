@@ -518,6 +518,55 @@ int        lmono_sor_diag(lmono_ctx *, lmono_sor *, int64_t out[2]);
  * capacity rules of lmono_voxel_map_insert_frames, unchanged (stats [4] per map as there). */
 int        lmono_voxel_map_insert_filtered(lmono_ctx *, int n, lmono_voxel_map *const *maps, lmono_sor *const *sors, int64_t *stats);
 
+/* ---- map builder: point-to-point ICP against a target cloud ------------------------------------------------
+ * The pcl::IterativeClosestPoint with setMaxCorrespondenceDistance(0.5) / setMaximumIterations(50) / setTransformationEpsilon(1e-8) /
+ * setEuclideanFitnessEpsilon(1) that MapBuilder::processMapping carries commented out between its outlier removal and its voxel grid
+ * (mono_lidar_mapping/src/map_builder/Map_Builder.cc:31-59), as a device-resident stage between the outlier filter and the voxel map.
+ * A definition of this project (lmono_amd/csrc/icp.hpp): every source point is paired with its nearest target point (ties by x, y, z)
+ * if that lies within max_corr; the pairs enter a closed-form rigid fit (Horn) through exact integer sums in 2^-16 m fixed point about
+ * the middle of the target's bounding box, so the result is a pure function of the SET of target points and of the source points: the
+ * same bytes for every point order, grid tuning (cell, max_rings), batch and launch schedule.  Parity with PCL is unpinned.
+ * eps: the run ends with status 0 when both the squared change of the translation and of the rotation matrix fall below it;
+ * mse_eps (0: off): status 2 when the mean squared distance changes by less between two iterations; status 1: max_iter reached;
+ * status 3: fewer than 3 pairs (the state is kept).  cell and max_rings tune the search grid and need (max_rings - 0.25) cell >= max_corr.
+ * stats [8] per stream: source points, source points not usable (non-finite or 2048 m or more from the origin on an axis), target
+ * points, target points rejected, iterations run, status, pairs and E = sum of squared distances in units of 2^-24 m^2 of the last
+ * iteration.  n > max returns LMONO_ECAPACITY before any launch; n == 0 is a successful empty result with no launch; an align before
+ * any set_target returns LMONO_EINVAL.  Every align replaces the aligner's last result. */
+typedef struct lmono_icp lmono_icp;
+lmono_icp *lmono_icp_create(lmono_ctx *, int64_t max_source_points, int64_t max_target_points, float max_corr, int max_iter, double eps, double mse_eps,
+                            float cell, int max_rings);
+void       lmono_icp_destroy(lmono_icp *);
+/* the default cell for max_corr at max_rings = 2: the smallest float32 h >= max_corr / 1.75f with (2 - 0.25) h >= max_corr in float32 */
+float      lmono_icp_default_cell(float max_corr);
+/* the initial guess, row-major 3 x 4 (NULL: identity), applied to every source point before the first iteration and composed into the result */
+int        lmono_icp_set_guess(lmono_ctx *, lmono_icp *, const double g[12]);
+/* pairs of step and solve launches between two reads of the streams' done words (default 2); the result does not depend on it */
+int        lmono_icp_set_poll_interval(lmono_ctx *, lmono_icp *, int pairs);
+/* the target: built once, it serves every align until the next set_target*.  _map: one point per occupied voxel, what lmono_voxel_map_read
+ * gives, without a host copy (frame-to-map).  _aligned: the aligned cloud of the last align (frame-to-frame, the reference's "last cloud"). */
+int        lmono_icp_set_target(lmono_ctx *, lmono_icp *, const lmono_point_rgb *pts_h, int64_t n);
+int        lmono_icp_set_target_d(lmono_ctx *, lmono_icp *, const lmono_point_rgb *pts_d, int64_t n);
+int        lmono_icp_set_target_map(lmono_ctx *, lmono_icp *, lmono_voxel_map *);
+int        lmono_icp_set_target_aligned(lmono_ctx *, lmono_icp *);
+int        lmono_icp_align(lmono_ctx *, lmono_icp *, const lmono_point_rgb *pts_h, int64_t n, int64_t *stats);
+int        lmono_icp_align_d(lmono_ctx *, lmono_icp *, const lmono_point_rgb *pts_d, int64_t n, int64_t *stats);
+/* n distinct aligners each take the world-frame cloud of the last frame of one of n distinct builders, or the last output of one of n
+ * distinct outlier filters, straight from device memory; one launch per phase for all streams.  A stream's bytes do not depend on the
+ * batch it travels in. */
+int        lmono_icp_align_frames(lmono_ctx *, int n, lmono_icp *const *icps, lmono_map_builder *const *mbs, int64_t *stats);
+int        lmono_icp_align_filtered(lmono_ctx *, int n, lmono_icp *const *icps, lmono_sor *const *sors, int64_t *stats);
+/* the last align: its transform (row-major 3 x 4, what lmono_voxel_map_compose takes: guess included), every input point in input order
+ * moved by it (payload untouched), (pairs, E) of every iteration that ran, and the last iteration's squared distance per source point
+ * (+inf: unmatched).  cloud, history and distances return the count (and copy when the pointer is not NULL). */
+int        lmono_icp_transform(lmono_ctx *, lmono_icp *, double out[12]);
+int64_t    lmono_icp_cloud(lmono_ctx *, lmono_icp *, lmono_point_rgb *out_h, int64_t cap);
+int64_t    lmono_icp_history(lmono_ctx *, lmono_icp *, int64_t *n_e_h, int64_t cap);
+int64_t    lmono_icp_distances(lmono_ctx *, lmono_icp *, float *d2_h, int64_t cap);
+/* n distinct maps each fold in the aligned cloud of one of n distinct aligners, from device memory: the two insert launches and the
+ * capacity rules of lmono_voxel_map_insert_frames, unchanged (stats [4] per map as there). */
+int        lmono_voxel_map_insert_aligned(lmono_ctx *, int n, lmono_voxel_map *const *maps, lmono_icp *const *icps, int64_t *stats);
+
 /* ---- image feature tracker ---------------------------------------------------------------------------------
  * Replaces FeatureTracker::trackImage of the mono path, use_rejectF = 0 or 1 (lmono_tracker_set_reject_f) (mono_lidar_mapping/src/image_process/
  * FeatureTracker.cc:189-433): BGR2GRAY (:193), forward / backward pyramidal LK with the 0.5 px round-trip and inBorder tests

@@ -785,6 +785,19 @@ class VoxelMap(_Handle):
         ctx.check(ctx.L.lmono_voxel_map_insert_filtered(ctx.h, n, mh, fh, stats.ctypes.data))
         return stats
 
+    @staticmethod
+    def insert_aligned(maps, aligners):
+        """The aligned cloud of each CloudAligner's last align into its map, from device memory: the two insert launches and the capacity
+        rules of insert_frames; returns stats [n][4]."""
+        n = len(maps)
+        if n == 0 or len(aligners) != n:
+            raise LmonoError("one aligner per map")
+        ctx = maps[0].ctx
+        mh = (C.c_void_p * n)(*[m.h for m in maps]); ah = (C.c_void_p * n)(*[a.h for a in aligners])
+        stats = np.zeros((n, 4), np.int64)
+        ctx.check(ctx.L.lmono_voxel_map_insert_aligned(ctx.h, n, mh, ah, stats.ctypes.data))
+        return stats
+
     def compose(self, sources, transforms, stats=False):
         """Fold the voxel maps `sources`, each moved by its rigid transform ([n][12] or [n][3][4] float64, row-major 3 x 4, applied as given),
         into this map (lmono_voxel_map_compose): every source voxel with its count as weight.  All or nothing; the sources are
@@ -974,6 +987,128 @@ class OutlierFilter(_Handle):
         out = np.zeros(2, np.int64)
         self.ctx.check(self.ctx.L.lmono_sor_diag(self.ctx.h, self.h, out.ctypes.data))
         return out
+
+
+class CloudAligner(_Handle):
+    """Point-to-point ICP of a cloud against a target on the device, between OutlierFilter and VoxelMap (lmono_icp_*).  A target is
+    set once (a POINT_RGB array, device memory, a VoxelMap, or the last aligned cloud) and serves every align until the next one.  align* return the
+    call's stats [source points, not usable, target points, rejected, iterations, status, pairs, E of the last iteration]; the aligned cloud
+    stays on the device for VoxelMap.insert_aligned and comes to the host with cloud().  cell and max_rings tune the search grid and change no
+    result (defaults: lmono_icp_default_cell(max_corr), which is max_corr / 1.75 or an ulp or two above it, and 2).  An LmonoError carries the C return value in .code."""
+
+    _destroy = "lmono_icp_destroy"
+
+    def __init__(self, ctx, max_source_points, max_target_points, max_corr=0.5, max_iter=50, eps=1e-8, mse_eps=0.0, cell=None, max_rings=2):
+        super().__init__(ctx)
+        self.max_source_points = int(max_source_points)
+        self.max_target_points = int(max_target_points)
+        self.stats = np.zeros(8, np.int64)
+        if cell is None:
+            cell = ctx.L.lmono_icp_default_cell(C.c_float(max_corr))   # the smallest cell >= max_corr / 1.75 that 2 rings cover max_corr with
+        self._create("lmono_icp_create", int(max_source_points), int(max_target_points), C.c_float(max_corr), int(max_iter), C.c_double(eps),
+                     C.c_double(mse_eps), C.c_float(cell), int(max_rings))
+
+    @staticmethod
+    def _points(points):
+        p = np.ascontiguousarray(points)
+        if p.dtype != POINT_RGB:
+            raise LmonoError("points must be a POINT_RGB array")
+        return p
+
+    def set_guess(self, g=None):
+        """g: [12] or [3][4] float64, row-major 3 x 4, applied to the source before the first iteration; None: identity."""
+        if g is None:
+            self.ctx.check(self.ctx.L.lmono_icp_set_guess(self.ctx.h, self.h, None))
+            return
+        g = np.ascontiguousarray(g, np.float64).reshape(-1)
+        if g.size != 12:
+            raise LmonoError("the guess is a 3 x 4 transform")
+        self.ctx.check(self.ctx.L.lmono_icp_set_guess(self.ctx.h, self.h, g.ctypes.data))
+
+    def set_poll_interval(self, pairs):
+        """Launch pairs between two reads of the done words; changes no result."""
+        self.ctx.check(self.ctx.L.lmono_icp_set_poll_interval(self.ctx.h, self.h, int(pairs)))
+
+    def set_target(self, points):
+        p = self._points(points)
+        self.ctx.check(self.ctx.L.lmono_icp_set_target(self.ctx.h, self.h, p.ctypes.data if len(p) else None, len(p)))
+
+    def set_target_d(self, ptr, n):
+        """n lmono_point_rgb records in device memory."""
+        self.ctx.check(self.ctx.L.lmono_icp_set_target_d(self.ctx.h, self.h, C.c_void_p(int(ptr)), int(n)))
+
+    def set_target_map(self, voxel_map):
+        """One point per occupied voxel of a VoxelMap (what read() gives), without a host copy."""
+        self.ctx.check(self.ctx.L.lmono_icp_set_target_map(self.ctx.h, self.h, voxel_map.h))
+
+    def set_target_aligned(self):
+        """The aligned cloud of the last align becomes the target."""
+        self.ctx.check(self.ctx.L.lmono_icp_set_target_aligned(self.ctx.h, self.h))
+
+    def align(self, points):
+        """points: a POINT_RGB array on the host."""
+        p = self._points(points)
+        stats = np.zeros(8, np.int64)
+        self.ctx.check(self.ctx.L.lmono_icp_align(self.ctx.h, self.h, p.ctypes.data if len(p) else None, len(p), stats.ctypes.data))
+        self.stats = stats
+        return stats
+
+    def align_d(self, ptr, n):
+        """n lmono_point_rgb records in device memory."""
+        stats = np.zeros(8, np.int64)
+        self.ctx.check(self.ctx.L.lmono_icp_align_d(self.ctx.h, self.h, C.c_void_p(int(ptr)), int(n), stats.ctypes.data))
+        self.stats = stats
+        return stats
+
+    @staticmethod
+    def _batch(fn, aligners, others, what):
+        n = len(aligners)
+        if n == 0 or len(others) != n:
+            raise LmonoError("one %s per aligner" % what)
+        ctx = aligners[0].ctx
+        ah = (C.c_void_p * n)(*[a.h for a in aligners]); oh = (C.c_void_p * n)(*[o.h for o in others])
+        stats = np.zeros((n, 8), np.int64)
+        ctx.check(getattr(ctx.L, fn)(ctx.h, n, ah, oh, stats.ctypes.data))
+        for a, s in zip(aligners, stats):
+            a.stats = s.copy()
+        return stats
+
+    @staticmethod
+    def align_frames(aligners, builders):
+        """The world-frame cloud of each builder's last frame against its aligner's target, one launch per phase for all; returns stats [n][8]."""
+        return CloudAligner._batch("lmono_icp_align_frames", aligners, builders, "builder")
+
+    @staticmethod
+    def align_filtered(aligners, filters):
+        """The last output of each OutlierFilter against its aligner's target; returns stats [n][8]."""
+        return CloudAligner._batch("lmono_icp_align_filtered", aligners, filters, "filter")
+
+    def transform(self):
+        """[3][4] float64 of the last align, the guess included: what VoxelMap.compose takes."""
+        out = np.zeros(12, np.float64)
+        self.ctx.check(self.ctx.L.lmono_icp_transform(self.ctx.h, self.h, out.ctypes.data))
+        return out.reshape(3, 4)
+
+    def cloud(self):
+        """Every input point of the last align in input order, moved by its result; the payload is untouched."""
+        n = int(self.ctx.check(self.ctx.L.lmono_icp_cloud(self.ctx.h, self.h, None, 0)))
+        out = np.zeros(max(n, 1), POINT_RGB)
+        self.ctx.check(self.ctx.L.lmono_icp_cloud(self.ctx.h, self.h, out.ctypes.data, n))
+        return out[:n]
+
+    def history(self):
+        """(pairs, E) [k][2] int64 of every iteration of the last align."""
+        n = int(self.ctx.check(self.ctx.L.lmono_icp_history(self.ctx.h, self.h, None, 0)))
+        out = np.zeros((max(n, 1), 2), np.int64)
+        self.ctx.check(self.ctx.L.lmono_icp_history(self.ctx.h, self.h, out.ctypes.data, n))
+        return out[:n]
+
+    def distances(self):
+        """The last iteration's squared distance per source point, float32; +inf where the point is unmatched."""
+        n = int(self.ctx.check(self.ctx.L.lmono_icp_distances(self.ctx.h, self.h, None, 0)))
+        out = np.zeros(max(n, 1), np.float32)
+        self.ctx.check(self.ctx.L.lmono_icp_distances(self.ctx.h, self.h, out.ctypes.data, n))
+        return out[:n]
 
 
 TRACK_RECORD = np.dtype([("id", np.int32), ("x_n", np.float32), ("y_n", np.float32), ("u", np.float32), ("v", np.float32),

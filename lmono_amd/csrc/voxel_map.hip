@@ -254,12 +254,21 @@ __global__ __launch_bounds__(kVmT) void k_vm_rehash(const VmGrowJob *jobs)
 }
 
 // records with count > 0, in no order, into out[cap]; n counts them all
+// the output point of an occupied record as a cloud point (what lmono_voxel_map_read gives)
+__device__ inline PtRgb vm_out_point(const VmRec &r, float leaf)
+{
+    const VmPoint p = vm_point(r, leaf);
+    PtRgb o;
+    o.x = p.x; o.y = p.y; o.z = p.z; o.bgra = p.bgra;
+    return o;
+}
+
 __global__ __launch_bounds__(kVmT) void k_vm_compact(const VmRec *rec, unsigned long long slots, VmRec *out, unsigned cap, unsigned *n)
 {
     const unsigned long long s = (unsigned long long)blockIdx.x * kVmT + threadIdx.x;
     if (s >= slots) return;
     const VmRec r = rec[s];
-    if (r.key == kVmEmpty || r.w[0] == 0) return;
+    if (!vm_occupied(r)) return;
     const unsigned at = atomicAdd(n, 1u);
     if (at < cap) out[at] = r;
 }
@@ -338,10 +347,7 @@ __global__ __launch_bounds__(kVmT) void k_vm_finish(const VmRec *rec, unsigned n
 {
     const unsigned i = blockIdx.x * kVmT + threadIdx.x;
     if (i >= n) return;
-    const VmPoint p = vm_point(rec[i], leaf);
-    PtRgb o;
-    o.x = p.x; o.y = p.y; o.z = p.z; o.bgra = p.bgra;
-    out[i] = o;
+    out[i] = vm_out_point(rec[i], leaf);
 }
 
 } // namespace lmono

@@ -59,6 +59,9 @@ LMONO_VM_HD uint64_t vm_mix(uint64_t k)
     return k;
 }
 
+// a table slot that holds a voxel: claimed, and by a call that was not refused (a refused call's claims stay with count 0, unseen)
+LMONO_VM_HD bool vm_occupied(const VmRec &r) { return r.key != kVmEmpty && r.w[0] != 0; }
+
 // exact (every conversion and the sum under the division are exact, so the result is the correctly rounded chain of the formula) while
 // s + count / 2 < 2^53; s <= 65535 * count, so while a voxel's count stays below 2^36 -- composed maps (below) reach counts inserts never do
 LMONO_VM_HD float vm_axis_out(int i, uint64_t s, uint64_t count, float leaf)

@@ -421,6 +421,12 @@ public:
     // The pcl::StatisticalOutlierRemoval the reference carries commented out in front of that grid (Map_Builder.cc:24-29), as this project
     // defines it: once set, the queued frame goes through the filter on the device and the voxel map takes the kept points.
     void setOutlierFilter(int mean_k, double stddev_mul, float cell = 0.1f, int max_rings = 8);
+    // The pcl::IterativeClosestPoint the reference carries commented out between the two (Map_Builder.cc:31-59), as this project defines it
+    // (DESIGN.md 6c-5), against the map instead of the frame before: once set (after setVoxelMap), the queued frame -- the filter's kept points
+    // when a filter is set -- is aligned against the voxel map on the device and the map takes the aligned cloud.  While the map is empty there
+    // is no target and the frame is inserted as it is.  alignerStats(): the [8] stats of the queued frame's align (when none ran: status 3, the rest 0).
+    void setAligner(float max_corr, int max_iter = 50, double eps = 1e-8, double mse_eps = 0.0);
+    const int64_t *alignerStats() const { return icp_stats_; }
     // Submaps, so that the map can follow a corrected trajectory (the reference's own map-to-map attempt is commented out,
     // Map_Builder.cc:110-210).  After setVoxelMap: processMapping() folds the queued frame (through the outlier filter when one is set) into
     // the current submap too -- a voxel map of leaf_sub that takes frames_per_submap frames and is anchored at the pose of its first one.
@@ -442,6 +448,8 @@ private:
     // (fold_ captures this: a MapBuilder is neither copied nor moved, see the deleted copy operations above)
     std::shared_ptr<lmono_voxel_map> vm_;
     std::shared_ptr<lmono_sor> sor_;
+    std::shared_ptr<lmono_icp> icp_;
+    int64_t icp_stats_[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
     std::function<void()> fold_;
     struct Submaps {
         int per = 0, frames = 0;                                  // frames per submap (0: not set), frames folded

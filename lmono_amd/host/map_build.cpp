@@ -4,11 +4,13 @@
 // -> MapBuilder::associateToMap -> processMapping; writes <out>/rgb_map<index>.ply every 10 frames and the timing log
 // <out>/mapping_recorder.txt, and dumps the products of the last frame (<out>/depth_last.u8, <out>/cloud_cam_last.bin,
 // <out>/cloud_world_last.bin) for inspection.
-//   map_build <sequence_dir> <trajectory.txt> <out_dir> [n_frames] [width height fx fy cx cy] [submap=N:CORRECTED_TRAJECTORY[:LEAF_SUB]] [sor=K:MULT[:CELL:RINGS]] [voxel=LEAF[:MAX_VOXELS[:GROW_LIMIT]]]
+//   map_build <sequence_dir> <trajectory.txt> <out_dir> [n_frames] [width height fx fy cx cy] [submap=N:CORRECTED_TRAJECTORY[:LEAF_SUB]] [sor=K:MULT[:CELL:RINGS]] [icp=D[:ITERS[:EPS]]] [voxel=LEAF[:MAX_VOXELS[:GROW_LIMIT]]]
 // With the trailing voxel= argument every frame is also folded into a voxel-grid map, written at the end as
 // <out>/rgb_map_voxel.ply; without it nothing changes.  With a GROW_LIMIT the map starts at MAX_VOXELS and grows on the device up to that limit, and so
 // do the composed map and the submaps (each from MAX_VOXELS), whose tables are shrunk to their content once closed.  With sor= in front of it every frame passes the statistical outlier removal
-// (CELL 0.1 and RINGS 8 unless given) on its way into that map.  With submap= in front of those every N frames also go into a
+// (CELL 0.1 and RINGS 8 unless given) on its way into that map.  With icp= directly in front of voxel= every frame but the first is aligned against that map by
+// point-to-point ICP (max correspondence distance D, ITERS 50 and EPS 1e-8 unless given) before it is folded in, and an
+// "ICP <frame> iterations <k> status <s> N <pairs> mse <m^2>" line is printed per frame (a frame that was not aligned: iterations 0, status 3).  With submap= in front of those every N frames also go into a
 // submap of their own (LEAF_SUB 0.05 unless given), and at the end the submaps are composed under the poses of CORRECTED_TRAJECTORY (same format,
 // one line per frame: a loop-closed trajectory) into <out>/rgb_map_global.ply at the voxel= leaf.
 #include "kitti_io.hpp"
@@ -53,6 +55,14 @@ int main(int argc, char **argv)
         if (!(voxel_leaf > 0.0f)) { std::fprintf(stderr, "map_build: voxel=LEAF[:MAX_VOXELS[:GROW_LIMIT]] needs a leaf > 0\n"); return 2; }
         argc--;
     }
+    float icp_d = 0.0f;
+    int icp_iters = 50;
+    double icp_eps = 1e-8;
+    if (argc > 4 && std::strncmp(argv[argc - 1], "icp=", 4) == 0) {
+        const int got = std::sscanf(argv[argc - 1] + 4, "%f:%d:%lf", &icp_d, &icp_iters, &icp_eps);
+        if (got < 1 || !(icp_d > 0.0f) || icp_iters < 1 || !(icp_eps >= 0.0) || !(voxel_leaf > 0.0f)) { std::fprintf(stderr, "map_build: icp=D[:ITERS[:EPS]] needs D > 0, ITERS >= 1, EPS >= 0 and a voxel= argument behind it\n"); return 2; }
+        argc--;
+    }
     int sor_k = 0, sor_rings = 8;
     double sor_mul = 1.0;
     float sor_cell = 0.1f;
@@ -80,7 +90,7 @@ int main(int argc, char **argv)
         }
         argc--;
     }
-    if (argc < 4) { std::fprintf(stderr, "usage: map_build <sequence_dir> <trajectory.txt> <out_dir> [n_frames] [width height fx fy cx cy] [submap=N:CORRECTED_TRAJECTORY[:LEAF_SUB]] [sor=K:MULT[:CELL:RINGS]] [voxel=LEAF[:MAX_VOXELS[:GROW_LIMIT]]]\n"); return 2; }
+    if (argc < 4) { std::fprintf(stderr, "usage: map_build <sequence_dir> <trajectory.txt> <out_dir> [n_frames] [width height fx fy cx cy] [submap=N:CORRECTED_TRAJECTORY[:LEAF_SUB]] [sor=K:MULT[:CELL:RINGS]] [icp=D[:ITERS[:EPS]]] [voxel=LEAF[:MAX_VOXELS[:GROW_LIMIT]]]\n"); return 2; }
     const std::string seq = argv[1], traj = argv[2], out = argv[3];
     int n_frames = argc > 4 ? std::atoi(argv[4]) : -1;
     lmono_camera cam = { 1241, 376, 718.856, 718.856, 607.1928, 185.2157, 0, 0, 0, 0, 5, 0, 0 };   // kitti00_cam.yaml, kitti_map_config_00.yaml
@@ -110,6 +120,7 @@ int main(int argc, char **argv)
         MapBuilder map_builder(hip, cam, true, out);
         if (voxel_leaf > 0.0f) map_builder.setVoxelMap(voxel_leaf, voxel_max, voxel_grow);
         if (sor_k > 0) map_builder.setOutlierFilter(sor_k, sor_mul, sor_cell, sor_rings);
+        if (icp_d > 0.0f) map_builder.setAligner(icp_d, icp_iters, icp_eps);
         if (sub_n > 0 && voxel_grow > 0) map_builder.setSubmaps(sub_n, sub_leaf, voxel_max, voxel_grow, /*compact_closed=*/true);
         else if (sub_n > 0) map_builder.setSubmaps(sub_n, sub_leaf);
         MappingLog recorder(out + "/mapping_recorder.txt");
@@ -127,6 +138,10 @@ int main(int argc, char **argv)
             recorder.write(p[0], std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
             const std::string written = map_builder.processMapping();
             std::printf("FRAME %d points_in %ld points_out %d%s%s\n", k, n, m, written.empty() ? "" : " wrote ", written.c_str());
+            if (icp_d > 0.0f) {
+                const int64_t *st = map_builder.alignerStats();
+                std::printf("ICP %d iterations %lld status %lld N %lld mse %.9g\n", k, (long long)st[4], (long long)st[5], (long long)st[6], st[6] > 0 ? (double)st[7] / (double)st[6] / 16777216.0 : 0.0);
+            }
             if (k == n_frames - 1) {
                 if (!dump(out + "/depth_last.u8", map_builder.depthMap()) || !dump(out + "/cloud_cam_last.bin", map_builder.rgbCloud(0))) return 1;
                 if (written.empty() && !dump(out + "/cloud_world_last.bin", map_builder.rgbCloud(1))) return 1;

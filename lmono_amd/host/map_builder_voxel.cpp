@@ -24,10 +24,23 @@ void MapBuilder::setVoxelMap(float leaf, int64_t max_voxels, int64_t grow_limit)
     fold_ = [this] {
         lmono_voxel_map *m = vm_.get();
         lmono_voxel_map *sub = submapForFrame();                           // the same frame into its submap
+        lmono_icp *a = icp_.get();
+        for (int64_t &v : icp_stats_) v = 0;
+        icp_stats_[5] = 3;                                               // no align ran: no iteration, no pairs, as an align of nothing reports
+        const bool align = a && lmono_voxel_map_size(hip_.get(), m) > 0;  // :31-59 between them; an empty map is no target
+        if (align) hip_.check(lmono_icp_set_target_map(hip_.get(), a, m), "lmono_icp_set_target_map");
         if (lmono_sor *f = sor_.get()) {                                   // :24-29 in front of :82-98
             hip_.check(lmono_sor_filter_frames(hip_.get(), 1, &f, &mb_, nullptr), "lmono_sor_filter_frames");
-            hip_.check(lmono_voxel_map_insert_filtered(hip_.get(), 1, &m, &f, nullptr), "lmono_voxel_map_insert_filtered");
-            if (sub) hip_.check(lmono_voxel_map_insert_filtered(hip_.get(), 1, &sub, &f, nullptr), "lmono_voxel_map_insert_filtered");
+            if (align) hip_.check(lmono_icp_align_filtered(hip_.get(), 1, &a, &f, icp_stats_), "lmono_icp_align_filtered");
+            else {
+                hip_.check(lmono_voxel_map_insert_filtered(hip_.get(), 1, &m, &f, nullptr), "lmono_voxel_map_insert_filtered");
+                if (sub) hip_.check(lmono_voxel_map_insert_filtered(hip_.get(), 1, &sub, &f, nullptr), "lmono_voxel_map_insert_filtered");
+                return;
+            }
+        } else if (align) hip_.check(lmono_icp_align_frames(hip_.get(), 1, &a, &mb_, icp_stats_), "lmono_icp_align_frames");
+        if (align) {
+            hip_.check(lmono_voxel_map_insert_aligned(hip_.get(), 1, &m, &a, nullptr), "lmono_voxel_map_insert_aligned");
+            if (sub) hip_.check(lmono_voxel_map_insert_aligned(hip_.get(), 1, &sub, &a, nullptr), "lmono_voxel_map_insert_aligned");
             return;
         }
         hip_.check(lmono_voxel_map_insert_frames(hip_.get(), 1, &m, &mb_, nullptr), "lmono_voxel_map_insert_frames");
@@ -125,6 +138,15 @@ void MapBuilder::setOutlierFilter(int mean_k, double stddev_mul, float cell, int
     lmono_sor *f = lmono_sor_create(hip_.get(), (int64_t)cam_.width * cam_.height, mean_k, stddev_mul, cell, max_rings);
     if (!f) throw std::runtime_error(std::string("lmono_sor_create: ") + lmono_last_error(hip_.get()));
     sor_ = std::shared_ptr<lmono_sor>(f, lmono_sor_destroy);
+}
+
+void MapBuilder::setAligner(float max_corr, int max_iter, double eps, double mse_eps)
+{
+    if (!vm_) throw std::runtime_error("MapBuilder::setAligner: setVoxelMap first (the map is the target)");
+    // the target is the map: as many points as it may ever hold voxels; the grid at its defaults (lmono_icp_default_cell, 2 rings)
+    lmono_icp *a = lmono_icp_create(hip_.get(), (int64_t)cam_.width * cam_.height, vm_grow_ > vm_max_ ? vm_grow_ : vm_max_, max_corr, max_iter, eps, mse_eps, lmono_icp_default_cell(max_corr), 2);
+    if (!a) throw std::runtime_error(std::string("lmono_icp_create: ") + lmono_last_error(hip_.get()));
+    icp_ = std::shared_ptr<lmono_icp>(a, lmono_icp_destroy);
 }
 
 std::vector<lmono_point_rgb> MapBuilder::voxelMap()

@@ -567,6 +567,42 @@ int64_t    lmono_icp_distances(lmono_ctx *, lmono_icp *, float *d2_h, int64_t ca
  * capacity rules of lmono_voxel_map_insert_frames, unchanged (stats [4] per map as there). */
 int        lmono_voxel_map_insert_aligned(lmono_ctx *, int n, lmono_voxel_map *const *maps, lmono_icp *const *icps, int64_t *stats);
 
+/* ---- map builder: surface normals and curvature of a cloud -------------------------------------------------
+ * The pcl::NormalEstimation with setRadiusSearch(0.05) on both clouds that opens MapBuilder::alignmentToMap, the coarse map-to-map
+ * alignment the reference carries commented out (mono_lidar_mapping/src/map_builder/Map_Builder.cc:110-210); every later stage of that
+ * function (SIFT keypoints, FPFH, the sample-consensus initial alignment) consumes these normals, and none of them is provided yet.
+ * A definition of this project (lmono_amd/csrc/normals.hpp): the neighbours of a point are all valid points, itself and duplicates
+ * included, within radius of it (d2 <= radius^2 in float32); their offsets from the point in 2^-16 m fixed point about the middle of
+ * the cloud's bounding box give exact integer sums; the scatter matrix of those sums is diagonalised in fp64 (cyclic Jacobi, 8 sweeps);
+ * the normal is the unit eigenvector of the smallest eigenvalue, curvature = that eigenvalue over the trace (0 for a zero trace).  The
+ * normal faces the viewpoint; without one, or exactly edge-on, its component of largest magnitude is positive.  A record is a pure
+ * function of the SET of points and of the point: the same bytes for every point order, grid tuning (cell, max_rings) and batch.
+ * Parity with PCL is unpinned.  Limits: max_points <= 2^26, 0 < radius <= 4, min_neighbours >= 3, (max_rings - 0.25) cell >= radius.
+ * A point that is non-finite or 2048 m or more from the origin on an axis is rejected: never a neighbour, count 0.  A rejected point
+ * and a point with fewer than min_neighbours neighbours get four NaNs (0x7fc00000).
+ * stats [8] per stream: points in, rejected, with a normal, without (too few neighbours), sum of the neighbour counts, largest
+ * neighbour count, 0, 0.  n > max_points returns LMONO_ECAPACITY before any launch; n == 0 is a successful empty result with no
+ * launch.  Every compute replaces the handle's last result. */
+typedef struct lmono_normals lmono_normals;
+typedef struct { float nx, ny, nz, curvature; } lmono_normal;
+lmono_normals *lmono_normals_create(lmono_ctx *, int64_t max_points, float radius, int min_neighbours, float cell, int max_rings);
+void       lmono_normals_destroy(lmono_normals *);
+/* the default cell for radius at max_rings = 2: the smallest float32 h >= radius / 1.75f with (2 - 0.25) h >= radius in float32 */
+float      lmono_normals_default_cell(float radius);
+/* viewpoint: three finite floats or NULL */
+int        lmono_normals_compute(lmono_ctx *, lmono_normals *, const lmono_point_rgb *pts_h, int64_t n, const float *viewpoint, int64_t *stats);
+int        lmono_normals_compute_d(lmono_ctx *, lmono_normals *, const lmono_point_rgb *pts_d, int64_t n, const float *viewpoint, int64_t *stats);
+/* n distinct handles each take the world-frame cloud of the last frame of one of n distinct builders straight from device memory; one
+ * launch per phase for all streams (viewpoints: [n][3] or NULL).  A stream's bytes do not depend on the batch it travels in. */
+int        lmono_normals_compute_frames(lmono_ctx *, int n, lmono_normals *const *normals, lmono_map_builder *const *mbs, const float *viewpoints, int64_t *stats);
+/* one point per occupied voxel, what lmono_voxel_map_read gives, without a host copy and in the order the device found them:
+ * lmono_normals_cloud tells which point each record belongs to */
+int        lmono_normals_compute_map(lmono_ctx *, lmono_normals *, lmono_voxel_map *, const float *viewpoint, int64_t *stats);
+/* the last result in input order: records and neighbour counts (either pointer may be NULL), and the points they belong to.  Both
+ * return the count (and copy when a pointer is not NULL). */
+int64_t    lmono_normals_read(lmono_ctx *, lmono_normals *, lmono_normal *out_h, uint32_t *count_h, int64_t cap);
+int64_t    lmono_normals_cloud(lmono_ctx *, lmono_normals *, lmono_point_rgb *out_h, int64_t cap);
+
 /* ---- image feature tracker ---------------------------------------------------------------------------------
  * Replaces FeatureTracker::trackImage of the mono path, use_rejectF = 0 or 1 (lmono_tracker_set_reject_f) (mono_lidar_mapping/src/image_process/
  * FeatureTracker.cc:189-433): BGR2GRAY (:193), forward / backward pyramidal LK with the 0.5 px round-trip and inBorder tests

@@ -1111,6 +1111,92 @@ class CloudAligner(_Handle):
         return out[:n]
 
 
+NORMAL = np.dtype([("nx", np.float32), ("ny", np.float32), ("nz", np.float32), ("curvature", np.float32)])
+
+
+class SurfaceNormals(_Handle):
+    """Surface normals and curvature of a cloud on the device (lmono_normals_*): per point the unit eigenvector of the smallest
+    eigenvalue of its neighbours' scatter matrix within radius, facing the viewpoint (without one: its largest component positive), and that
+    eigenvalue over the trace.  compute* return the call's stats [points in, rejected, with a normal, without, sum of the neighbour counts, largest
+    count, 0, 0]; read() gives (records, counts) in input order, NaN records where a point is rejected or has fewer than min_neighbours
+    neighbours; cloud() the points they belong to.  cell and max_rings tune the search grid and change no result (defaults:
+    lmono_normals_default_cell(radius) and 2).  An LmonoError carries the C return value in .code."""
+
+    _destroy = "lmono_normals_destroy"
+
+    def __init__(self, ctx, max_points, radius=0.05, min_neighbours=3, cell=None, max_rings=2):
+        super().__init__(ctx)
+        self.max_points = int(max_points)
+        self.stats = np.zeros(8, np.int64)
+        if cell is None:
+            cell = ctx.L.lmono_normals_default_cell(C.c_float(radius))
+        self._create("lmono_normals_create", int(max_points), C.c_float(radius), int(min_neighbours), C.c_float(cell), int(max_rings))
+
+    @staticmethod
+    def _viewpoints(v, n):
+        """-> (float32 array or None, its address or None); the array must outlive the call."""
+        if v is None:
+            return None, None
+        v = np.ascontiguousarray(v, np.float32).reshape(-1)
+        if v.size != 3 * n:
+            raise LmonoError("a viewpoint is three floats per stream")
+        return v, v.ctypes.data
+
+    def compute(self, points, viewpoint=None):
+        """points: a POINT_RGB array on the host."""
+        p = CloudAligner._points(points)
+        v, vp = self._viewpoints(viewpoint, 1)
+        stats = np.zeros(8, np.int64)
+        self.ctx.check(self.ctx.L.lmono_normals_compute(self.ctx.h, self.h, p.ctypes.data if len(p) else None, len(p), vp, stats.ctypes.data))
+        self.stats = stats
+        return stats
+
+    def compute_d(self, ptr, n, viewpoint=None):
+        """n lmono_point_rgb records in device memory."""
+        v, vp = self._viewpoints(viewpoint, 1)
+        stats = np.zeros(8, np.int64)
+        self.ctx.check(self.ctx.L.lmono_normals_compute_d(self.ctx.h, self.h, C.c_void_p(int(ptr)), int(n), vp, stats.ctypes.data))
+        self.stats = stats
+        return stats
+
+    @staticmethod
+    def compute_frames(normals, builders, viewpoints=None):
+        """The world-frame cloud of each builder's last frame, one launch per phase for all; viewpoints: [n][3] or None; returns stats [n][8]."""
+        n = len(normals)
+        if n == 0 or len(builders) != n:
+            raise LmonoError("one builder per SurfaceNormals")
+        ctx = normals[0].ctx
+        v, vp = SurfaceNormals._viewpoints(viewpoints, n)
+        nh = (C.c_void_p * n)(*[a.h for a in normals]); bh = (C.c_void_p * n)(*[b.h for b in builders])
+        stats = np.zeros((n, 8), np.int64)
+        ctx.check(ctx.L.lmono_normals_compute_frames(ctx.h, n, nh, bh, vp, stats.ctypes.data))
+        for a, s in zip(normals, stats):
+            a.stats = s.copy()
+        return stats
+
+    def compute_map(self, voxel_map, viewpoint=None):
+        """One point per occupied voxel of a VoxelMap (what read() gives, in the device's order: see cloud()), without a host copy."""
+        v, vp = self._viewpoints(viewpoint, 1)
+        stats = np.zeros(8, np.int64)
+        self.ctx.check(self.ctx.L.lmono_normals_compute_map(self.ctx.h, self.h, voxel_map.h, vp, stats.ctypes.data))
+        self.stats = stats
+        return stats
+
+    def read(self):
+        """(records [n] NORMAL, counts [n] uint32) of the last compute, in input order."""
+        n = int(self.ctx.check(self.ctx.L.lmono_normals_read(self.ctx.h, self.h, None, None, 0)))
+        rec = np.zeros(max(n, 1), NORMAL); cnt = np.zeros(max(n, 1), np.uint32)
+        self.ctx.check(self.ctx.L.lmono_normals_read(self.ctx.h, self.h, rec.ctypes.data, cnt.ctypes.data, n))
+        return rec[:n], cnt[:n]
+
+    def cloud(self):
+        """The points the records of the last compute belong to, in input order."""
+        n = int(self.ctx.check(self.ctx.L.lmono_normals_cloud(self.ctx.h, self.h, None, 0)))
+        out = np.zeros(max(n, 1), POINT_RGB)
+        self.ctx.check(self.ctx.L.lmono_normals_cloud(self.ctx.h, self.h, out.ctypes.data, n))
+        return out[:n]
+
+
 TRACK_RECORD = np.dtype([("id", np.int32), ("x_n", np.float32), ("y_n", np.float32), ("u", np.float32), ("v", np.float32),
                          ("vx", np.float32), ("vy", np.float32), ("track_cnt", np.int32)])
 TRACK_MAX_POINTS = 512

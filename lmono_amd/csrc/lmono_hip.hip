@@ -355,6 +355,7 @@ template <typename H> static int batch_handle_fault(const lmono_ctx *c, int s, H
 #include "voxel_map_abi.hip"
 #include "sor_abi.hip"
 #include "icp_abi.hip"
+#include "normals_abi.hip"
 #include "track_abi.hip"
 #include "keyframe_abi.hip"
 #include "pnp_abi.hip"

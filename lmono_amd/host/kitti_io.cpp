@@ -97,6 +97,24 @@ bool write_ply_binary(const std::string &path, const PointRgb *pts, size_t n)
     return std::fclose(f) == 0 && ok;
 }
 
+bool write_ply_binary_normals(const std::string &path, const PointRgb *pts, const PlyNormal *normals, size_t n)
+{
+    FILE *f = std::fopen(path.c_str(), "wb");
+    if (!f) return false;
+    std::fprintf(f, "ply\nformat binary_little_endian 1.0\ncomment lmono surface normals\nelement vertex %zu\n", n);
+    std::fprintf(f, "property float x\nproperty float y\nproperty float z\nproperty uchar red\nproperty uchar green\nproperty uchar blue\n");
+    std::fprintf(f, "property float nx\nproperty float ny\nproperty float nz\nproperty float curvature\nend_header\n");
+    std::vector<unsigned char> buf(n * 31);
+    for (size_t i = 0; i < n; i++) {
+        unsigned char *o = buf.data() + i * 31;
+        std::memcpy(o, &pts[i].x, 12);
+        o[12] = (unsigned char)(pts[i].bgra >> 16); o[13] = (unsigned char)(pts[i].bgra >> 8); o[14] = (unsigned char)pts[i].bgra;
+        std::memcpy(o + 15, &normals[i], 16);
+    }
+    const bool ok = n == 0 || std::fwrite(buf.data(), 31, n, f) == n;
+    return std::fclose(f) == 0 && ok;
+}
+
 bool read_ply_binary(const std::string &path, std::vector<PointRgb> &pts)
 {
     FILE *f = std::fopen(path.c_str(), "rb");

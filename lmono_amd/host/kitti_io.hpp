@@ -51,6 +51,10 @@ private:
 struct PointRgb { float x, y, z; unsigned int bgra; };
 bool write_ply_binary(const std::string &path, const PointRgb *pts, size_t n);
 bool read_ply_binary(const std::string &path, std::vector<PointRgb> &pts);     // reads what write_ply_binary wrote
+// a coloured cloud with its surface normals: vertex x y z float, red green blue uchar, nx ny nz curvature float, no other
+// element (what lmono_amd.kitti_io.read_ply_binary_normals reads); one record per point, the layout of lmono_normal
+struct PlyNormal { float nx, ny, nz, curvature; };
+bool write_ply_binary_normals(const std::string &path, const PointRgb *pts, const PlyNormal *normals, size_t n);
 std::string rgb_map_path(const std::string &dir, int map_index);               // <dir>/rgb_map<index>.ply (Map_Builder.cc:75)
 
 class MappingLog {                                                             // map_build_node.cc:230 "%f %f \n"

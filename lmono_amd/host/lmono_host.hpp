@@ -427,6 +427,12 @@ public:
     // is no target and the frame is inserted as it is.  alignerStats(): the [8] stats of the queued frame's align (when none ran: status 3, the rest 0).
     void setAligner(float max_corr, int max_iter = 50, double eps = 1e-8, double mse_eps = 0.0);
     const int64_t *alignerStats() const { return icp_stats_; }
+    // The pcl::NormalEstimation that opens the reference's commented-out alignmentToMap (Map_Builder.cc:110-210), as this project defines it
+    // (DESIGN.md 6c-6), over the voxel map: once set (after setVoxelMap), voxelNormals() computes the normal and curvature of every voxel's point on
+    // the device, without a viewpoint, and returns the points (the voxelMap() points in the device's order) with one record each.  The grid at
+    // its defaults (lmono_normals_default_cell, 2 rings) unless given.
+    void setNormals(float radius, int min_neighbours = 3, float cell = 0.0f, int max_rings = 2);
+    void voxelNormals(std::vector<lmono_point_rgb> &points, std::vector<lmono_normal> &normals);
     // Submaps, so that the map can follow a corrected trajectory (the reference's own map-to-map attempt is commented out,
     // Map_Builder.cc:110-210).  After setVoxelMap: processMapping() folds the queued frame (through the outlier filter when one is set) into
     // the current submap too -- a voxel map of leaf_sub that takes frames_per_submap frames and is anchored at the pose of its first one.
@@ -449,6 +455,7 @@ private:
     std::shared_ptr<lmono_voxel_map> vm_;
     std::shared_ptr<lmono_sor> sor_;
     std::shared_ptr<lmono_icp> icp_;
+    std::shared_ptr<lmono_normals> nrm_;
     int64_t icp_stats_[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
     std::function<void()> fold_;
     struct Submaps {

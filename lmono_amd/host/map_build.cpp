@@ -4,8 +4,10 @@
 // -> MapBuilder::associateToMap -> processMapping; writes <out>/rgb_map<index>.ply every 10 frames and the timing log
 // <out>/mapping_recorder.txt, and dumps the products of the last frame (<out>/depth_last.u8, <out>/cloud_cam_last.bin,
 // <out>/cloud_world_last.bin) for inspection.
-//   map_build <sequence_dir> <trajectory.txt> <out_dir> [n_frames] [width height fx fy cx cy] [submap=N:CORRECTED_TRAJECTORY[:LEAF_SUB]] [sor=K:MULT[:CELL:RINGS]] [icp=D[:ITERS[:EPS]]] [voxel=LEAF[:MAX_VOXELS[:GROW_LIMIT]]]
-// With the trailing voxel= argument every frame is also folded into a voxel-grid map, written at the end as
+//   map_build <sequence_dir> <trajectory.txt> <out_dir> [n_frames] [width height fx fy cx cy] [submap=N:CORRECTED_TRAJECTORY[:LEAF_SUB]] [sor=K:MULT[:CELL:RINGS]] [icp=D[:ITERS[:EPS]]] [voxel=LEAF[:MAX_VOXELS[:GROW_LIMIT]]] [normals=R[:MIN[:CELL:RINGS]]]
+// With normals= behind voxel= the finished voxel map's points get their surface normals and curvature within radius R (MIN 3 neighbours,
+// the default grid unless given; no viewpoint), written as <out>/rgb_map_voxel_normals.ply beside rgb_map_voxel.ply: the same points in the device's order.
+// With the voxel= argument every frame is also folded into a voxel-grid map, written at the end as
 // <out>/rgb_map_voxel.ply; without it nothing changes.  With a GROW_LIMIT the map starts at MAX_VOXELS and grows on the device up to that limit, and so
 // do the composed map and the submaps (each from MAX_VOXELS), whose tables are shrunk to their content once closed.  With sor= in front of it every frame passes the statistical outlier removal
 // (CELL 0.1 and RINGS 8 unless given) on its way into that map.  With icp= directly in front of voxel= every frame but the first is aligned against that map by
@@ -43,6 +45,16 @@ template <typename T> static bool dump(const std::string &path, const std::vecto
 
 int main(int argc, char **argv)
 {
+    float nrm_r = 0.0f, nrm_cell = 0.0f;
+    int nrm_min = 3, nrm_rings = 2;
+    if (argc > 5 && std::strncmp(argv[argc - 1], "normals=", 8) == 0) {
+        const int got = std::sscanf(argv[argc - 1] + 8, "%f:%d:%f:%d", &nrm_r, &nrm_min, &nrm_cell, &nrm_rings);
+        if ((got != 1 && got != 2 && got != 4) || !(nrm_r > 0.0f) || nrm_min < 3 || std::strncmp(argv[argc - 2], "voxel=", 6) != 0) {
+            std::fprintf(stderr, "map_build: normals=R[:MIN[:CELL:RINGS]] needs R > 0, MIN >= 3 and a voxel= argument directly in front of it\n");
+            return 2;
+        }
+        argc--;
+    }
     float voxel_leaf = 0.0f;
     long long voxel_max = 1 << 22, voxel_grow = 0;
     if (argc > 4 && std::strncmp(argv[argc - 1], "voxel=", 6) == 0) {
@@ -90,7 +102,7 @@ int main(int argc, char **argv)
         }
         argc--;
     }
-    if (argc < 4) { std::fprintf(stderr, "usage: map_build <sequence_dir> <trajectory.txt> <out_dir> [n_frames] [width height fx fy cx cy] [submap=N:CORRECTED_TRAJECTORY[:LEAF_SUB]] [sor=K:MULT[:CELL:RINGS]] [icp=D[:ITERS[:EPS]]] [voxel=LEAF[:MAX_VOXELS[:GROW_LIMIT]]]\n"); return 2; }
+    if (argc < 4) { std::fprintf(stderr, "usage: map_build <sequence_dir> <trajectory.txt> <out_dir> [n_frames] [width height fx fy cx cy] [submap=N:CORRECTED_TRAJECTORY[:LEAF_SUB]] [sor=K:MULT[:CELL:RINGS]] [icp=D[:ITERS[:EPS]]] [voxel=LEAF[:MAX_VOXELS[:GROW_LIMIT]]] [normals=R[:MIN[:CELL:RINGS]]]\n"); return 2; }
     const std::string seq = argv[1], traj = argv[2], out = argv[3];
     int n_frames = argc > 4 ? std::atoi(argv[4]) : -1;
     lmono_camera cam = { 1241, 376, 718.856, 718.856, 607.1928, 185.2157, 0, 0, 0, 0, 5, 0, 0 };   // kitti00_cam.yaml, kitti_map_config_00.yaml
@@ -121,6 +133,7 @@ int main(int argc, char **argv)
         if (voxel_leaf > 0.0f) map_builder.setVoxelMap(voxel_leaf, voxel_max, voxel_grow);
         if (sor_k > 0) map_builder.setOutlierFilter(sor_k, sor_mul, sor_cell, sor_rings);
         if (icp_d > 0.0f) map_builder.setAligner(icp_d, icp_iters, icp_eps);
+        if (nrm_r > 0.0f) map_builder.setNormals(nrm_r, nrm_min, nrm_cell, nrm_rings);
         if (sub_n > 0 && voxel_grow > 0) map_builder.setSubmaps(sub_n, sub_leaf, voxel_max, voxel_grow, /*compact_closed=*/true);
         else if (sub_n > 0) map_builder.setSubmaps(sub_n, sub_leaf);
         MappingLog recorder(out + "/mapping_recorder.txt");
@@ -151,6 +164,14 @@ int main(int argc, char **argv)
             const std::vector<lmono_point_rgb> v = map_builder.voxelMap();
             const std::string path = out + "/rgb_map_voxel.ply";
             if (!write_ply_binary(path, reinterpret_cast<const PointRgb *>(v.data()), v.size())) { std::fprintf(stderr, "cannot write %s\n", path.c_str()); return 1; }
+        }
+        if (nrm_r > 0.0f) {
+            std::vector<lmono_point_rgb> v;
+            std::vector<lmono_normal> nv;
+            map_builder.voxelNormals(v, nv);
+            static_assert(sizeof(lmono_normal) == sizeof(PlyNormal), "the record is the file's");
+            const std::string path = out + "/rgb_map_voxel_normals.ply";
+            if (!write_ply_binary_normals(path, reinterpret_cast<const PointRgb *>(v.data()), reinterpret_cast<const PlyNormal *>(nv.data()), v.size())) { std::fprintf(stderr, "cannot write %s\n", path.c_str()); return 1; }
         }
         if (sub_n > 0) {
             const std::vector<lmono_point_rgb> v = map_builder.composeMap(corrected);

@@ -149,6 +149,29 @@ void MapBuilder::setAligner(float max_corr, int max_iter, double eps, double mse
     icp_ = std::shared_ptr<lmono_icp>(a, lmono_icp_destroy);
 }
 
+void MapBuilder::setNormals(float radius, int min_neighbours, float cell, int max_rings)
+{
+    if (!vm_) throw std::runtime_error("MapBuilder::setNormals: setVoxelMap first (the map's points get the normals)");
+    // one point per voxel: as many points as the map may ever hold voxels
+    lmono_normals *s = lmono_normals_create(hip_.get(), vm_grow_ > vm_max_ ? vm_grow_ : vm_max_, radius, min_neighbours, cell > 0.0f ? cell : lmono_normals_default_cell(radius), max_rings);
+    if (!s) throw std::runtime_error(std::string("lmono_normals_create: ") + lmono_last_error(hip_.get()));
+    nrm_ = std::shared_ptr<lmono_normals>(s, lmono_normals_destroy);
+}
+
+void MapBuilder::voxelNormals(std::vector<lmono_point_rgb> &points, std::vector<lmono_normal> &normals)
+{
+    points.clear(); normals.clear();
+    if (!nrm_) throw std::runtime_error("MapBuilder::voxelNormals: setNormals first");
+    lmono_normals *s = nrm_.get();
+    hip_.check(lmono_normals_compute_map(hip_.get(), s, vm_.get(), nullptr, nullptr), "lmono_normals_compute_map");
+    const int64_t n = lmono_normals_read(hip_.get(), s, nullptr, nullptr, 0);
+    hip_.check(n < 0 ? (int)n : 0, "lmono_normals_read");
+    points.resize((size_t)n); normals.resize((size_t)n);
+    if (n == 0) return;
+    hip_.check(lmono_normals_read(hip_.get(), s, normals.data(), nullptr, n) < 0 ? -1 : 0, "lmono_normals_read");
+    hip_.check(lmono_normals_cloud(hip_.get(), s, points.data(), n) < 0 ? -1 : 0, "lmono_normals_cloud");
+}
+
 std::vector<lmono_point_rgb> MapBuilder::voxelMap()
 {
     std::vector<lmono_point_rgb> out;

@@ -115,6 +115,55 @@ def read_ply_binary(path):
     return out
 
 
+_PLY_VERTEX_NORMAL = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("red", "u1"), ("green", "u1"), ("blue", "u1"),
+                               ("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4"), ("curvature", "<f4")])
+_NORMAL = np.dtype([("nx", np.float32), ("ny", np.float32), ("nz", np.float32), ("curvature", np.float32)])
+
+
+def write_ply_binary_normals(path, pts, normals):
+    """A coloured cloud with its surface normals: vertex x y z float, red green blue uchar, nx ny nz curvature float -- the
+    property names MeshLab and CloudCompare read; no other element.  pts: POINT_RGB records, normals: one (nx, ny, nz, curvature) record per
+    point (lmono_amd.NORMAL).  A point without a normal keeps its NaNs."""
+    pts = np.ascontiguousarray(pts, POINT_RGB)
+    normals = np.ascontiguousarray(normals, _NORMAL)
+    n = len(pts)
+    if len(normals) != n:
+        raise ValueError("one normal record per point")
+    head = "ply\nformat binary_little_endian 1.0\ncomment lmono surface normals\nelement vertex %d\n" % n
+    head += "property float x\nproperty float y\nproperty float z\nproperty uchar red\nproperty uchar green\nproperty uchar blue\n"
+    head += "property float nx\nproperty float ny\nproperty float nz\nproperty float curvature\nend_header\n"
+    v = np.zeros(n, _PLY_VERTEX_NORMAL)
+    v["x"], v["y"], v["z"] = pts["x"], pts["y"], pts["z"]
+    v["red"] = (pts["bgra"] >> 16) & 0xff; v["green"] = (pts["bgra"] >> 8) & 0xff; v["blue"] = pts["bgra"] & 0xff
+    for k in ("nx", "ny", "nz", "curvature"):
+        v[k] = normals[k]
+    with open(path, "wb") as f:
+        f.write(head.encode("ascii"))
+        f.write(v.tobytes())
+
+
+def read_ply_binary_normals(path):
+    """-> (POINT_RGB records, (nx, ny, nz, curvature) records) of a file write_ply_binary_normals (or the map_build program) wrote."""
+    with open(path, "rb") as f:
+        raw = f.read()
+    end = raw.index(b"end_header\n") + len(b"end_header\n")
+    head = raw[:end].decode("ascii").split("\n")
+    if "format binary_little_endian 1.0" not in head:
+        raise ValueError("not a binary little-endian PLY: " + path)
+    props = [l.split()[1:] for l in head if l.startswith("property ")]
+    if props != [["uchar" if t == "u1" else "float", k] for k, (t, _) in ((k, _PLY_VERTEX_NORMAL.fields[k]) for k in _PLY_VERTEX_NORMAL.names)]:
+        raise ValueError("not a cloud with normals (x y z red green blue nx ny nz curvature): " + path)
+    n = [int(l.split()[2]) for l in head if l.startswith("element vertex")][0]
+    v = np.frombuffer(raw, _PLY_VERTEX_NORMAL, n, end)
+    pts = np.zeros(n, POINT_RGB)
+    pts["x"], pts["y"], pts["z"] = v["x"], v["y"], v["z"]
+    pts["bgra"] = v["blue"].astype(np.uint32) | v["green"].astype(np.uint32) << 8 | v["red"].astype(np.uint32) << 16 | 0xff000000
+    normals = np.zeros(n, _NORMAL)
+    for k in ("nx", "ny", "nz", "curvature"):
+        normals[k] = v[k]
+    return pts, normals
+
+
 def format_mapping_line(stamp, toc_ms):
     """map_build_node.cc:230: fprintf(mapping_recorder, "%f %f \\n", stamp, toc)."""
     return "%f %f \n" % (stamp, toc_ms)

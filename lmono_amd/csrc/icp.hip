@@ -3,14 +3,7 @@
 // stage between the outlier filter and the voxel map.  The arithmetic is icp.hpp; this file is how the neighbours are found and the sums formed.
 // Every kernel takes blockIdx.y = stream over an array of jobs; none waits on another workgroup.
 //
-// A target is built once (five launches) and serves every align until the next one:
-//   k_icp_tclear    empties the cell table (open addressing over a power of two >= 2 n of 64-bit keys, as the outlier filter's) and the target's words.
-//   k_icp_tminmax   min and max of the valid points per axis: integer atomics on the icp_ord keys, exact in any order.
-//   k_icp_tcells    the origin from those words (the same bits on every thread); per point validity, span and key; the cell is claimed with a
-//                   64-bit compare-and-swap, one atomic add on the cell's count gives the point its rank in the cell.
-//   k_icp_toffsets  a prefix over the occupied cells in whatever order the workgroups arrive (one atomic per workgroup).
-//   k_icp_tscatter  copies xyz cell by cell.  The order inside a cell and the order of the cells differ from run to run; nothing downstream
-//                   depends on them: the neighbour is selected by value and every sum is an integer.
+// A target is the grid of the target cloud, with an origin (cell_grid.hip); it is built once and serves every align until the next one.
 // An align is k_icp_prepare, then max_iter pairs of k_icp_step and k_icp_solve, then k_icp_apply:
 //   k_icp_prepare   guess, u and the usable flag per source point.
 //   k_icp_step      the hot kernel: one source point per thread.  q under the stream's state, its cell, then ring by ring the cells of Chebyshev
@@ -22,27 +15,14 @@
 //   k_icp_apply     the aligned cloud under the final state.
 // k_icp_step and k_icp_solve return at once for a stream whose done word is set, so the result does not depend on how many pairs the host enqueues.
 #pragma once
-#include "common.hpp"
-#include "colour.hip"
-#include "sor.hip"
-#include "voxel_map.hip"
+#include "cell_grid.hip"
 #include "icp.hpp"
 
 namespace lmono {
 
 constexpr int kIcpT = 256;                // threads of every kernel here but k_icp_solve
-static_assert(kIcpT == kSorT, "k_icp_toffsets uses sor_block_scan, which is written for kSorT threads");
 
-struct IcpPt { float x, y, z; unsigned pad; };
 struct IcpU { float x, y, z; unsigned usable; };
-
-// the words of a target
-struct IcpTgt {
-    unsigned omin[3], omax[3];             // icp_ord keys over the valid points
-    unsigned rejected, alloc;              // target points invalid or out of span; points placed by k_icp_toffsets
-    float o[3];
-    unsigned n_vox;                        // records written by k_icp_from_voxels
-};
 
 // what an align keeps per stream on the device
 struct IcpDev {
@@ -52,17 +32,8 @@ struct IcpDev {
 };
 
 struct IcpJob {
-    // target
-    const PtRgb *tpts;
-    long long tn;
-    unsigned long long *tkey;
-    unsigned *tcnt, *toff;
-    unsigned tmask;
-    unsigned *tslot, *trank;
-    IcpPt *tsorted;
-    IcpTgt *tg;
-    float h, inv, D2;
-    int rings;
+    CellView g;                            // the target
+    float D2;
     // source
     const PtRgb *pts;
     long long n;
@@ -77,142 +48,7 @@ struct IcpJob {
     double G[12];
 };
 
-static_assert(sizeof(IcpPt) == 16 && sizeof(IcpU) == 16, "icp layouts");
-
-__global__ __launch_bounds__(kIcpT) void k_icp_tclear(const IcpJob *jobs)
-{
-    const IcpJob &j = jobs[blockIdx.y];
-    const unsigned long long s = (unsigned long long)blockIdx.x * kIcpT + threadIdx.x;
-    if (s == 0) {
-        IcpTgt t;
-        for (int a = 0; a < 3; a++) { t.omin[a] = 0xffffffffu; t.omax[a] = 0u; t.o[a] = 0.0f; }
-        t.rejected = 0; t.alloc = 0; t.n_vox = j.tg->n_vox;
-        *j.tg = t;
-    }
-    if (s > j.tmask) return;
-    j.tkey[s] = kVmEmpty;
-    j.tcnt[s] = 0;
-}
-
-__global__ __launch_bounds__(kIcpT) void k_icp_tminmax(const IcpJob *jobs)
-{
-    const IcpJob &j = jobs[blockIdx.y];
-    const long long i = (long long)blockIdx.x * kIcpT + threadIdx.x;
-    if ((long long)blockIdx.x * kIcpT >= j.tn) return;
-    __shared__ unsigned l_min[3], l_max[3];
-    if (threadIdx.x < 3) { l_min[threadIdx.x] = 0xffffffffu; l_max[threadIdx.x] = 0u; }
-    __syncthreads();
-    if (i < j.tn) {
-        const PtRgb pt = j.tpts[i];
-        uint64_t key;
-        int c[3];
-        if (sor_cell(pt.x, pt.y, pt.z, j.inv, key, c)) {
-            const unsigned k[3] = { icp_ord(pt.x), icp_ord(pt.y), icp_ord(pt.z) };
-            for (int a = 0; a < 3; a++) { atomicMin(&l_min[a], k[a]); atomicMax(&l_max[a], k[a]); }
-        }
-    }
-    __syncthreads();
-    if (threadIdx.x < 3 && l_min[threadIdx.x] <= l_max[threadIdx.x]) {
-        atomicMin(&j.tg->omin[threadIdx.x], l_min[threadIdx.x]);
-        atomicMax(&j.tg->omax[threadIdx.x], l_max[threadIdx.x]);
-    }
-}
-
-// the origin from the target's min / max words; 0 when no point is valid
-__device__ inline void icp_tgt_origin(const IcpTgt *tg, float o[3])
-{
-    for (int a = 0; a < 3; a++) {
-        const unsigned mn = tg->omin[a], mx = tg->omax[a];
-        o[a] = mn <= mx ? icp_origin(icp_unord(mn), icp_unord(mx)) : 0.0f;
-    }
-}
-
-// slot of `key`, claimed if new.  The table has at least 2 n slots for at most n keys: the probe always ends early
-__device__ inline unsigned icp_claim(const IcpJob &j, uint64_t key)
-{
-    unsigned h = (unsigned)vm_mix(key) & j.tmask;
-    for (unsigned probe = 0; probe <= j.tmask; probe++, h = (h + 1) & j.tmask) {
-        unsigned long long k = __hip_atomic_load(&j.tkey[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (k == kVmEmpty) k = atomicCAS(&j.tkey[h], (unsigned long long)kVmEmpty, (unsigned long long)key);
-        if (k == kVmEmpty || k == key) return h;
-    }
-    return kSorNoSlot;
-}
-
-// slot of `key` in the finished table, kSorNoSlot when no target point lies in that cell
-__device__ inline unsigned icp_find(const IcpJob &j, uint64_t key)
-{
-    unsigned h = (unsigned)vm_mix(key) & j.tmask;
-    for (unsigned probe = 0; probe <= j.tmask; probe++, h = (h + 1) & j.tmask) {
-        const unsigned long long k = j.tkey[h];
-        if (k == key) return h;
-        if (k == kVmEmpty) return kSorNoSlot;
-    }
-    return kSorNoSlot;
-}
-
-__global__ __launch_bounds__(kIcpT) void k_icp_tcells(const IcpJob *jobs)
-{
-    const IcpJob &j = jobs[blockIdx.y];
-    const long long i = (long long)blockIdx.x * kIcpT + threadIdx.x;
-    if ((long long)blockIdx.x * kIcpT >= j.tn) return;
-    __shared__ unsigned l_rej;
-    if (threadIdx.x == 0) l_rej = 0;
-    __syncthreads();
-    float o[3];
-    icp_tgt_origin(j.tg, o);
-    if (i == 0) for (int a = 0; a < 3; a++) j.tg->o[a] = o[a];
-    if (i < j.tn) {
-        const PtRgb pt = j.tpts[i];
-        uint64_t key = kVmEmpty;
-        int c[3];
-        unsigned slot = kSorNoSlot;
-        if (sor_cell(pt.x, pt.y, pt.z, j.inv, key, c) && icp_in_span(pt.x - o[0]) && icp_in_span(pt.y - o[1]) && icp_in_span(pt.z - o[2])) slot = icp_claim(j, key);
-        j.tslot[i] = slot;
-        if (slot == kSorNoSlot) atomicAdd(&l_rej, 1u);
-        else j.trank[i] = atomicAdd(&j.tcnt[slot], 1u);
-    }
-    __syncthreads();
-    if (threadIdx.x == 0 && l_rej) atomicAdd(&j.tg->rejected, l_rej);
-}
-
-__global__ __launch_bounds__(kIcpT) void k_icp_toffsets(const IcpJob *jobs)
-{
-    const IcpJob &j = jobs[blockIdx.y];
-    const unsigned long long s = (unsigned long long)blockIdx.x * kIcpT + threadIdx.x;
-    if (j.tn == 0 || (unsigned long long)blockIdx.x * kIcpT > j.tmask) return;
-    __shared__ unsigned long long wsum[kIcpT / 64], l_base;
-    const unsigned c = s <= j.tmask ? j.tcnt[s] : 0u;
-    unsigned long long total;
-    const unsigned long long ex = sor_block_scan((unsigned long long)c, wsum, total);
-    if (threadIdx.x == 0 && total) l_base = atomicAdd(&j.tg->alloc, (unsigned)total);
-    __syncthreads();
-    if (c) j.toff[s] = (unsigned)(l_base + ex);
-}
-
-__global__ __launch_bounds__(kIcpT) void k_icp_tscatter(const IcpJob *jobs)
-{
-    const IcpJob &j = jobs[blockIdx.y];
-    const long long i = (long long)blockIdx.x * kIcpT + threadIdx.x;
-    if (i >= j.tn) return;
-    const unsigned slot = j.tslot[i];
-    if (slot == kSorNoSlot) return;
-    const PtRgb pt = j.tpts[i];
-    IcpPt p;
-    p.x = pt.x; p.y = pt.y; p.z = pt.z; p.pad = 0;
-    j.tsorted[j.toff[slot] + j.trank[i]] = p;          // below the number of placed points, which is at most tn
-}
-
-// every occupied voxel's output point (vm_point, what lmono_voxel_map_read gives) into out, in any order; n counts them, cap bounds the writes
-__global__ __launch_bounds__(kIcpT) void k_icp_from_voxels(const VmRec *rec, unsigned long long slots, float leaf, PtRgb *out, unsigned cap, unsigned *n)
-{
-    const unsigned long long s = (unsigned long long)blockIdx.x * kIcpT + threadIdx.x;
-    if (s >= slots) return;
-    const VmRec r = rec[s];
-    if (!vm_occupied(r)) return;
-    const unsigned at = atomicAdd(n, 1u);
-    if (at < cap) out[at] = vm_out_point(r, leaf);
-}
+static_assert(sizeof(IcpU) == 16, "icp layouts");
 
 __global__ __launch_bounds__(kIcpT) void k_icp_prepare(const IcpJob *jobs)
 {
@@ -224,7 +60,7 @@ __global__ __launch_bounds__(kIcpT) void k_icp_prepare(const IcpJob *jobs)
     __syncthreads();
     if (i < j.n) {
         const PtRgb pt = j.pts[i];
-        const float *o = j.tg->o;
+        const float *o = j.g.w->o;
         IcpU u;
         u.x = icp_guess_axis(j.G, pt.x, pt.y, pt.z) - o[0];
         u.y = icp_guess_axis(j.G + 4, pt.x, pt.y, pt.z) - o[1];
@@ -253,33 +89,33 @@ __global__ __launch_bounds__(kIcpT) void k_icp_step(const IcpJob *jobs)
     if (i < j.n) {
         const IcpU u = j.u[i];
         float best = INFINITY, bx = 0.0f, by = 0.0f, bz = 0.0f;
-        const float *o = j.tg->o;
+        const float *o = j.g.w->o;
         const float o0 = o[0], o1 = o[1], o2 = o[2];
         uint64_t key;
         int c[3];
         if (u.usable) {
             const float qx = icp_q_axis(st.R, st.tau[0], o0, u.x, u.y, u.z), qy = icp_q_axis(st.R + 3, st.tau[1], o1, u.x, u.y, u.z),
                         qz = icp_q_axis(st.R + 6, st.tau[2], o2, u.x, u.y, u.z);
-            if (sor_cell(qx, qy, qz, j.inv, key, c)) {
+            if (sor_cell(qx, qy, qz, j.g.inv, key, c)) {
                 constexpr int L = 1 << 20;
-                for (int r = 1; r <= j.rings; r++) {
+                for (int r = 1; r <= j.g.rings; r++) {
                     for (int dz = -r; dz <= r; dz++)
                         for (int dy = -r; dy <= r; dy++)
                             for (int dx = -r; dx <= r; dx++) {
                                 if (r > 1 && abs(dx) < r && abs(dy) < r && abs(dz) < r) continue;      // inside: seen at the rings before
                                 const int x = c[0] + dx, y = c[1] + dy, z = c[2] + dz;
                                 if (x < -L || x >= L || y < -L || y >= L || z < -L || z >= L) continue;
-                                const unsigned slot = icp_find(j, vm_key(x, y, z));
-                                if (slot == kSorNoSlot) continue;
-                                const unsigned n = j.tcnt[slot];
-                                const IcpPt *p = j.tsorted + j.toff[slot];
+                                const unsigned slot = cellgrid_find(j.g, vm_key(x, y, z));
+                                if (slot == kCellNoSlot) continue;
+                                const unsigned n = j.g.cnt[slot];
+                                const CellPt *p = j.g.sorted + j.g.off[slot];
                                 for (unsigned e = 0; e < n; e++) {
-                                    const IcpPt m = p[e];
+                                    const CellPt m = p[e];
                                     const float d2 = sor_d2(qx, qy, qz, m.x, m.y, m.z);
                                     if (icp_better(d2, m.x, m.y, m.z, best, bx, by, bz)) { best = d2; bx = m.x; by = m.y; bz = m.z; }
                                 }
                             }
-                    if (best <= sor_rho2(r, j.h)) break;
+                    if (best <= sor_rho2(r, j.g.h)) break;
                 }
                 acc = best <= j.D2;
             }
@@ -337,7 +173,7 @@ __global__ __launch_bounds__(kIcpT) void k_icp_apply(const IcpJob *jobs)
     if (i >= j.n) return;
     const IcpState &st = j.dev->st;
     const IcpU u = j.u[i];
-    const float *o = j.tg->o;
+    const float *o = j.g.w->o;
     PtRgb p = j.pts[i];
     p.x = icp_q_axis(st.R, st.tau[0], o[0], u.x, u.y, u.z);
     p.y = icp_q_axis(st.R + 3, st.tau[1], o[1], u.x, u.y, u.z);

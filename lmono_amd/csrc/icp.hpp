@@ -7,7 +7,7 @@
 //
 // Target.  A point is valid iff sor_cell accepts it at inv = 1.0f / h.  The origin o[a] = (min_a + max_a) * 0.5f over the valid points, min and max in
 // the order of icp_ord (the float order, with -0 below +0, so that o has one definition).  w = m - o; a valid point with some |w_a| >= 2048 is out of
-// span: counted as rejected, never a neighbour.  iw_a = (int64)((double)w_a * 65536.0).
+// span: counted as rejected, never a neighbour (these rules are the grid's: cell_grid.hpp).  iw_a = (int64)((double)w_a * 65536.0).
 // Source.  p0 = (float)(G p) (icp_guess_axis: fp64, fixed order), u = p0 - o; usable iff every u_a is finite and |u_a| < 2048; iu as iw.
 // State.  R (fp64, row-major) and tau (fp64) in origin-centred coordinates: x' - o = R (x - o) + tau.  They start at I and 0.
 // Iteration k.  q = (float)((double)o + (R (double)u + tau)) (icp_q_axis).  q must be valid by sor_cell, else the point is unmatched.  Its
@@ -30,13 +30,12 @@
 #else
 #include "track_reject.hip"
 #endif
-#include "sor.hpp"
+#include "cell_grid.hpp"
 
 namespace lmono {
 
 constexpr int kIcpSweeps = 8;                   // cyclic Jacobi sweeps of the 4 x 4 problem (the off-diagonal is exactly 0 on the cases of tests/test_icp_ref_cpu.py)
 constexpr float kIcpMaxCorr = 16.0f;
-constexpr float kIcpSpan = 2048.0f;             // |w_a|, |u_a| stay below it: 2^-16 m fixed point in 28 bits
 constexpr int kIcpMaxIter = 65536;              // of a handle: the history is kept for every iteration
 constexpr int kIcpWords = 26;                   // of IcpSums
 
@@ -51,24 +50,7 @@ struct IcpState {
     int k, status, done, pad;                   // k: iterations run
 };
 
-// the order of min / max for the origin: float order with -0 below +0, as unsigned integers
-LMONO_VM_HD uint32_t icp_ord(float x)
-{
-    uint32_t b;
-    __builtin_memcpy(&b, &x, 4);
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-LMONO_VM_HD float icp_unord(uint32_t k)
-{
-    const uint32_t b = (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k;
-    float x;
-    __builtin_memcpy(&x, &b, 4);
-    return x;
-}
-LMONO_VM_HD float icp_origin(float mn, float mx) { return (mn + mx) * 0.5f; }
-
-// centred coordinate in range: finite and |c| < 2048
-LMONO_VM_HD bool icp_in_span(float c) { return c > -kIcpSpan && c < kIcpSpan; }
+// a centred, in-span coordinate (icp_in_span) in units of 2^-16 m
 LMONO_VM_HD long long icp_fix(float c) { return (long long)((double)c * 65536.0); }
 
 // one coordinate of G p: row of a row-major 3 x 4 fp64 transform

@@ -6,21 +6,17 @@
 struct lmono_icp {
     lmono_ctx *ctx = nullptr;
     int64_t max_src = 0, max_tgt = 0;
-    float D = 0.0f, D2 = 0.0f, h = 0.0f, inv = 0.0f;
-    int rings = 0, max_iter = 0, poll = 2;       // poll: pairs of launches between two reads of the done words
+    float D = 0.0f, D2 = 0.0f;
+    int max_iter = 0, poll = 2;                  // poll: pairs of launches between two reads of the done words
     double eps = 0.0, mse_eps = 0.0;
     double G[12] = { 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0 };
-    uint64_t slots = 0;                          // of the allocation; a target uses the smallest power of two >= 2 n (at least 64)
     DevOwner mem;
-    // the target: cell table, points cell by cell, words; tpts: staging of the host-buffer and the voxel-map entries
-    unsigned long long *tkey = nullptr;
-    unsigned *tcnt = nullptr, *toff = nullptr, *tslot = nullptr, *trank = nullptr;
-    IcpPt *tsorted = nullptr;
-    IcpTgt *tg = nullptr;
+    // the target: its grid (with an origin); tpts: staging of the host-buffer and the voxel-map entries, n_vox: the points the latter wrote
+    CellGrid grid;
     PtRgb *tpts = nullptr;
+    unsigned *n_vox = nullptr;
     bool has_target = false;
     int64_t tn = 0, t_rejected = 0;
-    uint64_t t_slots = 64;
     float o[3] = { 0.0f, 0.0f, 0.0f };
     // the source and the last align
     PtRgb *spts = nullptr, *out = nullptr;       // spts: staging of the host-buffer entry
@@ -59,14 +55,11 @@ extern "C" lmono_icp *lmono_icp_create(lmono_ctx *c, int64_t max_source_points, 
     lmono_icp *s = new lmono_icp();
     s->ctx = c;
     s->max_src = max_source_points; s->max_tgt = max_target_points;
-    s->D = max_corr; s->D2 = max_corr * max_corr; s->h = cell; s->inv = 1.0f / cell; s->rings = max_rings; s->max_iter = max_iter; s->eps = eps; s->mse_eps = mse_eps;
+    s->D = max_corr; s->D2 = max_corr * max_corr; s->max_iter = max_iter; s->eps = eps; s->mse_eps = mse_eps;
     icp_state_init(s->last);
-    s->slots = 64;
-    while (s->slots < 2 * (uint64_t)max_target_points) s->slots <<= 1;
     const size_t ns = (size_t)max_source_points, nt = (size_t)max_target_points;
-    const bool ok = s->mem.alloc(s->tkey, (size_t)s->slots) && s->mem.alloc(s->tcnt, (size_t)s->slots) && s->mem.alloc(s->toff, (size_t)s->slots) && s->mem.alloc(s->tslot, nt) &&
-                    s->mem.alloc(s->trank, nt) && s->mem.alloc(s->tsorted, nt) && s->mem.alloc_zero(s->tg, 1) && s->mem.alloc(s->tpts, nt) && s->mem.alloc(s->spts, ns) &&
-                    s->mem.alloc(s->out, ns) && s->mem.alloc(s->u, ns) && s->mem.alloc(s->d2, ns) && s->mem.alloc_zero(s->dev, 1) && s->mem.alloc(s->hist, 2 * (size_t)max_iter);
+    const bool ok = s->grid.alloc(s->mem, max_target_points, cell, max_rings, /*work_list=*/false) && s->mem.alloc_zero(s->n_vox, 1) && s->mem.alloc(s->tpts, nt) &&
+                    s->mem.alloc(s->spts, ns) && s->mem.alloc(s->out, ns) && s->mem.alloc(s->u, ns) && s->mem.alloc(s->d2, ns) && s->mem.alloc_zero(s->dev, 1) && s->mem.alloc(s->hist, 2 * (size_t)max_iter);
     if (!ok) { c->err = "lmono_icp_create: device allocation failed"; lmono_icp_destroy(s); return nullptr; }
     return s;
 }
@@ -91,10 +84,8 @@ extern "C" int lmono_icp_set_poll_interval(lmono_ctx *c, lmono_icp *s, int pairs
 // the job of one stream; the source half is filled by the align
 static void icp_job_target(const lmono_icp *s, IcpJob &j)
 {
-    j.tpts = nullptr; j.tn = s->tn;
-    j.tkey = s->tkey; j.tcnt = s->tcnt; j.toff = s->toff; j.tmask = (unsigned)(s->t_slots - 1);
-    j.tslot = s->tslot; j.trank = s->trank; j.tsorted = s->tsorted; j.tg = s->tg;
-    j.h = s->h; j.inv = s->inv; j.D2 = s->D2; j.rings = s->rings;
+    j.g = s->grid.view(nullptr, s->tn);
+    j.D2 = s->D2;
     j.pts = nullptr; j.n = 0; j.u = s->u; j.d2 = s->d2; j.out = s->out; j.dev = s->dev; j.hist = s->hist; j.done = nullptr;
     j.max_iter = s->max_iter; j.eps = s->eps; j.mse_eps = s->mse_eps;
     std::memcpy(j.G, s->G, sizeof j.G);
@@ -106,27 +97,13 @@ static int icp_build_target(lmono_ctx *c, const char *who, lmono_icp *s, const P
     s->has_target = false;
     if (!job_table(s->mem, s->jobs, s->results, s->jobs_cap, 1, 1)) { c->err = std::string(who) + ": job table allocation failed"; return LMONO_ENOMEM; }
     s->tn = n;
-    s->t_slots = 64;
-    while (s->t_slots < 2 * (uint64_t)n) s->t_slots <<= 1;      // <= s->slots, since n <= max_tgt
     IcpJob j;
     icp_job_target(s, j);
-    j.tpts = pts_d;
+    j.g.pts = pts_d;
     HIP_TRY(c, hipMemcpyAsync(s->jobs, &j, sizeof j, hipMemcpyHostToDevice, c->stream));
-    const dim3 g_slots((unsigned)((s->t_slots + kIcpT - 1) / kIcpT), 1), g_pts((unsigned)((n + kIcpT - 1) / kIcpT), 1);
-    k_icp_tclear<<<g_slots, kIcpT, 0, c->stream>>>(s->jobs);
-    if (int rc = check_launch(c, "k_icp_tclear")) return rc;
-    if (n > 0) {
-        k_icp_tminmax<<<g_pts, kIcpT, 0, c->stream>>>(s->jobs);
-        if (int rc = check_launch(c, "k_icp_tminmax")) return rc;
-        k_icp_tcells<<<g_pts, kIcpT, 0, c->stream>>>(s->jobs);
-        if (int rc = check_launch(c, "k_icp_tcells")) return rc;
-        k_icp_toffsets<<<g_slots, kIcpT, 0, c->stream>>>(s->jobs);
-        if (int rc = check_launch(c, "k_icp_toffsets")) return rc;
-        k_icp_tscatter<<<g_pts, kIcpT, 0, c->stream>>>(s->jobs);
-        if (int rc = check_launch(c, "k_icp_tscatter")) return rc;
-    }
-    IcpTgt t;
-    HIP_TRY(c, hipMemcpyAsync(&t, s->tg, sizeof t, hipMemcpyDeviceToHost, c->stream));
+    if (int rc = cellgrid_build</*kOrigin=*/true>(c, s->jobs, 1, n)) return rc;
+    CellWords t;
+    HIP_TRY(c, hipMemcpyAsync(&t, s->grid.words, sizeof t, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     if ((int64_t)t.alloc + (int64_t)t.rejected != n) { c->err = std::string(who) + ": the target's placed and rejected points do not add up to its size"; return LMONO_ENODEV; }
     for (int a = 0; a < 3; a++) s->o[a] = t.o[a];
@@ -156,15 +133,11 @@ extern "C" int lmono_icp_set_target_map(lmono_ctx *c, lmono_icp *s, lmono_voxel_
 {
     if (!c || !s || s->ctx != c || !m || m->ctx != c) return LMONO_EINVAL;
     if (m->n_vox > s->max_tgt) { c->err = "lmono_icp_set_target_map: more voxels than the aligner's max_target_points"; return LMONO_ECAPACITY; }
-    if (m->n_vox > 0) {
-        HIP_TRY(c, hipMemsetAsync(&s->tg->n_vox, 0, sizeof(unsigned), c->stream));
-        k_icp_from_voxels<<<(unsigned)((m->slots + kIcpT - 1) / kIcpT), kIcpT, 0, c->stream>>>(m->rec, m->slots, m->leaf, s->tpts, (unsigned)m->n_vox, &s->tg->n_vox);
-        if (int rc = check_launch(c, "k_icp_from_voxels")) return rc;
-    }
+    if (int rc = m->n_vox > 0 ? vm_enqueue_points(c, m, s->tpts, s->n_vox) : LMONO_OK) return rc;
     if (int rc = icp_build_target(c, "lmono_icp_set_target_map", s, s->tpts, m->n_vox)) return rc;
     if (m->n_vox > 0) {
         unsigned found = 0;
-        HIP_TRY(c, hipMemcpy(&found, &s->tg->n_vox, sizeof found, hipMemcpyDeviceToHost));
+        HIP_TRY(c, hipMemcpy(&found, s->n_vox, sizeof found, hipMemcpyDeviceToHost));
         if ((int64_t)found != m->n_vox) { s->has_target = false; c->err = "lmono_icp_set_target_map: the table's occupied records do not match the map's size"; return LMONO_ENODEV; }
     }
     return LMONO_OK;
@@ -278,13 +251,8 @@ extern "C" int lmono_icp_align_frames(lmono_ctx *c, int n, lmono_icp *const *icp
     std::vector<const PtRgb *> pts((size_t)n);
     std::vector<int64_t> ns((size_t)n);
     for (int s = 0; s < n; s++) {
-        const int fs = batch_handle_fault(c, s, icps), fb = batch_handle_fault(c, s, mbs);
-        if (fs == kHandleForeign || fb == kHandleForeign) { c->err = "lmono_icp_align_frames: bad stream arguments"; return LMONO_EINVAL; }
-        if (fs == kHandleRepeated || fb == kHandleRepeated) { c->err = "lmono_icp_align_frames: aligners and map builders must be distinct"; return LMONO_EINVAL; }
-        const lmono_map_builder *b = mbs[s];
-        if (b->last_off + b->last_n > b->map_n) { c->err = "lmono_icp_align_frames: the world cloud of a builder's last frame is no longer in rgb_map"; return LMONO_EINVAL; }
-        pts[(size_t)s] = b->map + b->last_off;
-        ns[(size_t)s] = b->last_n;
+        if (!batch_pair_ok(c, "lmono_icp_align_frames", "aligners and map builders", s, icps, mbs)) return LMONO_EINVAL;
+        if (!builder_last_cloud(c, "lmono_icp_align_frames", mbs[s], pts[(size_t)s], ns[(size_t)s])) return LMONO_EINVAL;
     }
     return icp_align_batch(c, "lmono_icp_align_frames", n, icps, pts.data(), ns.data(), stats);
 }
@@ -295,9 +263,7 @@ extern "C" int lmono_icp_align_filtered(lmono_ctx *c, int n, lmono_icp *const *i
     std::vector<const PtRgb *> pts((size_t)n);
     std::vector<int64_t> ns((size_t)n);
     for (int s = 0; s < n; s++) {
-        const int fs = batch_handle_fault(c, s, icps), ff = batch_handle_fault(c, s, sors);
-        if (fs == kHandleForeign || ff == kHandleForeign) { c->err = "lmono_icp_align_filtered: bad stream arguments"; return LMONO_EINVAL; }
-        if (fs == kHandleRepeated || ff == kHandleRepeated) { c->err = "lmono_icp_align_filtered: aligners and filters must be distinct"; return LMONO_EINVAL; }
+        if (!batch_pair_ok(c, "lmono_icp_align_filtered", "aligners and filters", s, icps, sors)) return LMONO_EINVAL;
         pts[(size_t)s] = sors[s]->out;
         ns[(size_t)s] = sors[s]->last_kept;
     }
@@ -316,12 +282,7 @@ extern "C" int64_t lmono_icp_cloud(lmono_ctx *c, lmono_icp *s, lmono_point_rgb *
 {
     if (!c || !s || s->ctx != c) return LMONO_EINVAL;
     if (!out_h) return s->last_n;
-    if (cap < s->last_n) { c->err = "lmono_icp_cloud: output capacity too small"; return LMONO_ECAPACITY; }
-    if (s->last_n > 0) {
-        HIP_TRY(c, hipMemcpyAsync(out_h, s->out, sizeof(PtRgb) * (size_t)s->last_n, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-    }
-    return s->last_n;
+    return read_last(c, "lmono_icp_cloud", s->last_n, cap, out_h, s->out, sizeof(PtRgb));
 }
 
 extern "C" int64_t lmono_icp_history(lmono_ctx *c, lmono_icp *s, int64_t *n_e_h, int64_t cap)
@@ -329,24 +290,14 @@ extern "C" int64_t lmono_icp_history(lmono_ctx *c, lmono_icp *s, int64_t *n_e_h,
     if (!c || !s || s->ctx != c) return LMONO_EINVAL;
     const int64_t k = s->last.k;
     if (!n_e_h) return k;
-    if (cap < k) { c->err = "lmono_icp_history: output capacity too small"; return LMONO_ECAPACITY; }
-    if (k > 0) {
-        HIP_TRY(c, hipMemcpyAsync(n_e_h, s->hist, sizeof(int64_t) * 2 * (size_t)k, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-    }
-    return k;
+    return read_last(c, "lmono_icp_history", k, cap, n_e_h, s->hist, 2 * sizeof(int64_t));
 }
 
 extern "C" int64_t lmono_icp_distances(lmono_ctx *c, lmono_icp *s, float *d2_h, int64_t cap)
 {
     if (!c || !s || s->ctx != c) return LMONO_EINVAL;
     if (!d2_h) return s->last_n;
-    if (cap < s->last_n) { c->err = "lmono_icp_distances: output capacity too small"; return LMONO_ECAPACITY; }
-    if (s->last_n > 0) {
-        HIP_TRY(c, hipMemcpyAsync(d2_h, s->d2, sizeof(float) * (size_t)s->last_n, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-    }
-    return s->last_n;
+    return read_last(c, "lmono_icp_distances", s->last_n, cap, d2_h, s->d2, sizeof(float));
 }
 
 extern "C" int lmono_voxel_map_insert_aligned(lmono_ctx *c, int n, lmono_voxel_map *const *maps, lmono_icp *const *icps, int64_t *stats)
@@ -355,9 +306,7 @@ extern "C" int lmono_voxel_map_insert_aligned(lmono_ctx *c, int n, lmono_voxel_m
     std::vector<const PtRgb *> pts((size_t)n);
     std::vector<int64_t> ns((size_t)n);
     for (int s = 0; s < n; s++) {
-        const int fm = batch_handle_fault(c, s, maps), fs = batch_handle_fault(c, s, icps);
-        if (fm == kHandleForeign || fs == kHandleForeign) { c->err = "lmono_voxel_map_insert_aligned: bad stream arguments"; return LMONO_EINVAL; }
-        if (fm == kHandleRepeated || fs == kHandleRepeated) { c->err = "lmono_voxel_map_insert_aligned: maps and aligners must be distinct"; return LMONO_EINVAL; }
+        if (!batch_pair_ok(c, "lmono_voxel_map_insert_aligned", "maps and aligners", s, maps, icps)) return LMONO_EINVAL;
         pts[(size_t)s] = icps[s]->out;
         ns[(size_t)s] = icps[s]->last_n;
     }

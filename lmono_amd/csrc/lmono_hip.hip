@@ -347,6 +347,37 @@ template <typename H> static int batch_handle_fault(const lmono_ctx *c, int s, H
     return kHandleOk;
 }
 
+// the two handles of stream s of the batched call `who`, for the entry points that report both kinds alike; nouns: "filters and map builders"
+template <typename A, typename B> static bool batch_pair_ok(lmono_ctx *c, const char *who, const char *nouns, int s, A *const *as, B *const *bs)
+{
+    const int fa = batch_handle_fault(c, s, as), fb = batch_handle_fault(c, s, bs);
+    if (fa == kHandleForeign || fb == kHandleForeign) { c->err = std::string(who) + ": bad stream arguments"; return false; }
+    if (fa == kHandleRepeated || fb == kHandleRepeated) { c->err = std::string(who) + ": " + nouns + " must be distinct"; return false; }
+    return true;
+}
+
+// the world cloud of a map builder's last frame, as long as it is still in rgb_map (B: lmono_map_builder, defined in colour_abi.hip)
+template <typename B, typename P> static bool builder_last_cloud(lmono_ctx *c, const char *who, const B *b, const P *&pts, int64_t &n)
+{
+    if (b->last_off + b->last_n > b->map_n) { c->err = std::string(who) + ": the world cloud of a builder's last frame is no longer in rgb_map"; return false; }
+    pts = b->map + b->last_off; n = b->last_n;
+    return true;
+}
+
+// The last result of a handle into the caller's arrays: n items of up to two device arrays (a null destination is skipped), one synchronisation.
+// Returns n, or LMONO_ECAPACITY when cap < n
+static int64_t read_last(lmono_ctx *c, const char *who, int64_t n, int64_t cap, void *dst0, const void *src0, size_t item0, void *dst1 = nullptr, const void *src1 = nullptr,
+                         size_t item1 = 0)
+{
+    if (cap < n) { c->err = std::string(who) + ": output capacity too small"; return LMONO_ECAPACITY; }
+    if (n > 0) {
+        if (dst0) HIP_TRY(c, hipMemcpyAsync(dst0, src0, item0 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+        if (dst1) HIP_TRY(c, hipMemcpyAsync(dst1, src1, item1 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+    }
+    return n;
+}
+
 #include "lidar_abi.hip"
 #include "ba_abi.hip"
 #include "feat_abi.hip"

@@ -5,7 +5,7 @@
 // (build with -ffp-contract=off).  The definition is this project's own: a point's record is a pure function of the SET of input points and of
 // the point itself.  Parity with PCL is unpinned.
 //
-// Valid points, origin, span: the rules of the ICP's target (icp.hpp).  A point is valid iff sor_cell accepts it at inv = 1.0f / h; the origin
+// Valid points, origin, span: the rules of a grid with an origin (cell_grid.hpp), as the ICP's target.  A point is valid iff sor_cell accepts it at inv = 1.0f / h; the origin
 // o[a] = (min_a + max_a) * 0.5f over the valid points in the order of icp_ord; w = p - o; a valid point with some |w_a| >= 2048 is out of span.
 // An invalid or out-of-span point is rejected: counted, never a neighbour, and its record is four NaNs (kNrmNaN) with count 0.  iw_a = nrm_fix(w_a).
 // Neighbourhood of i: every non-rejected j, i itself and every duplicate included, with sor_d2(p_i, p_j) <= r * r in float32; N of them.
@@ -26,6 +26,7 @@
 // sor_rho(R, h) = (R - 0.25) h -- far above the float32 roundings of d2.  So every point outside the cube has d2 > sor_rho2(R, h), and with
 // sor_rho(R, h) >= r (float32 rounding is monotone: sor_rho2 >= r * r) the set { j : d2 <= r * r } lies inside the cube whole.
 #pragma once
+#include "cell_grid.hpp"
 #include "icp.hpp"
 
 namespace lmono {

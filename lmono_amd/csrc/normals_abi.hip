@@ -5,25 +5,22 @@
 struct lmono_normals {
     lmono_ctx *ctx = nullptr;
     int64_t max_points = 0;
-    float r = 0.0f, r2 = 0.0f, h = 0.0f, inv = 0.0f;
-    int rings = 0, min_nb = 0;
-    uint64_t slots = 0;                          // of the allocation; a cloud uses the smallest power of two >= 2 n (at least 64)
+    float r = 0.0f, r2 = 0.0f;
+    int min_nb = 0;
     DevOwner mem;
-    // the grid over the cloud (the ICP's target layout) and the cloud itself: every entry point brings its points into pts first
-    unsigned long long *tkey = nullptr;
-    unsigned *tcnt = nullptr, *toff = nullptr, *tslot = nullptr, *trank = nullptr;
-    IcpPt *tsorted = nullptr;
-    IcpTgt *tg = nullptr;
+    // the grid over the cloud (with an origin) and the cloud itself: every entry point brings its points into pts first; n_vox: the points
+    // compute_map wrote there
+    CellGrid grid;
     PtRgb *pts = nullptr;
+    unsigned *n_vox = nullptr;
     // the last result
     NrmRecord *rec = nullptr;
     unsigned *count = nullptr;
     NrmDev *dev = nullptr;
     int64_t last_n = 0, stats[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
-    // per-call job tables of a batch led by this handle
-    IcpJob *grid = nullptr;
+    // per-call job table of a batch led by this handle
     NrmJob *jobs = nullptr;
-    int grid_cap = 0, jobs_cap = 0;
+    int jobs_cap = 0;
 };
 
 extern "C" void lmono_normals_destroy(lmono_normals *s) { delete s; }
@@ -42,12 +39,9 @@ extern "C" lmono_normals *lmono_normals_create(lmono_ctx *c, int64_t max_points,
     lmono_normals *s = new lmono_normals();
     s->ctx = c;
     s->max_points = max_points;
-    s->r = radius; s->r2 = radius * radius; s->h = cell; s->inv = 1.0f / cell; s->rings = max_rings; s->min_nb = min_neighbours;
-    s->slots = 64;
-    while (s->slots < 2 * (uint64_t)max_points) s->slots <<= 1;
+    s->r = radius; s->r2 = radius * radius; s->min_nb = min_neighbours;
     const size_t n = (size_t)max_points;
-    const bool ok = s->mem.alloc(s->tkey, (size_t)s->slots) && s->mem.alloc(s->tcnt, (size_t)s->slots) && s->mem.alloc(s->toff, (size_t)s->slots) && s->mem.alloc(s->tslot, n) &&
-                    s->mem.alloc(s->trank, n) && s->mem.alloc(s->tsorted, n) && s->mem.alloc_zero(s->tg, 1) && s->mem.alloc(s->pts, n) && s->mem.alloc(s->rec, n) &&
+    const bool ok = s->grid.alloc(s->mem, max_points, cell, max_rings, /*work_list=*/false) && s->mem.alloc_zero(s->n_vox, 1) && s->mem.alloc(s->pts, n) && s->mem.alloc(s->rec, n) &&
                     s->mem.alloc(s->count, n) && s->mem.alloc_zero(s->dev, 1);
     if (!ok) { c->err = "lmono_normals_create: device allocation failed"; lmono_normals_destroy(s); return nullptr; }
     return s;
@@ -60,11 +54,10 @@ static bool nrm_viewpoints_ok(const float *vps, int n)
 }
 
 // one compute for n handles whose clouds of ns[s] points (ns[s] <= max_points) are in flight into their pts buffers; vps: [n][3] or nullptr.
-// One launch per phase for all streams: the five of the grid, k_nrm_compute, k_nrm_stats.  Ends synchronised.
+// One launch per phase for all streams: the five of the grid (cellgrid_build), k_nrm_compute, k_nrm_stats.  Ends synchronised.
 static int nrm_compute_batch(lmono_ctx *c, const char *who, int n, lmono_normals *const *hs, const int64_t *ns, const float *vps, int64_t *stats)
 {
     int64_t max_n = 0;
-    uint64_t max_slots = 64;
     // the handles show a result only once the call has ended well
     for (int s = 0; s < n; s++) {
         hs[s]->last_n = 0;
@@ -81,55 +74,33 @@ static int nrm_compute_batch(lmono_ctx *c, const char *who, int n, lmono_normals
     };
     if (max_n == 0) return finish();                            // nothing to do: no launch
     lmono_normals *lead = hs[0];
-    if (!lead->mem.grow_replace(lead->grid, lead->grid_cap, (size_t)n, /*floor=*/1) || !lead->mem.grow_replace(lead->jobs, lead->jobs_cap, (size_t)n, /*floor=*/1)) {
-        c->err = std::string(who) + ": job table allocation failed";
-        return LMONO_ENOMEM;
-    }
-    std::vector<IcpJob> grid((size_t)n);
+    if (!lead->mem.grow_replace(lead->jobs, lead->jobs_cap, (size_t)n, /*floor=*/1)) { c->err = std::string(who) + ": job table allocation failed"; return LMONO_ENOMEM; }
     std::vector<NrmJob> jobs((size_t)n);
     for (int s = 0; s < n; s++) {
         const lmono_normals *f = hs[s];
-        uint64_t slots = 64;
-        while (slots < 2 * (uint64_t)ns[s]) slots <<= 1;        // <= f->slots, since ns[s] <= max_points
-        max_slots = std::max(max_slots, slots);
-        IcpJob &g = grid[(size_t)s];
-        std::memset(&g, 0, sizeof g);                           // the source half of the job is not read by the target kernels
-        g.tpts = f->pts; g.tn = ns[s];
-        g.tkey = f->tkey; g.tcnt = f->tcnt; g.toff = f->toff; g.tmask = (unsigned)(slots - 1);
-        g.tslot = f->tslot; g.trank = f->trank; g.tsorted = f->tsorted; g.tg = f->tg;
-        g.h = f->h; g.inv = f->inv; g.D2 = f->r2; g.rings = f->rings;
         NrmJob &q = jobs[(size_t)s];
+        q.g = f->grid.view(f->pts, ns[s]);
         q.rec = f->rec; q.count = f->count; q.dev = f->dev; q.r2 = f->r2; q.min_nb = f->min_nb; q.has_vp = vps ? 1 : 0;
         for (int a = 0; a < 3; a++) q.vp[a] = vps ? vps[3 * s + a] : 0.0f;
     }
-    HIP_TRY(c, hipMemcpyAsync(lead->grid, grid.data(), sizeof(IcpJob) * (size_t)n, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipMemcpyAsync(lead->jobs, jobs.data(), sizeof(NrmJob) * (size_t)n, hipMemcpyHostToDevice, c->stream));
-    const dim3 g_slots((unsigned)((max_slots + kIcpT - 1) / kIcpT), (unsigned)n), g_pts((unsigned)((max_n + kIcpT - 1) / kIcpT), (unsigned)n);
-    k_icp_tclear<<<g_slots, kIcpT, 0, c->stream>>>(lead->grid);
-    if (int rc = check_launch(c, "k_icp_tclear")) return rc;
-    k_icp_tminmax<<<g_pts, kIcpT, 0, c->stream>>>(lead->grid);
-    if (int rc = check_launch(c, "k_icp_tminmax")) return rc;
-    k_icp_tcells<<<g_pts, kIcpT, 0, c->stream>>>(lead->grid);
-    if (int rc = check_launch(c, "k_icp_tcells")) return rc;
-    k_icp_toffsets<<<g_slots, kIcpT, 0, c->stream>>>(lead->grid);
-    if (int rc = check_launch(c, "k_icp_toffsets")) return rc;
-    k_icp_tscatter<<<g_pts, kIcpT, 0, c->stream>>>(lead->grid);
-    if (int rc = check_launch(c, "k_icp_tscatter")) return rc;
-    k_nrm_compute<<<g_pts, kNrmT, 0, c->stream>>>(lead->grid, lead->jobs);
+    if (int rc = cellgrid_build</*kOrigin=*/true>(c, lead->jobs, n, max_n)) return rc;
+    const dim3 g_pts((unsigned)((max_n + kNrmT - 1) / kNrmT), (unsigned)n);
+    k_nrm_compute<<<g_pts, kNrmT, 0, c->stream>>>(lead->jobs);
     if (int rc = check_launch(c, "k_nrm_compute")) return rc;
-    k_nrm_stats<<<g_pts, kNrmT, 0, c->stream>>>(lead->grid, lead->jobs);
+    k_nrm_stats<<<g_pts, kNrmT, 0, c->stream>>>(lead->jobs);
     if (int rc = check_launch(c, "k_nrm_stats")) return rc;
-    std::vector<IcpTgt> tg((size_t)n);
+    std::vector<CellWords> tg((size_t)n);
     std::vector<NrmDev> dev((size_t)n);
     for (int s = 0; s < n; s++) {
         if (ns[s] == 0) continue;
-        HIP_TRY(c, hipMemcpyAsync(&tg[(size_t)s], hs[s]->tg, sizeof(IcpTgt), hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(&tg[(size_t)s], hs[s]->grid.words, sizeof(CellWords), hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(c, hipMemcpyAsync(&dev[(size_t)s], hs[s]->dev, sizeof(NrmDev), hipMemcpyDeviceToHost, c->stream));
     }
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     for (int s = 0; s < n; s++) {
         if (ns[s] == 0) continue;
-        const IcpTgt &t = tg[(size_t)s];
+        const CellWords &t = tg[(size_t)s];
         const NrmDev &d = dev[(size_t)s];
         if ((int64_t)t.alloc + (int64_t)t.rejected != ns[s] || (int64_t)d.w[0] != (int64_t)t.rejected || (int64_t)(d.w[0] + d.w[1] + d.w[2]) != ns[s]) {
             c->err = std::string(who) + ": the placed, rejected and counted points do not add up to the cloud's size";
@@ -166,18 +137,15 @@ extern "C" int lmono_normals_compute_frames(lmono_ctx *c, int n, lmono_normals *
     if (!c || n <= 0 || !hs || !mbs) return LMONO_EINVAL;
     if (n > 65535) { c->err = "lmono_normals_compute_frames: more than 65535 streams in one call"; return LMONO_EINVAL; }
     if (!nrm_viewpoints_ok(viewpoints, n)) { c->err = "lmono_normals_compute_frames: non-finite viewpoint"; return LMONO_EINVAL; }
+    std::vector<const PtRgb *> pts((size_t)n);
     std::vector<int64_t> ns((size_t)n);
     for (int s = 0; s < n; s++) {
-        const int fs = batch_handle_fault(c, s, hs), fb = batch_handle_fault(c, s, mbs);
-        if (fs == kHandleForeign || fb == kHandleForeign) { c->err = "lmono_normals_compute_frames: bad stream arguments"; return LMONO_EINVAL; }
-        if (fs == kHandleRepeated || fb == kHandleRepeated) { c->err = "lmono_normals_compute_frames: handles and map builders must be distinct"; return LMONO_EINVAL; }
-        const lmono_map_builder *b = mbs[s];
-        if (b->last_off + b->last_n > b->map_n) { c->err = "lmono_normals_compute_frames: the world cloud of a builder's last frame is no longer in rgb_map"; return LMONO_EINVAL; }
-        if (b->last_n > hs[s]->max_points) { c->err = "lmono_normals_compute_frames: more points than the handle's max_points"; return LMONO_ECAPACITY; }
-        ns[(size_t)s] = b->last_n;
+        if (!batch_pair_ok(c, "lmono_normals_compute_frames", "handles and map builders", s, hs, mbs)) return LMONO_EINVAL;
+        if (!builder_last_cloud(c, "lmono_normals_compute_frames", mbs[s], pts[(size_t)s], ns[(size_t)s])) return LMONO_EINVAL;
+        if (ns[(size_t)s] > hs[s]->max_points) { c->err = "lmono_normals_compute_frames: more points than the handle's max_points"; return LMONO_ECAPACITY; }
     }
     for (int s = 0; s < n; s++)
-        if (ns[(size_t)s] > 0) HIP_TRY(c, hipMemcpyAsync(hs[s]->pts, mbs[s]->map + mbs[s]->last_off, sizeof(PtRgb) * (size_t)ns[(size_t)s], hipMemcpyDeviceToDevice, c->stream));
+        if (ns[(size_t)s] > 0) HIP_TRY(c, hipMemcpyAsync(hs[s]->pts, pts[(size_t)s], sizeof(PtRgb) * (size_t)ns[(size_t)s], hipMemcpyDeviceToDevice, c->stream));
     return nrm_compute_batch(c, "lmono_normals_compute_frames", n, hs, ns.data(), viewpoints, stats);
 }
 
@@ -187,15 +155,11 @@ extern "C" int lmono_normals_compute_map(lmono_ctx *c, lmono_normals *s, lmono_v
     if (!nrm_viewpoints_ok(viewpoint, 1)) { c->err = "lmono_normals_compute_map: non-finite viewpoint"; return LMONO_EINVAL; }
     if (m->n_vox > s->max_points) { c->err = "lmono_normals_compute_map: more voxels than the handle's max_points"; return LMONO_ECAPACITY; }
     const int64_t n = m->n_vox;
-    if (n > 0) {
-        HIP_TRY(c, hipMemsetAsync(&s->tg->n_vox, 0, sizeof(unsigned), c->stream));
-        k_icp_from_voxels<<<(unsigned)((m->slots + kIcpT - 1) / kIcpT), kIcpT, 0, c->stream>>>(m->rec, m->slots, m->leaf, s->pts, (unsigned)n, &s->tg->n_vox);
-        if (int rc = check_launch(c, "k_icp_from_voxels")) return rc;
-    }
+    if (int rc = n > 0 ? vm_enqueue_points(c, m, s->pts, s->n_vox) : LMONO_OK) return rc;
     if (int rc = nrm_compute_batch(c, "lmono_normals_compute_map", 1, &s, &n, viewpoint, stats)) return rc;
     if (n > 0) {
         unsigned found = 0;
-        HIP_TRY(c, hipMemcpy(&found, &s->tg->n_vox, sizeof found, hipMemcpyDeviceToHost));
+        HIP_TRY(c, hipMemcpy(&found, s->n_vox, sizeof found, hipMemcpyDeviceToHost));
         if ((int64_t)found != n) { s->last_n = 0; c->err = "lmono_normals_compute_map: the table's occupied records do not match the map's size"; return LMONO_ENODEV; }
     }
     return LMONO_OK;
@@ -205,23 +169,12 @@ extern "C" int64_t lmono_normals_read(lmono_ctx *c, lmono_normals *s, lmono_norm
 {
     if (!c || !s || s->ctx != c) return LMONO_EINVAL;
     if (!out_h && !count_h) return s->last_n;
-    if (cap < s->last_n) { c->err = "lmono_normals_read: output capacity too small"; return LMONO_ECAPACITY; }
-    if (s->last_n > 0) {
-        if (out_h) HIP_TRY(c, hipMemcpyAsync(out_h, s->rec, sizeof(NrmRecord) * (size_t)s->last_n, hipMemcpyDeviceToHost, c->stream));
-        if (count_h) HIP_TRY(c, hipMemcpyAsync(count_h, s->count, sizeof(unsigned) * (size_t)s->last_n, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-    }
-    return s->last_n;
+    return read_last(c, "lmono_normals_read", s->last_n, cap, out_h, s->rec, sizeof(NrmRecord), count_h, s->count, sizeof(unsigned));
 }
 
 extern "C" int64_t lmono_normals_cloud(lmono_ctx *c, lmono_normals *s, lmono_point_rgb *out_h, int64_t cap)
 {
     if (!c || !s || s->ctx != c) return LMONO_EINVAL;
     if (!out_h) return s->last_n;
-    if (cap < s->last_n) { c->err = "lmono_normals_cloud: output capacity too small"; return LMONO_ECAPACITY; }
-    if (s->last_n > 0) {
-        HIP_TRY(c, hipMemcpyAsync(out_h, s->pts, sizeof(PtRgb) * (size_t)s->last_n, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-    }
-    return s->last_n;
+    return read_last(c, "lmono_normals_cloud", s->last_n, cap, out_h, s->pts, sizeof(PtRgb));
 }

@@ -2,59 +2,40 @@
 // MapBuilder::processMapping carries commented out in front of its voxel grid (mono_lidar_mapping/src/map_builder/Map_Builder.cc:24-29),
 // as a device-resident filter between the map builder and the voxel map.  The arithmetic is sor.hpp; this file is how the neighbours are found.
 //
-// One filter call is seven launches for all streams (blockIdx.y = stream), none of which waits on another workgroup:
-//   k_sor_clear     empties the cell table of the call (open addressing over a power of two >= 2 n of 64-bit keys, as the voxel map's).
-//   k_sor_cells     per point: validity and key; the cell is claimed with the 64-bit compare-and-swap of k_vm_find; one atomic add on the
-//                   cell's count gives the point its rank in the cell.
-//   k_sor_offsets   a prefix over the occupied cells in whatever order the workgroups arrive (one atomic per workgroup), and the query's
-//                   work list: one item per 64 points of a cell.
-//   k_sor_scatter   copies xyz + input index cell by cell.  The order inside a cell and the order of the cells differ from run to run;
-//                   nothing downstream depends on them: selection is by value and every sum is an integer.
+// One filter call is seven launches for all streams (blockIdx.y = stream), none of which waits on another workgroup.  The first four build the
+// grid of the call, without an origin and with the query's work list (cell_grid.hip: clear, cells, offsets, scatter).  Then
 //   k_sor_query     the hot kernel.  A workgroup is one wave and takes work items from a counter; an item is up to 64 queries of ONE cell, which share
 //                   their neighbourhood.  A query takes a group of 64 / (queries, rounded up to a power of two) adjacent lanes, which deal the
 //                   candidates among themselves and add their integer counts and sums with wave shuffles.  For ring r = 1, 2 ... the wave stages
 //                   the points of the (2r + 1)^3 cells in LDS tile by tile and each query counts its candidates with d2 <= sor_rho2(r, h).  Queries
-//                   that hold k of them are
-//                   finished at this ring: they find the k-th smallest d2 EXACTLY by a radix select over its bits (non-negative floats order as
+//                   that hold k of them are finished at this ring: they find the k-th smallest d2 EXACTLY by a radix select over its bits (non-negative floats order as
 //                   uint32; five bits a pass, counting the candidates under the prefix found so far by their next digit, by re-scanning: it
 //                   stores counts and no candidate, so it holds for any number of them), then S = sum of u over d2 < tau, plus
 //                   (k - count) u(tau).  The ring grows only while a lane of the wave is unfinished.  Per-wave integer reduction of the
 //                   statistics, then 64-bit atomic adds.
-//   k_sor_flag      every thread forms the threshold from the four words (sor_threshold: identical bits everywhere), writes the keep flag and
-//                   counts a tile's kept points.
+//   k_sor_flag      every thread forms the threshold from the four words (sor_threshold: identical bits everywhere), writes the keep flag (and
+//                   kSorNoScore as the score of a point the grid rejected) and counts a tile's kept points.
 //   k_sor_compact   stable compaction into the filter's output cloud: a tile starts where the tiles in front of it end.
 #pragma once
 #include "common.hpp"
-#include "colour.hip"
-#include "sor.hpp"
+#include "cell_grid.hip"
 
 namespace lmono {
 
 constexpr int kSorT = 256;                // threads of the streaming kernels
-constexpr int kSorQ = 64;                 // queries of one work item of k_sor_query: one wave
+constexpr int kSorQ = kCellQ;             // queries of one work item of k_sor_query: one wave
 constexpr int kSorTile = 256;             // candidates staged in LDS at a time (4 KB), and as many on their way in registers
 constexpr int kSorDigit = 5;              // bits of d2 a pass of the radix select settles (a 32 x 64 histogram in LDS, 8 KB)
 constexpr int kSorKeepTile = 1024;        // points per workgroup of k_sor_flag / k_sor_compact
-constexpr unsigned kSorNoSlot = 0xffffffffu;
 
-struct SorPt { float x, y, z; unsigned i; };
-struct SorWork { unsigned slot, tile; };
-
-// the 64-bit words of a stream's results
-enum { kSorM = 0, kSorA, kSorBhi, kSorBlo, kSorIsolated, kSorRejected, kSorKept, kSorAlloc, kSorNWork, kSorRingSum, kSorSelected, kSorNext, kSorWords = 16 };
+// the 64-bit words of a stream's results; the grid's words (CellWords) lie behind them, from kSorGrid
+enum { kSorM = 0, kSorA, kSorBhi, kSorBlo, kSorIsolated, kSorKept, kSorRingSum, kSorSelected, kSorNext, kSorGrid, kSorWords = 16 };
+static_assert(8 * kSorGrid + sizeof(CellWords) <= 8 * kSorWords, "the grid's words fit behind the filter's");
 
 struct SorJob {
-    const PtRgb *pts;
-    long long n;
-    unsigned long long *key;               // the cell table: key, points, first point in `sorted`
-    unsigned *cnt, *off;
-    unsigned mask;                         // slots of this call - 1
-    float h, inv;
-    int k, rings;
+    CellView g;                            // the call's cloud and its grid; g.w lies in st
+    int k;
     double mul;
-    unsigned *pslot, *prank;               // per input point: its cell's slot (kSorNoSlot: rejected) and its rank in the cell
-    SorPt *sorted;
-    SorWork *work;
     unsigned *v;                           // per input point: score, kSorNoScore when rejected or isolated
     unsigned char *keep;
     unsigned *tile_n;                      // kept points per tile of kSorKeepTile
@@ -62,121 +43,10 @@ struct SorJob {
     unsigned long long *st;                // [kSorWords]
 };
 
-static_assert(sizeof(SorPt) == 16 && sizeof(SorWork) == 8, "sor layouts");
-
-// exclusive prefix of x over the kSorT threads of a workgroup (wsum: 4 words of LDS); total = the workgroup's sum
-__device__ inline unsigned long long sor_block_scan(unsigned long long x, unsigned long long *wsum, unsigned long long &total)
-{
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    unsigned long long incl = x;
-    for (int d = 1; d < 64; d <<= 1) {
-        const unsigned long long y = __shfl_up(incl, d);
-        if (lane >= d) incl += y;
-    }
-    if (lane == 63) wsum[w] = incl;
-    __syncthreads();
-    unsigned long long base = 0;
-    total = 0;
-    for (int u = 0; u < kSorT / 64; u++) { if (u < w) base += wsum[u]; total += wsum[u]; }
-    __syncthreads();                        // wsum may be written again
-    return base + incl - x;
-}
-
-__global__ __launch_bounds__(kSorT) void k_sor_clear(const SorJob *jobs)
-{
-    const SorJob &j = jobs[blockIdx.y];
-    const unsigned long long s = (unsigned long long)blockIdx.x * kSorT + threadIdx.x;
-    if (j.n == 0 || s > j.mask) return;
-    j.key[s] = kVmEmpty;
-    j.cnt[s] = 0;
-}
-
-// slot of `key`, claimed if new.  The table has at least 2 n slots for at most n keys: the probe always ends early
-__device__ inline unsigned sor_claim(const SorJob &j, uint64_t key)
-{
-    unsigned h = (unsigned)vm_mix(key) & j.mask;
-    for (unsigned probe = 0; probe <= j.mask; probe++, h = (h + 1) & j.mask) {
-        unsigned long long k = __hip_atomic_load(&j.key[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (k == kVmEmpty) k = atomicCAS(&j.key[h], (unsigned long long)kVmEmpty, (unsigned long long)key);
-        if (k == kVmEmpty || k == key) return h;
-    }
-    return kSorNoSlot;
-}
-
-// slot of `key` in the finished table, kSorNoSlot when no point lies in that cell
-__device__ inline unsigned sor_find(const SorJob &j, uint64_t key)
-{
-    unsigned h = (unsigned)vm_mix(key) & j.mask;
-    for (unsigned probe = 0; probe <= j.mask; probe++, h = (h + 1) & j.mask) {
-        const unsigned long long k = j.key[h];
-        if (k == key) return h;
-        if (k == kVmEmpty) return kSorNoSlot;
-    }
-    return kSorNoSlot;
-}
-
-__global__ __launch_bounds__(kSorT) void k_sor_cells(const SorJob *jobs)
-{
-    const SorJob &j = jobs[blockIdx.y];
-    const long long i = (long long)blockIdx.x * kSorT + threadIdx.x;
-    if ((long long)blockIdx.x * kSorT >= j.n) return;
-    __shared__ unsigned l_rej;
-    if (threadIdx.x == 0) l_rej = 0;
-    __syncthreads();
-    if (i < j.n) {
-        const PtRgb pt = j.pts[i];
-        uint64_t key = kVmEmpty;
-        int c[3];
-        unsigned slot = kSorNoSlot;
-        if (sor_cell(pt.x, pt.y, pt.z, j.inv, key, c)) slot = sor_claim(j, key);
-        j.pslot[i] = slot;
-        if (slot == kSorNoSlot) { atomicAdd(&l_rej, 1u); j.v[i] = kSorNoScore; }
-        else j.prank[i] = atomicAdd(&j.cnt[slot], 1u);
-    }
-    __syncthreads();
-    if (threadIdx.x == 0 && l_rej) atomicAdd(&j.st[kSorRejected], (unsigned long long)l_rej);
-}
-
-__global__ __launch_bounds__(kSorT) void k_sor_offsets(const SorJob *jobs)
-{
-    const SorJob &j = jobs[blockIdx.y];
-    const unsigned long long s = (unsigned long long)blockIdx.x * kSorT + threadIdx.x;
-    if (j.n == 0 || (unsigned long long)blockIdx.x * kSorT > j.mask) return;
-    __shared__ unsigned long long wsum[kSorT / 64], l_base;
-    const unsigned c = s <= j.mask ? j.cnt[s] : 0u;
-    const unsigned t = (c + kSorQ - 1) / kSorQ;
-    unsigned long long total;
-    const unsigned long long ex = sor_block_scan((unsigned long long)t << 32 | c, wsum, total);      // both sums stay below 2^32: n <= 2^28
-    if (threadIdx.x == 0 && total) {
-        const unsigned long long bc = atomicAdd(&j.st[kSorAlloc], total & 0xffffffffull);
-        const unsigned long long bt = atomicAdd(&j.st[kSorNWork], total >> 32);
-        l_base = bt << 32 | bc;
-    }
-    __syncthreads();
-    if (c == 0) return;
-    const unsigned long long at = l_base + ex;          // no carry between the halves: each half is a sum below 2^32
-    j.off[s] = (unsigned)at;
-    SorWork *w = j.work + (at >> 32);
-    for (unsigned q = 0; q < t; q++) { w[q].slot = (unsigned)s; w[q].tile = q; }
-}
-
-__global__ __launch_bounds__(kSorT) void k_sor_scatter(const SorJob *jobs)
-{
-    const SorJob &j = jobs[blockIdx.y];
-    const long long i = (long long)blockIdx.x * kSorT + threadIdx.x;
-    if (i >= j.n) return;
-    const unsigned slot = j.pslot[i];
-    if (slot == kSorNoSlot) return;
-    const PtRgb pt = j.pts[i];
-    SorPt p;
-    p.x = pt.x; p.y = pt.y; p.z = pt.z; p.i = (unsigned)i;
-    j.sorted[j.off[slot] + j.prank[i]] = p;
-}
-
 // The points of the cells within ring r of cell (cx, cy, cz), staged in LDS tile by tile.  The lanes of a group (`group` lanes, a power of two;
 // `sub` = the lane's place in its group) share one query and deal a tile's points among themselves: f(point) runs for every point on
 // exactly one lane of each group, and lanes with the same `sub` read the same staged point at the same time (a broadcast).
-template <typename F> __device__ inline void sor_scan(const SorJob &j, int cx, int cy, int cz, int r, unsigned group, unsigned sub, SorPt *tile, unsigned *seg_pre, unsigned *seg_off, F f)
+template <typename F> __device__ inline void sor_scan(const CellView &g, int cx, int cy, int cz, int r, unsigned group, unsigned sub, CellPt *tile, unsigned *seg_pre, unsigned *seg_off, F f)
 {
     const int lane = threadIdx.x;
     const int side = 2 * r + 1, cells = side * side * side;
@@ -187,8 +57,8 @@ template <typename F> __device__ inline void sor_scan(const SorJob &j, int cx, i
             const int x = cx + cid % side - r, y = cy + cid / side % side - r, z = cz + cid / (side * side) - r;
             constexpr int L = 1 << 20;
             if (x >= -L && x < L && y >= -L && y < L && z >= -L && z < L) {
-                const unsigned slot = sor_find(j, vm_key(x, y, z));
-                if (slot != kSorNoSlot) { n = j.cnt[slot]; o = j.off[slot]; }
+                const unsigned slot = cellgrid_find(g, vm_key(x, y, z));
+                if (slot != kCellNoSlot) { n = g.cnt[slot]; o = g.off[slot]; }
             }
         }
         unsigned incl = n;
@@ -201,7 +71,7 @@ template <typename F> __device__ inline void sor_scan(const SorJob &j, int cx, i
         seg_pre[lane] = incl - n; seg_off[lane] = o;
         __syncthreads();
         // the points of the tile at t0 into registers: a tile is fetched while the tile before it is scanned
-        SorPt buf[kSorTile / 64];
+        CellPt buf[kSorTile / 64];
         auto fetch = [&](unsigned t0) {
 #pragma unroll
             for (int u = 0; u < kSorTile / 64; u++) {
@@ -209,7 +79,7 @@ template <typename F> __device__ inline void sor_scan(const SorJob &j, int cx, i
                 if (p >= total) continue;
                 int s = 0;                                  // the last segment that starts at or before p: it is not empty, since p < total
                 for (int step = 32; step > 0; step >>= 1) if (seg_pre[s + step] <= p) s += step;
-                buf[u] = j.sorted[seg_off[s] + (p - seg_pre[s])];
+                buf[u] = g.sorted[seg_off[s] + (p - seg_pre[s])];
             }
         };
         if (total) fetch(0);
@@ -242,12 +112,12 @@ template <typename T> __device__ inline T sor_group_sum(T x, unsigned group)
 __global__ __launch_bounds__(kSorQ) void k_sor_query(const SorJob *jobs)
 {
     const SorJob &j = jobs[blockIdx.y];
-    if (j.n == 0) return;
-    __shared__ SorPt tile[kSorTile];
+    if (j.g.n == 0) return;
+    __shared__ CellPt tile[kSorTile];
     __shared__ unsigned seg_pre[64], seg_off[64];
     __shared__ unsigned hist[1 << kSorDigit][kSorQ];
     const int lane = threadIdx.x;
-    const unsigned nwork = (unsigned)j.st[kSorNWork];
+    const unsigned nwork = j.g.w->nwork;
     const unsigned k = (unsigned)j.k;
     unsigned long long sM = 0, sA = 0, sBhi = 0, sBlo = 0, sIso = 0, sRing = 0;
     for (;;) {
@@ -256,24 +126,24 @@ __global__ __launch_bounds__(kSorQ) void k_sor_query(const SorJob *jobs)
         if (lane == 0) w = (unsigned)atomicAdd(&j.st[kSorNext], 1ull);
         w = __shfl(w, 0);
         if (w >= nwork) break;
-        const SorWork wk = j.work[w];
-        const unsigned long long key = j.key[wk.slot];
+        const CellWork wk = j.g.work[w];
+        const unsigned long long key = j.g.key[wk.slot];
         const int cx = (int)(key & 0x1fffff) - (1 << 20), cy = (int)(key >> 21 & 0x1fffff) - (1 << 20), cz = (int)(key >> 42 & 0x1fffff) - (1 << 20);
         // the item's queries (at most 64) take `group` adjacent lanes each: the largest power of two that fits them into the wave.  Most cells of a
         // frame cloud hold far fewer than 64 points; their queries would leave most of the wave idle
-        const unsigned nq = min(j.cnt[wk.slot] - wk.tile * kSorQ, (unsigned)kSorQ);
+        const unsigned nq = min(j.g.cnt[wk.slot] - wk.tile * kSorQ, (unsigned)kSorQ);
         unsigned group = 1, shift = 0;
         while (nq * (group << 1) <= (unsigned)kSorQ) { group <<= 1; shift++; }
         const unsigned sub = lane & (group - 1), qi = wk.tile * kSorQ + (lane >> shift);
         const bool mine = (unsigned)lane >> shift < nq;
-        SorPt q = { 0.0f, 0.0f, 0.0f, kSorNoSlot };
-        if (mine) q = j.sorted[j.off[wk.slot] + qi];
+        CellPt q = { 0.0f, 0.0f, 0.0f, kCellNoSlot };
+        if (mine) q = j.g.sorted[j.g.off[wk.slot] + qi];
         bool active = mine;
         unsigned v = kSorNoScore;
-        for (int r = 1; r <= j.rings && __any(active); r++) {
-            const float bound = sor_rho2(r, j.h);
+        for (int r = 1; r <= j.g.rings && __any(active); r++) {
+            const float bound = sor_rho2(r, j.g.h);
             unsigned c = 0;
-            sor_scan(j, cx, cy, cz, r, group, sub, tile, seg_pre, seg_off, [&](const SorPt &p) {
+            sor_scan(j.g, cx, cy, cz, r, group, sub, tile, seg_pre, seg_off, [&](const CellPt &p) {
                 if (p.i != q.i && sor_d2(q.x, q.y, q.z, p.x, p.y, p.z) <= bound) c++;
             });
             c = sor_group_sum(c, group);
@@ -289,7 +159,7 @@ __global__ __launch_bounds__(kSorQ) void k_sor_query(const SorJob *jobs)
                 const int lo = hi >= kSorDigit - 1 ? hi - (kSorDigit - 1) : 0;
                 const unsigned dmax = (2u << (hi - lo)) - 1u, want = prefix >> (hi + 1);
                 for (unsigned d = 0; d <= dmax; d++) hist[d][lane] = 0;
-                sor_scan(j, cx, cy, cz, r, group, sub, tile, seg_pre, seg_off, [&](const SorPt &p) {
+                sor_scan(j.g, cx, cy, cz, r, group, sub, tile, seg_pre, seg_off, [&](const CellPt &p) {
                     const unsigned bits = __float_as_uint(sor_d2(q.x, q.y, q.z, p.x, p.y, p.z));
                     if (p.i != q.i && bits >> (hi + 1) == want) atomicAdd(&hist[bits >> lo & dmax][lane], 1u);      // no-return LDS add: the scan does not wait for it
                 });
@@ -303,7 +173,7 @@ __global__ __launch_bounds__(kSorQ) void k_sor_query(const SorJob *jobs)
                 prefix |= digit << lo;
             }
             unsigned long long S = 0;
-            sor_scan(j, cx, cy, cz, r, group, sub, tile, seg_pre, seg_off, [&](const SorPt &p) {
+            sor_scan(j.g, cx, cy, cz, r, group, sub, tile, seg_pre, seg_off, [&](const CellPt &p) {
                 const float d2 = sor_d2(q.x, q.y, q.z, p.x, p.y, p.z);
                 if (fin && p.i != q.i && __float_as_uint(d2) < prefix) S += sor_u(d2);
             });
@@ -336,7 +206,7 @@ __global__ __launch_bounds__(kSorT) void k_sor_flag(const SorJob *jobs)
 {
     const SorJob &j = jobs[blockIdx.y];
     const long long base = (long long)blockIdx.x * kSorKeepTile;
-    if (base >= j.n) return;
+    if (base >= j.g.n) return;
     __shared__ unsigned l_n;
     if (threadIdx.x == 0) l_n = 0;
     __syncthreads();
@@ -345,8 +215,11 @@ __global__ __launch_bounds__(kSorT) void k_sor_flag(const SorJob *jobs)
     unsigned mine = 0;
     for (int r = 0; r < kSorKeepTile / kSorT; r++) {
         const long long i = base + r * kSorT + threadIdx.x;
-        if (i >= j.n) break;
-        const bool kp = sor_keep(j.v[i], thr);
+        if (i >= j.g.n) break;
+        const bool rejected = j.g.slot[i] == kCellNoSlot;     // no query wrote its score
+        const unsigned v = rejected ? kSorNoScore : j.v[i];
+        if (rejected) j.v[i] = v;
+        const bool kp = sor_keep(v, thr);
         j.keep[i] = kp ? 1 : 0;
         mine += kp ? 1u : 0u;
     }
@@ -362,17 +235,17 @@ __global__ __launch_bounds__(kSorT) void k_sor_compact(const SorJob *jobs)
 {
     const SorJob &j = jobs[blockIdx.y];
     const long long base = (long long)blockIdx.x * kSorKeepTile;
-    if (base >= j.n) return;
+    if (base >= j.g.n) return;
     __shared__ unsigned long long wsum[kSorT / 64];
     unsigned long long before = 0, total;
     for (unsigned b = threadIdx.x; b < blockIdx.x; b += kSorT) before += j.tile_n[b];
-    (void)sor_block_scan(before, wsum, total);
+    (void)cellgrid_block_scan<kSorT>(before, wsum, total);
     unsigned long long at = total;                        // kept points of the tiles in front: <= base, so every write below stays inside out[n]
     for (int r = 0; r < kSorKeepTile / kSorT; r++) {
         const long long i = base + r * kSorT + threadIdx.x;
-        const bool kp = i < j.n && j.keep[i] != 0;
-        const unsigned long long pos = sor_block_scan(kp ? 1ull : 0ull, wsum, total);
-        if (kp) j.out[at + pos] = j.pts[i];
+        const bool kp = i < j.g.n && j.keep[i] != 0;
+        const unsigned long long pos = cellgrid_block_scan<kSorT>(kp ? 1ull : 0ull, wsum, total);
+        if (kp) j.out[at + pos] = j.g.pts[i];
         at += total;
     }
 }

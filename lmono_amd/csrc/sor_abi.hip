@@ -6,15 +6,11 @@
 struct lmono_sor {
     lmono_ctx *ctx = nullptr;
     int64_t max_points = 0;
-    int k = 0, rings = 0;
+    int k = 0;
     double mul = 0.0;
-    float h = 0.0f, inv = 0.0f;
-    uint64_t slots = 0;                      // of the allocation; a call uses the smallest power of two >= 2 n (at least 64)
     DevOwner mem;
-    unsigned long long *key = nullptr;
-    unsigned *cnt = nullptr, *off = nullptr, *pslot = nullptr, *prank = nullptr, *v = nullptr, *tile_n = nullptr;
-    SorPt *sorted = nullptr;
-    SorWork *work = nullptr;
+    CellGrid grid;                           // with the query's work list; its words lie in the call's results
+    unsigned *v = nullptr, *tile_n = nullptr;
     unsigned char *keep = nullptr;
     PtRgb *out = nullptr, *pts = nullptr;    // pts: staging of the host-buffer entry
     // the last call: points in, kept, and its statistics as the ABI reports them (+ the two diagnostic words)
@@ -41,13 +37,10 @@ extern "C" lmono_sor *lmono_sor_create(lmono_ctx *c, int64_t max_points, int mea
     if (hipSetDevice(c->device) != hipSuccess) { c->err = "hipSetDevice failed"; return nullptr; }
     lmono_sor *s = new lmono_sor();
     s->ctx = c;
-    s->max_points = max_points; s->k = mean_k; s->rings = max_rings; s->mul = stddev_mul; s->h = cell; s->inv = 1.0f / cell;
-    s->slots = 64;
-    while (s->slots < 2 * (uint64_t)max_points) s->slots <<= 1;
+    s->max_points = max_points; s->k = mean_k; s->mul = stddev_mul;
     const size_t n = (size_t)max_points;
-    const bool ok = s->mem.alloc(s->key, (size_t)s->slots) && s->mem.alloc(s->cnt, (size_t)s->slots) && s->mem.alloc(s->off, (size_t)s->slots) && s->mem.alloc(s->pslot, n) &&
-                    s->mem.alloc(s->prank, n) && s->mem.alloc(s->v, n) && s->mem.alloc(s->tile_n, (n + kSorKeepTile - 1) / kSorKeepTile) && s->mem.alloc(s->sorted, n) &&
-                    s->mem.alloc(s->work, n + n / kSorQ + 1) && s->mem.alloc(s->keep, n) && s->mem.alloc(s->out, n) && s->mem.alloc(s->pts, n);
+    const bool ok = s->grid.alloc(s->mem, max_points, cell, max_rings, /*work_list=*/true) && s->mem.alloc(s->v, n) && s->mem.alloc(s->tile_n, (n + kSorKeepTile - 1) / kSorKeepTile) &&
+                    s->mem.alloc(s->keep, n) && s->mem.alloc(s->out, n) && s->mem.alloc(s->pts, n);
     if (!ok) { c->err = "lmono_sor_create: device allocation failed"; lmono_sor_destroy(s); return nullptr; }
     return s;
 }
@@ -72,31 +65,19 @@ static int sor_filter_batch(lmono_ctx *c, const char *who, int n, lmono_sor *con
     if (!job_table(lead->mem, lead->jobs, lead->results, lead->jobs_cap, n, 2 * kSorWords)) { c->err = std::string(who) + ": job table allocation failed"; return LMONO_ENOMEM; }
     unsigned long long *st = (unsigned long long *)lead->results;
     std::vector<SorJob> jobs((size_t)n);
-    uint64_t max_slots = 0;
     for (int s = 0; s < n; s++) {
         lmono_sor *f = sors[s];
-        uint64_t slots = 64;
-        while (slots < 2 * (uint64_t)ns[s]) slots <<= 1;        // <= f->slots, since ns[s] <= max_points
-        if (ns[s] > 0) max_slots = std::max(max_slots, slots);
         SorJob &j = jobs[(size_t)s];
-        j.pts = pts_d[s]; j.n = ns[s];
-        j.key = f->key; j.cnt = f->cnt; j.off = f->off; j.mask = (unsigned)(slots - 1);
-        j.h = f->h; j.inv = f->inv; j.k = f->k; j.rings = f->rings; j.mul = f->mul;
-        j.pslot = f->pslot; j.prank = f->prank; j.sorted = f->sorted; j.work = f->work; j.v = f->v; j.keep = f->keep; j.tile_n = f->tile_n; j.out = f->out;
+        j.g = f->grid.view(pts_d[s], ns[s]);
+        j.k = f->k; j.mul = f->mul;
+        j.v = f->v; j.keep = f->keep; j.tile_n = f->tile_n; j.out = f->out;
         j.st = st + (size_t)kSorWords * s;
+        j.g.w = (CellWords *)(j.st + kSorGrid);                 // they come back with the results, in the call's one copy
     }
     HIP_TRY(c, hipMemcpyAsync(lead->jobs, jobs.data(), sizeof(SorJob) * (size_t)n, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipMemsetAsync(st, 0, sizeof(unsigned long long) * kSorWords * (size_t)n, c->stream));
-    const dim3 g_slots((unsigned)((max_slots + kSorT - 1) / kSorT), (unsigned)n), g_pts((unsigned)((max_n + kSorT - 1) / kSorT), (unsigned)n);
     const dim3 g_query((unsigned)std::min<int64_t>(max_n + max_n / kSorQ + 1, 4096), (unsigned)n), g_keep((unsigned)((max_n + kSorKeepTile - 1) / kSorKeepTile), (unsigned)n);
-    k_sor_clear<<<g_slots, kSorT, 0, c->stream>>>(lead->jobs);
-    if (int rc = check_launch(c, "k_sor_clear")) return rc;
-    k_sor_cells<<<g_pts, kSorT, 0, c->stream>>>(lead->jobs);
-    if (int rc = check_launch(c, "k_sor_cells")) return rc;
-    k_sor_offsets<<<g_slots, kSorT, 0, c->stream>>>(lead->jobs);
-    if (int rc = check_launch(c, "k_sor_offsets")) return rc;
-    k_sor_scatter<<<g_pts, kSorT, 0, c->stream>>>(lead->jobs);
-    if (int rc = check_launch(c, "k_sor_scatter")) return rc;
+    if (int rc = cellgrid_build</*kOrigin=*/false>(c, lead->jobs, n, max_n)) return rc;
     k_sor_query<<<g_query, kSorQ, 0, c->stream>>>(lead->jobs);
     if (int rc = check_launch(c, "k_sor_query")) return rc;
     k_sor_flag<<<g_keep, kSorT, 0, c->stream>>>(lead->jobs);
@@ -110,7 +91,7 @@ static int sor_filter_batch(lmono_ctx *c, const char *who, int n, lmono_sor *con
         lmono_sor *f = sors[s];
         if (ns[s] == 0) continue;
         const unsigned long long *r = res.data() + (size_t)kSorWords * s;
-        f->stats[1] = (int64_t)r[kSorRejected]; f->stats[2] = (int64_t)r[kSorIsolated]; f->stats[3] = (int64_t)r[kSorM]; f->stats[4] = (int64_t)r[kSorKept];
+        f->stats[1] = (int64_t)((const CellWords *)(r + kSorGrid))->rejected; f->stats[2] = (int64_t)r[kSorIsolated]; f->stats[3] = (int64_t)r[kSorM]; f->stats[4] = (int64_t)r[kSorKept];
         f->stats[5] = (int64_t)r[kSorA]; f->stats[6] = (int64_t)r[kSorBhi]; f->stats[7] = (int64_t)r[kSorBlo];
         f->diag[0] = (int64_t)r[kSorRingSum]; f->diag[1] = (int64_t)r[kSorSelected];
         f->last_kept = f->stats[4];
@@ -142,13 +123,8 @@ extern "C" int lmono_sor_filter_frames(lmono_ctx *c, int n, lmono_sor *const *so
     std::vector<const PtRgb *> pts((size_t)n);
     std::vector<int64_t> ns((size_t)n);
     for (int s = 0; s < n; s++) {
-        const int fs = batch_handle_fault(c, s, sors), fb = batch_handle_fault(c, s, mbs);
-        if (fs == kHandleForeign || fb == kHandleForeign) { c->err = "lmono_sor_filter_frames: bad stream arguments"; return LMONO_EINVAL; }
-        if (fs == kHandleRepeated || fb == kHandleRepeated) { c->err = "lmono_sor_filter_frames: filters and map builders must be distinct"; return LMONO_EINVAL; }
-        const lmono_map_builder *b = mbs[s];
-        if (b->last_off + b->last_n > b->map_n) { c->err = "lmono_sor_filter_frames: the world cloud of a builder's last frame is no longer in rgb_map"; return LMONO_EINVAL; }
-        pts[(size_t)s] = b->map + b->last_off;
-        ns[(size_t)s] = b->last_n;
+        if (!batch_pair_ok(c, "lmono_sor_filter_frames", "filters and map builders", s, sors, mbs)) return LMONO_EINVAL;
+        if (!builder_last_cloud(c, "lmono_sor_filter_frames", mbs[s], pts[(size_t)s], ns[(size_t)s])) return LMONO_EINVAL;
     }
     return sor_filter_batch(c, "lmono_sor_filter_frames", n, sors, pts.data(), ns.data(), stats);
 }
@@ -157,25 +133,14 @@ extern "C" int64_t lmono_sor_cloud(lmono_ctx *c, lmono_sor *s, lmono_point_rgb *
 {
     if (!c || !s || s->ctx != c) return LMONO_EINVAL;
     if (!out_h) return s->last_kept;
-    if (cap < s->last_kept) { c->err = "lmono_sor_cloud: output capacity too small"; return LMONO_ECAPACITY; }
-    if (s->last_kept > 0) {
-        HIP_TRY(c, hipMemcpyAsync(out_h, s->out, sizeof(PtRgb) * (size_t)s->last_kept, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-    }
-    return s->last_kept;
+    return read_last(c, "lmono_sor_cloud", s->last_kept, cap, out_h, s->out, sizeof(PtRgb));
 }
 
 extern "C" int64_t lmono_sor_scores(lmono_ctx *c, lmono_sor *s, uint8_t *keep_h, uint32_t *v_h, int64_t cap)
 {
     if (!c || !s || s->ctx != c) return LMONO_EINVAL;
     if (!keep_h && !v_h) return s->last_n;
-    if (cap < s->last_n) { c->err = "lmono_sor_scores: output capacity too small"; return LMONO_ECAPACITY; }
-    if (s->last_n > 0) {
-        if (keep_h) HIP_TRY(c, hipMemcpyAsync(keep_h, s->keep, (size_t)s->last_n, hipMemcpyDeviceToHost, c->stream));
-        if (v_h) HIP_TRY(c, hipMemcpyAsync(v_h, s->v, sizeof(uint32_t) * (size_t)s->last_n, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-    }
-    return s->last_n;
+    return read_last(c, "lmono_sor_scores", s->last_n, cap, keep_h, s->keep, 1, v_h, s->v, sizeof(uint32_t));
 }
 
 extern "C" int lmono_sor_threshold(lmono_ctx *c, lmono_sor *s, double out[3])
@@ -198,9 +163,7 @@ extern "C" int lmono_voxel_map_insert_filtered(lmono_ctx *c, int n, lmono_voxel_
     std::vector<const PtRgb *> pts((size_t)n);
     std::vector<int64_t> ns((size_t)n);
     for (int s = 0; s < n; s++) {
-        const int fm = batch_handle_fault(c, s, maps), fs = batch_handle_fault(c, s, sors);
-        if (fm == kHandleForeign || fs == kHandleForeign) { c->err = "lmono_voxel_map_insert_filtered: bad stream arguments"; return LMONO_EINVAL; }
-        if (fm == kHandleRepeated || fs == kHandleRepeated) { c->err = "lmono_voxel_map_insert_filtered: maps and filters must be distinct"; return LMONO_EINVAL; }
+        if (!batch_pair_ok(c, "lmono_voxel_map_insert_filtered", "maps and filters", s, maps, sors)) return LMONO_EINVAL;
         pts[(size_t)s] = sors[s]->out;
         ns[(size_t)s] = sors[s]->last_kept;
     }

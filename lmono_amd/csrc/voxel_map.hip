@@ -273,6 +273,18 @@ __global__ __launch_bounds__(kVmT) void k_vm_compact(const VmRec *rec, unsigned 
     if (at < cap) out[at] = r;
 }
 
+// every occupied voxel's output point (vm_point, what lmono_voxel_map_read gives) into out, in any order; n counts them, cap bounds the writes:
+// a map as the input cloud of another stage (the ICP's target, the surface normals)
+__global__ __launch_bounds__(kVmT) void k_vm_points_unordered(const VmRec *rec, unsigned long long slots, float leaf, PtRgb *out, unsigned cap, unsigned *n)
+{
+    const unsigned long long s = (unsigned long long)blockIdx.x * kVmT + threadIdx.x;
+    if (s >= slots) return;
+    const VmRec r = rec[s];
+    if (!vm_occupied(r)) return;
+    const unsigned at = atomicAdd(n, 1u);
+    if (at < cap) out[at] = vm_out_point(r, leaf);
+}
+
 // ---- compose: whole voxel maps, each under a rigid transform, folded into one destination ----
 // The sources' occupied records (k_vm_compact, no order) are the input; blockIdx.y = source.  The plain form -- one probe and one entry per record --
 // because a map's records are one per cell already: at comparable leaves about one source voxel lands in a destination voxel per tile, so a

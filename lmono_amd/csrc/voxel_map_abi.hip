@@ -274,13 +274,8 @@ extern "C" int lmono_voxel_map_insert_frames(lmono_ctx *c, int n, lmono_voxel_ma
     std::vector<const PtRgb *> pts((size_t)n);
     std::vector<int64_t> ns((size_t)n);
     for (int s = 0; s < n; s++) {
-        const int fm = batch_handle_fault(c, s, maps), fb = batch_handle_fault(c, s, mbs);
-        if (fm == kHandleForeign || fb == kHandleForeign) { c->err = "lmono_voxel_map_insert_frames: bad stream arguments"; return LMONO_EINVAL; }
-        if (fm == kHandleRepeated || fb == kHandleRepeated) { c->err = "lmono_voxel_map_insert_frames: maps and map builders must be distinct"; return LMONO_EINVAL; }
-        const lmono_map_builder *b = mbs[s];
-        if (b->last_off + b->last_n > b->map_n) { c->err = "lmono_voxel_map_insert_frames: the world cloud of a builder's last frame is no longer in rgb_map"; return LMONO_EINVAL; }
-        pts[(size_t)s] = b->map + b->last_off;
-        ns[(size_t)s] = b->last_n;
+        if (!batch_pair_ok(c, "lmono_voxel_map_insert_frames", "maps and map builders", s, maps, mbs)) return LMONO_EINVAL;
+        if (!builder_last_cloud(c, "lmono_voxel_map_insert_frames", mbs[s], pts[(size_t)s], ns[(size_t)s])) return LMONO_EINVAL;
     }
     return vm_insert_batch(c, "lmono_voxel_map_insert_frames", n, maps, pts.data(), ns.data(), stats);
 }
@@ -308,6 +303,15 @@ static int vm_collect(lmono_ctx *c, lmono_voxel_map *m, std::vector<VmRec> &recs
     HIP_TRY(c, hipMemcpy(recs.data(), m->rd_rec, sizeof(VmRec) * recs.size(), hipMemcpyDeviceToHost));
     std::sort(recs.begin(), recs.end(), [](const VmRec &a, const VmRec &b) { return a.key < b.key; });
     return LMONO_OK;
+}
+
+// a non-empty map as another stage's input cloud: its output points into out_d[n_vox] in any order, their number into *found_d (the caller
+// compares it with n_vox once its own call has synchronised).  One launch, no wait
+static int vm_enqueue_points(lmono_ctx *c, const lmono_voxel_map *m, PtRgb *out_d, unsigned *found_d)
+{
+    HIP_TRY(c, hipMemsetAsync(found_d, 0, sizeof(unsigned), c->stream));
+    k_vm_points_unordered<<<(unsigned)((m->slots + kVmT - 1) / kVmT), kVmT, 0, c->stream>>>(m->rec, m->slots, m->leaf, out_d, (unsigned)m->n_vox, found_d);
+    return check_launch(c, "k_vm_points_unordered");
 }
 
 extern "C" int64_t lmono_voxel_map_cells(lmono_ctx *c, lmono_voxel_map *m, uint64_t *keys_h, uint32_t *counts_h, uint64_t *sums_h, int64_t cap)

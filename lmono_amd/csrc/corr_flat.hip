@@ -604,12 +604,11 @@ __global__ __launch_bounds__(kCfT, LMONO_CF_WAVES) void k_corr_flat(BatchView b,
     }
     ((int4 *)o.corr + (size_t)c * kMaxQueries)[qi] = rres;
     if (outer == 0 && seed_c) seed_c[qi] = closest_out;
-    // residual-block record for the solver: the feature point and its 2 (edge) or 3 (plane) partners, 64 B
+    // residual-block record for the solver: the feature point and its 2 (edge) or 3 (plane) partners, staged (64 B)
     float4 A = make_float4(0.f, 0.f, 0.f, 0.f), B = A, C = A;
     if (rres.w != 0) { A = cloud[rres.x]; B = cloud[rres.y]; if (rres.z >= 0) C = cloud[rres.z]; }
     fp.w = __int_as_float(rres.w);
-    float4 *rec = o.crec + ((size_t)c * kMaxQueries + qi) * 4;
-    rec[0] = fp; rec[1] = A; rec[2] = B; rec[3] = C;
+    store_staged_record(o.crec + ((size_t)c * kMaxQueries + qi) * 4, fp, A, B, C);
 }
 
 } // namespace lmono

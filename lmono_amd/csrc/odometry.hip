@@ -15,6 +15,7 @@
 // The (scan line, azimuth bin) index the searches sweep (lb_key, az_bin, line_of, elev_of, lb_for_runs) is line_index.hip's, included ahead of this file;
 // the front end builds it (k_compact_index).
 #include "batch.hpp"
+#include "wave_sum28.hpp"
 
 namespace lmono {
 
@@ -258,7 +259,7 @@ struct OdomView {
                           // kThinStride-th workgroup's share (their result is only the next pair's warm start); -1: all pairs use all
     double *state;        // [n_chains][8]  q(xyzw), t, pad
     int *corr;            // [n_chains][kMaxQueries][4]
-    float4 *crec;         // [n_chains][kMaxQueries][4] residual-block records: (cp, kind), a, b, c
+    float4 *crec;         // [n_chains][kMaxQueries][4] residual-block records, staged (store_staged_record): (cp, kind), then six doubles
     float4 *lmrec;        // [n_chains][4 - planes][kMaxQueries] the planes of k_lm_solve<planes>'s staged blocks that are not in LDS (LmRec)
     double *incr;         // [n_scans][7]
     int *lm_info;         // [n_chains][4]
@@ -788,6 +789,42 @@ __device__ __forceinline__ int4 correspond_g32(const BatchView &b, int k, int qi
     return out;
 }
 
+// A staged residual block (64 B in LDS, planes of 16 B): (cp, kind) as float4, then six doubles that do not depend on the pose and
+// are computed once per launch instead of once per evaluation (up to nine per launch):
+//   edge   a, e^ = (a - b) / |a - b|:          r = (lp - a) x e^   [= ((lp - a) x (lp - b)) / |a - b| since (lp - a) x (lp - a) = 0],  d r / d lp = -[e^]_x
+//   plane  j, n = normalised((j - l) x (j - m)):  r = (lp - j) . n,  d r / d lp = n^T
+__device__ __forceinline__ void stage_block(const float4 cp, const float4 A, const float4 B, const float4 Cc, double *P)
+{
+    const int kind = __float_as_int(cp.w);
+    if (kind == 1) {
+        const double ex = (double)A.x - (double)B.x, ey = (double)A.y - (double)B.y, ez = (double)A.z - (double)B.z;
+        const double inv = 1.0 / sqrt(ex * ex + ey * ey + ez * ez);
+        P[0] = (double)A.x; P[1] = (double)A.y; P[2] = (double)A.z;
+        P[3] = ex * inv; P[4] = ey * inv; P[5] = ez * inv;
+    } else {
+        const double jx = (double)A.x, jy = (double)A.y, jz = (double)A.z;
+        const double ux = jx - (double)B.x, uy = jy - (double)B.y, uz = jz - (double)B.z;
+        const double wx = jx - (double)Cc.x, wy = jy - (double)Cc.y, wz = jz - (double)Cc.z;
+        double nx = uy * wz - uz * wy, ny = uz * wx - ux * wz, nz = ux * wy - uy * wx;
+        const double nn = sqrt(nx * nx + ny * ny + nz * nz);
+        if (nn > 0.0) { nx /= nn; ny /= nn; nz /= nn; }
+        P[0] = jx; P[1] = jy; P[2] = jz; P[3] = nx; P[4] = ny; P[5] = nz;
+    }
+}
+
+// The solver's 64-B record of one feature, written where the record is born (the search has the feature point and its partners at
+// hand; k_lm_solve used to read them back and stage every block itself, up to nine per thread one after the other): the staged block
+// (cp, kind | P0 P1 | P2 P3 | P4 P5).  stage_block is uncontracted code, so its doubles do not depend on which kernel computes them.
+__device__ __forceinline__ void store_staged_record(float4 *rec, const float4 cp, const float4 A, const float4 B, const float4 Cc)
+{
+    double P[6] = { 0.0, 0.0, 0.0, 0.0, 0.0, 0.0 };
+    if (__float_as_int(cp.w) != 0) stage_block(cp, A, B, Cc, P);
+    rec[0] = cp;
+    ((double2 *)rec)[1] = make_double2(P[0], P[1]);
+    ((double2 *)rec)[2] = make_double2(P[2], P[3]);
+    ((double2 *)rec)[3] = make_double2(P[4], P[5]);
+}
+
 // one feature point served by a 32-lane group: search, correspondence indices, seed of the second outer iteration and the
 // 64-B residual-block record of the solver
 __device__ __forceinline__ void correspond_group(const BatchView &b, const OdomView &o, int c, int k, int qi, int outer, int gl, int gbase)
@@ -801,19 +838,15 @@ __device__ __forceinline__ void correspond_group(const BatchView &b, const OdomV
     const double *x = o.state + c * 8;
     const int4 r = qi < n_sharp ? correspond_g32<true>(b, k, qi, x, gl, gbase, seed, closest) : correspond_g32<false>(b, k, qi, x, gl, gbase, seed, closest);
     if (gl == 0) { corr[qi] = r; if (outer == 0 && seed_c) seed_c[qi] = closest; }
-    // residual-block record for the solver: the feature point and its 2 (edge) or 3 (plane) partners, 64 B
-    if (gl < 4) {
+    // residual-block record for the solver: the feature point and its 2 (edge) or 3 (plane) partners, staged (64 B)
+    if (gl == 0) {
         const bool edge = qi < n_sharp;
         const float4 *cloud = edge ? b.less_sharp + (size_t)l * kMaxLessSharp : b.less_flat + b.off[l];
-        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (gl == 0) {
-            v = edge ? b.sharp[(size_t)k * kMaxSharp + qi] : b.flat[(size_t)k * kMaxFlat + (qi - n_sharp)];
-            v.w = __int_as_float(r.w);
-        } else if (r.w != 0) {
-            const int idx = gl == 1 ? r.x : (gl == 2 ? r.y : r.z);
-            if (idx >= 0) v = cloud[idx];
-        }
-        o.crec[((size_t)c * kMaxQueries + qi) * 4 + gl] = v;
+        float4 cp = edge ? b.sharp[(size_t)k * kMaxSharp + qi] : b.flat[(size_t)k * kMaxFlat + (qi - n_sharp)];
+        cp.w = __int_as_float(r.w);
+        float4 A = make_float4(0.f, 0.f, 0.f, 0.f), B = A, Cc = A;
+        if (r.w != 0) { if (r.x >= 0) A = cloud[r.x]; if (r.y >= 0) B = cloud[r.y]; if (r.z >= 0) Cc = cloud[r.z]; }
+        store_staged_record(o.crec + ((size_t)c * kMaxQueries + qi) * 4, cp, A, B, Cc);
     }
 }
 
@@ -826,13 +859,14 @@ __device__ __forceinline__ void correspond_wave(const BatchView &b, const OdomVi
     const double *x = o.state + c * 8;
     const int4 r = correspond_one(b, k, qi, x, lane);
     if (lane == 0) { corr[qi] = r; if (o.seed) o.seed[(size_t)c * kMaxQueries + qi] = -1; }
-    if (lane < 4) {
+    if (lane == 0) {
         const bool edge = qi < n_sharp;
         const float4 *cloud = edge ? b.less_sharp + (size_t)l * kMaxLessSharp : b.less_flat + b.off[l];
-        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (lane == 0) { v = edge ? b.sharp[(size_t)k * kMaxSharp + qi] : b.flat[(size_t)k * kMaxFlat + (qi - n_sharp)]; v.w = __int_as_float(r.w); }
-        else if (r.w != 0) { const int idx = lane == 1 ? r.x : (lane == 2 ? r.y : r.z); if (idx >= 0) v = cloud[idx]; }
-        o.crec[((size_t)c * kMaxQueries + qi) * 4 + lane] = v;
+        float4 cp = edge ? b.sharp[(size_t)k * kMaxSharp + qi] : b.flat[(size_t)k * kMaxFlat + (qi - n_sharp)];
+        cp.w = __int_as_float(r.w);
+        float4 A = make_float4(0.f, 0.f, 0.f, 0.f), B = A, Cc = A;
+        if (r.w != 0) { if (r.x >= 0) A = cloud[r.x]; if (r.y >= 0) B = cloud[r.y]; if (r.z >= 0) Cc = cloud[r.z]; }
+        store_staged_record(o.crec + ((size_t)c * kMaxQueries + qi) * 4, cp, A, B, Cc);
     }
 }
 
@@ -911,29 +945,6 @@ constexpr int kLmW = kLmT / 64;
 // bar is a tolerance (1e-9 against the oracle's loop), and with -ffp-contract=off every a * b + c of the 6 x 6 normal equations is two
 // dependent instructions on the one wave per SIMD that runs a chain's solve.  The de-skew transform of the SEARCH (quat_rotate in the
 // correspondence kernels) stays uncontracted: its float result must equal the oracle's bit for bit.
-// A staged residual block (64 B in LDS, planes of 16 B): (cp, kind) as float4, then six doubles that do not depend on the pose and
-// are computed once per launch instead of once per evaluation (up to nine per launch):
-//   edge   a, e^ = (a - b) / |a - b|:          r = (lp - a) x e^   [= ((lp - a) x (lp - b)) / |a - b| since (lp - a) x (lp - a) = 0],  d r / d lp = -[e^]_x
-//   plane  j, n = normalised((j - l) x (j - m)):  r = (lp - j) . n,  d r / d lp = n^T
-__device__ __forceinline__ void stage_block(const float4 cp, const float4 A, const float4 B, const float4 Cc, double *P)
-{
-    const int kind = __float_as_int(cp.w);
-    if (kind == 1) {
-        const double ex = (double)A.x - (double)B.x, ey = (double)A.y - (double)B.y, ez = (double)A.z - (double)B.z;
-        const double inv = 1.0 / sqrt(ex * ex + ey * ey + ez * ez);
-        P[0] = (double)A.x; P[1] = (double)A.y; P[2] = (double)A.z;
-        P[3] = ex * inv; P[4] = ey * inv; P[5] = ez * inv;
-    } else {
-        const double jx = (double)A.x, jy = (double)A.y, jz = (double)A.z;
-        const double ux = jx - (double)B.x, uy = jy - (double)B.y, uz = jz - (double)B.z;
-        const double wx = jx - (double)Cc.x, wy = jy - (double)Cc.y, wz = jz - (double)Cc.z;
-        double nx = uy * wz - uz * wy, ny = uz * wx - ux * wz, nz = ux * wy - uy * wx;
-        const double nn = sqrt(nx * nx + ny * ny + nz * nz);
-        if (nn > 0.0) { nx /= nn; ny /= nn; nz /= nn; }
-        P[0] = jx; P[1] = jy; P[2] = jz; P[3] = nx; P[4] = ny; P[5] = nz;
-    }
-}
-
 // One Jacobian row of a residual block: d r / d lp = d (3-vector), scaled by sr.  d lp / d(local rotation) = -2 [R v]_x: the reference
 // differentiates the polynomial lp = v + 2 w (u x v) + 2 u x (u x v) with respect to the four quaternion components and multiplies by
 // the 4 x 3 plus-Jacobian of ceres::EigenQuaternionParameterization (x_new = (delta, 1) (x) x, a rotation by 2 |delta| in front of R);
@@ -1017,8 +1028,8 @@ struct LmRec {
     }
 };
 
-// Sum over all residual blocks of a chain by the kLmT threads of its workgroup (wave butterfly, then the wave partials are added in
-// fixed order); the sums -- H (21, upper triangle row by row), g (6), cost -- are left in LDS (s_sum) for every thread to read: the
+// Sum over all residual blocks of a chain by the kLmT threads of its workgroup (a reduce-scatter inside every wave, then the wave partials
+// are added in fixed order); the sums -- H (21, upper triangle row by row), g (6), cost -- are left in LDS (s_sum) for every thread to read: the
 // trust-region code below keeps no copy of them in registers.  rec = the chain's staged blocks (LmRec).
 template <bool kJac, int kPlanes>
 __device__ __forceinline__ void evaluate_block(const LmRec<kPlanes> rec, int n_edge, int nq, const double *x, double (*s_red)[28], double *s_sum)
@@ -1070,20 +1081,24 @@ __device__ __forceinline__ void evaluate_block(const LmRec<kPlanes> rec, int n_e
             cur = nxt;
         }
     }
-    acc.cost = wave_sum_d(acc.cost);
     if (kJac) {
+        // the 28 sums of the wave as one reduce-scatter (wave_sum28.hpp: wave_sum_d's pairs and order, so its bytes; 32 exchanges and adds
+        // instead of 168): lanes 2 i and 2 i + 1 end with slot i, and lane 2 i stores it -- one store instruction per wave
+        double v[32];
 #pragma unroll
-        for (int i = 0; i < 21; i++) acc.H[i] = wave_sum_d(acc.H[i]);
+        for (int i = 0; i < 21; i++) v[i] = acc.H[i];
 #pragma unroll
-        for (int i = 0; i < 6; i++) acc.g[i] = wave_sum_d(acc.g[i]);
-    }
-    __syncthreads();   // previous readers of s_red are done
-    if (lane == 0) {
-        s_red[wave][27] = acc.cost;
-        if (kJac) {
-            for (int i = 0; i < 21; i++) s_red[wave][i] = acc.H[i];
-            for (int i = 0; i < 6; i++) s_red[wave][21 + i] = acc.g[i];
-        }
+        for (int i = 0; i < 6; i++) v[21 + i] = acc.g[i];
+        v[27] = acc.cost;
+#pragma unroll
+        for (int i = 28; i < 32; i++) v[i] = 0.0;
+        wave_sum28_scatter(Ws28Wave{ lane }, v);
+        __syncthreads();   // previous readers of s_red are done
+        if (!(lane & 1) && lane < 56) s_red[wave][lane >> 1] = v[0];
+    } else {
+        acc.cost = wave_sum_d(acc.cost);       // one sum: the butterfly
+        __syncthreads();   // previous readers of s_red are done
+        if (lane == 0) s_red[wave][27] = acc.cost;
     }
     __syncthreads();
     if (tid < 28 && (kJac || tid == 27)) {
@@ -1138,15 +1153,15 @@ __global__ __launch_bounds__(kLmT) __attribute__((amdgpu_num_vgpr(LMONO_LM_VGPRS
     const LmRec<kPlanes> rec = { s_rec, kPlanes < 4 ? o.lmrec + (size_t)c * (4 - kPlanes) * kMaxQueries : nullptr };
     int n_used = 0;
     {
-        // one record per thread and round: its four 16-B quarters are requested together, the pose-independent part of the
-        // residual block is computed once (stage_block) and the block is staged as (cp, kind) + six doubles
+        // one record per thread and round: its four 16-B quarters are requested together.  The record is the staged block already (the
+        // searches' store_staged_record): here it is masked, counted and moved to where the sweeps read it
         const bool thin = lead_in_thinned(o, k, s);
         for (int qi = tid; qi < nq; qi += kLmT) {
             float4 cp = crec[qi * 4];
-            const float4 A = crec[qi * 4 + 1], B = crec[qi * 4 + 2], Cc = crec[qi * 4 + 3];
+            const double2 p01 = ((const double2 *)crec)[qi * 4 + 1], p23 = ((const double2 *)crec)[qi * 4 + 2], p45 = ((const double2 *)crec)[qi * 4 + 3];
             if (thin && (qi % kThinBlocks) % kThinStride != 0) cp.w = 0.f;       // not searched in this launch: a stale record
-            double P[6] = { 0.0, 0.0, 0.0, 0.0, 0.0, 0.0 };
-            if (__float_as_int(cp.w) != 0) { stage_block(cp, A, B, Cc, P); n_used++; }
+            if (__float_as_int(cp.w) != 0) n_used++;
+            const double P[6] = { p01.x, p01.y, p23.x, p23.y, p45.x, p45.y };
             rec.put(qi, cp, P);
         }
     }

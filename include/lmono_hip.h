@@ -123,7 +123,9 @@ int lmono_batch_counts(lmono_ctx *, lmono_scan_batch *, int32_t *counts_h);
 /* which: 0 ring-sorted cloud, 1 sharp, 2 less_sharp, 3 flat, 4 less_flat.  out_h: [cap][4] float32.
  * Returns the number of points copied (>= 0) or a negative error.                               */
 int lmono_batch_get_cloud(lmono_ctx *, lmono_scan_batch *, int scan, int which, float *out_h, int cap);
-/* curvature (float32) and label (int32: 2 sharp, 1 less sharp, -1 flat, 0 other) of the sorted cloud */
+/* curvature (float32) and label (int32: 2 sharp, 1 less sharp, -1 flat, 0 other) of the sorted cloud.  The registration keeps no
+ * curvature array (k_select computes what it needs per sector): with curv_h set, this call computes the scan's curvature on the
+ * context stream into a buffer of its own and changes nothing that a later registration or odometry call reads. */
 int lmono_batch_get_curvature(lmono_ctx *, lmono_scan_batch *, int scan, float *curv_h, int32_t *label_h, int cap);
 
 /* ---- LiDAR odometry: A-LOAM laserOdometry main loop + lidarFactor.hpp + ceres::Solve ------- *
@@ -848,7 +850,7 @@ int lmono_pose_rebase_d(lmono_ctx *, const double *bases_d, int n_bases, double 
 
 /* Device-time accounting with hipEvents recorded on the context stream around every kernel group of every
  * lmono_scanreg_batch / lmono_odom_batch call since the last reset.  ms_out[0..8] = summed milliseconds of:
- * [0] front end total, [1] odometry total, [2] k_ring_sort, [3] k_curvature, [4] k_select, [5] k_voxel,
+ * [0] front end total, [1] odometry total, [2] k_ring_sort, [3] k_curvature (an empty slot: k_select computes the curvature), [4] k_select, [5] k_voxel,
  * [6] k_compact_index (compaction + line index), [7] k_grid_build, [8] k_line_index (the full-width launch),
  * [9] all k_correspond launches, [10] all k_lm_solve launches, [11] number of k_correspond (= k_lm_solve)
  * launches.  Both calls synchronise the stream.                                                            */

@@ -28,9 +28,7 @@ struct BatchView {
     float min_range;
     // ---- ring-sorted cloud (same offsets as the input; n_cloud[s] valid points)
     float4 *cloud;           // [total] x y z (ring + 0.1 relTime)
-    float *curv;             // [total]
     int8_t *label;           // [total]
-    uint8_t *gap;            // [total] gap[i] = |p[i+1]-p[i]|^2 > 0.05
     int8_t *ring_tmp;        // [total] ring id per input point (-1 = discarded)
     int *seg_hist;           // [(total >> 10) + n_scans + 1][64] ring histogram of every 1024-point segment, then its exclusive prefix within the scan
     int *scan_ends;          // [n_scans][2] first / last valid input point (-1: none)

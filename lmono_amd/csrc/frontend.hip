@@ -1,12 +1,12 @@
 // lmono_amd/csrc/frontend.hip -- gfx950 kernels of the LiDAR front end (A-LOAM scanRegistration;
 // source absent from the reference tree, behavioural spec SURVEY.md Appendix A.1).
 //
-// Five kernel stages per batch of scans over HBM-resident SoA/float4 pools:
+// Four kernel stages per batch of scans over HBM-resident SoA/float4 pools:
 //   k_ring_*     filter, ring id, azimuth, stable counting sort into ring-major order: four tile-parallel launches (ends, tag,
 //                offsets, scatter); every wave owns a 1024-point segment in both passes, no barriers inside the passes; the tag
 //                pass decides ring and half sweep without an arctangent (ring_decide.hpp), fp64 forms inside the guard bands
-//   k_curvature  one workgroup per 1024-point tile: LDS tile with +-5 halo, curvature and neighbour-gap flags
-//   k_select     one wave per (scan, ring), a lane holds 5 / 6 / 11 consecutive points of a sector in registers: the <= 20 edge picks are
+//   k_select     one wave per (scan, ring), a lane holds 5 / 6 / 11 consecutive points of a sector in registers: their curvature and the
+//                neighbour-gap flags around them are computed from those registers and the next lanes' (curv_window.hpp); the <= 20 edge picks are
 //                the head of an independent set that parallel rounds settle (sel_rounds.hpp: winners against the ten neighbours in the
 //                lane's and the next lanes' registers, DPP wave shifts), ranked one member per lane; the <= 4 planar picks are repeated
 //                64-lane arg-min reductions (DPP) with neighbour suppression; no sort needed;
@@ -15,8 +15,12 @@
 //                ballots, bucket sort of the segment keys in LDS; <9 slots> / <16 slots> instantiations + work list)
 //   k_compact_index  one workgroup per scan: prefix sums over (ring, sector), compaction of the four clouds, line tables, and the (scan line,
 //                azimuth bin) index of the two "last" clouds (the steps of line_index.hip) built while their points pass through
+// and, outside the registration:
+//   k_curvature  one workgroup per 1024-point tile of ONE scan: LDS tile with +-5 halo, the curvature of every point, for the host
+//                accessor lmono_batch_get_curvature
 // Arithmetic is float/double exactly as the CPU restatement evaluates it (compiled with -ffp-contract=off).
 #include "batch.hpp"
+#include "curv_window.hpp"
 #include "ring_decide.hpp"
 #include "sel_rounds.hpp"
 #include "vox_runs.hpp"
@@ -293,11 +297,12 @@ __global__ __launch_bounds__(kRtT) void k_ring_scatter(BatchView b)
 }
 
 // ------------------------------------------------------------------------------------------------
+// k_curvature: the curvature of every point of ONE scan's ring-sorted cloud, for the host accessor (lmono_batch_get_curvature).  The
+// registration does not run it: k_select computes the curvature and the gap flags of a sector from the cloud (curv_window.hpp).
 constexpr int kCurvTile = 1024;
 
-__global__ __launch_bounds__(256) void k_curvature(BatchView b)
+__global__ __launch_bounds__(256) void k_curvature(BatchView b, int s, float *curv)
 {
-    const int s = b.scan0 + blockIdx.y;
     const int n = b.n_cloud[s];
     const int t0 = blockIdx.x * kCurvTile;
     if (t0 >= n) return;
@@ -322,13 +327,7 @@ __global__ __launch_bounds__(256) void k_curvature(BatchView b)
             const float dz = sz[q - 5] + sz[q - 4] + sz[q - 3] + sz[q - 2] + sz[q - 1] - 10 * sz[q] + sz[q + 1] + sz[q + 2] + sz[q + 3] + sz[q + 4] + sz[q + 5];
             cv = dx * dx + dy * dy + dz * dz;
         }
-        b.curv[off + i] = cv;
-        unsigned char g = 0;
-        if (i + 1 < n) {
-            const float gx = sx[q + 1] - sx[q], gy = sy[q + 1] - sy[q], gz = sz[q + 1] - sz[q];
-            g = ((double)(gx * gx + gy * gy + gz * gz) > 0.05) ? 1 : 0;
-        }
-        b.gap[off + i] = g;
+        curv[i] = cv;
     }
 }
 
@@ -342,6 +341,9 @@ __global__ __launch_bounds__(256) void k_curvature(BatchView b)
 // The flat picks run exactly so.  The sharp picks do not take 21 reductions one after the other: the points that such a
 // walk takes are the 20 of highest key of an independent set that parallel rounds find (sel_rounds.hpp, two rounds for
 // most sectors), and they are ranked one per lane afterwards.
+// The curvature is not read from memory: a sector's elements and their ten neighbours are the registers of the lane and of the two lanes
+// next to it, so the wave computes curvature and gap flags of the sector from the ring-sorted cloud itself (curv_window.hpp), with
+// k_curvature's operands in k_curvature's order.  Sector elements lie in ring-local [5, len - 6]: every neighbour is in the same ring.
 constexpr int kSelMaxPerLane = (kRingCap / 6 + 1 + 63) / 64;   // 11 elements per lane for the largest legal sector
 
 // key of a sector element: hi = curvature bits, lo = (index << 8 | suppression reach).  Ordering by (hi, lo) = ordering by
@@ -358,23 +360,79 @@ __device__ __forceinline__ unsigned int lane_behind(unsigned int v) { return (un
 // neighbours that a round of the sharp picks compares an element with are registers of the lane or of the two lanes next to it
 constexpr int kSelScratch = 64 * 8;      // per wave: one (curvature bits, index | reach) pair per lane, the members of a sector for ranking
 
+// the lanes of curv_window.hpp: the shifts above with bound_ctrl off, so that the lane at the wave's end keeps `old`
+struct SelLanes {
+    typedef unsigned int bits;
+    __device__ __forceinline__ unsigned int before(unsigned int v, unsigned int old) const { return (unsigned int)__builtin_amdgcn_update_dpp((int)old, (int)v, 0x138, 0xf, 0xf, false); }
+    __device__ __forceinline__ unsigned int behind(unsigned int v, unsigned int old) const { return (unsigned int)__builtin_amdgcn_update_dpp((int)old, (int)v, 0x130, 0xf, 0xf, false); }
+    __device__ __forceinline__ float before(float v, float old) const { return __uint_as_float(before(__float_as_uint(v), __float_as_uint(old))); }
+    __device__ __forceinline__ float behind(float v, float old) const { return __uint_as_float(behind(__float_as_uint(v), __float_as_uint(old))); }
+};
+
 template <int M>
-__device__ __forceinline__ void select_sector(int lane, int j, int sp, int slen, int rbeg, const float *curv, unsigned char *picked,
-                                              signed char *label, const unsigned long long *gap, int *sel_sh, int *sel_sh_n, int *sel_fl, int *sel_fl_n,
+__device__ __forceinline__ void select_sector(int lane, int j, int sp, int slen, int rbeg, const float4 *pts, unsigned char *picked,
+                                              signed char *label, int *sel_sh, int *sel_sh_n, int *sel_fl, int *sel_fl_n,
                                               unsigned int *scratch)
 {
     unsigned int kh[M], kl[M];
     unsigned int dead = 0, big = 0, small = 0;     // bit m: suppressed / out of range; curvature > 0.1; < 0.1
+    // (the lane as a value of this sector's own: what derives from it -- lane M + m, the ballot masks, the halo's side -- is then a few
+    // instructions per sector, where the compiler otherwise computes all of it once per ring for the three instantiations and keeps it
+    // in scratch)
+    asm volatile("" : "+v"(lane));
     const int e0 = lane * M;
-    // gap flags around the lane's elements, one window per lane: bit k = gap flag of point sp + e0 - 5 + k, k < M + 10 (two 8-byte LDS
-    // reads; sp >= 5, and a lane that holds an element reads inside the ring's words)
-    // A lane behind the sector's end reads the sector's last point instead and keeps nothing of it: no branch around the loads.
+    // The curvature of the lane's elements and the gap flags around them, from the ring's points (pts = the ring's first; curv_window.hpp).
+    // Element e of the sector is ring point sp + e, and its windows read the points sp - 5 .. ep + 5 = sp + slen + 4, all of them in the
+    // ring (sp >= 5, ep <= len - 6).  A lane loads its M points whether they are elements or not: the lanes behind the sector's end hold
+    // the points that follow it, which is the halo of the last elements, and read point ep + 5 again where they would go further (what
+    // they compute is used by nobody).  Lane 0 fetches the five points before the sector, lane 63 the five behind its own.
+    // gwin: bit k = gap flag of point sp + e0 - 5 + k, k < M + 9.
+    float cv[M];
     unsigned int gwin;
     {
-        const int jw = sp + min(e0, slen - 1) - 5;
-        const unsigned long long wa = gap[jw >> 6], wb = gap[(jw >> 6) + 1];
-        const int sh = jw & 63;
-        gwin = (unsigned int)((wa >> sh) | (sh ? wb << (64 - sh) : 0ull));
+        // (every lane behind lane 0 loads lane 63's halo, one address for 63 lanes: cheaper than a branch around the loads)
+        const int last = slen + 4;
+        const float4 *hp = pts + sp + (lane == 0 ? -kCurvReach : min(64 * M, last));
+        const int hmax = lane == 0 ? kCurvReach : max(last - 64 * M, 0);       // halo point d stands at hp[min(d, hmax)]
+        const SelLanes lanes;
+        unsigned int hb;
+        float hx0, hy0, hz0;
+        {
+            float h[3][kCurvReach + 1];
+#pragma unroll
+            for (int d = 0; d <= kCurvReach; d++) {
+                const float4 p = hp[min(d, hmax)];          // lane 0's sixth: the sector's first point
+                h[0][d] = p.x; h[1][d] = p.y; h[2][d] = p.z;
+            }
+            hb = curv_halo_flags<unsigned int>(h[0], h[1], h[2]);
+            hx0 = h[0][0]; hy0 = h[1][0]; hz0 = h[2][0];
+        }
+        float o[3][M];
+#pragma unroll
+        for (int m = 0; m < M; m++) {
+            const float4 p = pts[sp + min(e0 + m, last)];
+            o[0][m] = p.x; o[1][m] = p.y; o[2][m] = p.z;
+        }
+        gwin = curv_gap_window<M>(lanes, o[0], o[1], o[2], hx0, hy0, hz0, hb);
+        // (the halo again, one coordinate at a time: fifteen registers through the three passes cost more than these loads)
+#pragma unroll
+        for (int c = 0; c < 3; c++) {
+            float h[kCurvReach];
+#pragma unroll
+            for (int d = 0; d < kCurvReach; d++) h[d] = ((const float *)(hp + min(d, hmax)))[c];
+            if constexpr (M <= 6) {
+                curv_window_coord<M>(lanes, o[c], h, c == 0, cv);
+            } else {
+                // the wide instantiation has no registers for 33 coordinates beside a window of 21: it fetches its points again
+                // (through an index the compiler cannot see through, or it keeps the first fetch's registers after all)
+                float oc[M];
+                int ec = e0;
+                asm volatile("" : "+v"(ec));
+#pragma unroll
+                for (int m = 0; m < M; m++) oc[m] = ((const float *)(pts + sp + min(ec + m, last)))[c];
+                curv_window_coord<M>(lanes, oc, h, c == 0, cv);
+            }
+        }
     }
     // (double)c > 0.1 and (double)c < 0.1 as float compares: 0.1f is the smallest float above the double 0.1, so c > 0.1 iff c >= 0.1f and
     // c < 0.1 iff c < 0.1f, for every float c (a NaN fails both either way)
@@ -383,7 +441,7 @@ __device__ __forceinline__ void select_sector(int lane, int j, int sp, int slen,
         const int e = e0 + m;
         const bool in = e < slen;
         const int i = sp + min(e, slen - 1);
-        const float c = curv[i];
+        const float c = cv[m];
         // suppression reach: the neighbour walk marks l = 1..5 forward while the gap before point i+l is short, and the same backward --
         // the zero runs above / below bit i of the ring's gap BIT mask
         const unsigned int win = gwin >> m;                                                       // bit k = gap flag of point i - 5 + k
@@ -519,11 +577,11 @@ __device__ __forceinline__ void select_sector(int lane, int j, int sp, int slen,
 
 // The 11-element instantiation (rings of the second launch) as a function of its own: its registers and spills stay out of the code
 // of the 5- and 6-element sectors that every HDL-64 ring runs.
-__device__ __noinline__ void select_sector_wide(int lane, int j, int sp, int slen, int rbeg, const float *curv, unsigned char *picked,
-                                                signed char *label, const unsigned long long *gap, int *sel_sh, int *sel_sh_n, int *sel_fl, int *sel_fl_n,
+__device__ __noinline__ void select_sector_wide(int lane, int j, int sp, int slen, int rbeg, const float4 *pts, unsigned char *picked,
+                                                signed char *label, int *sel_sh, int *sel_sh_n, int *sel_fl, int *sel_fl_n,
                                                 unsigned int *scratch)
 {
-    select_sector<kSelMaxPerLane>(lane, j, sp, slen, rbeg, curv, picked, label, gap, sel_sh, sel_sh_n, sel_fl, sel_fl_n, scratch);
+    select_sector<kSelMaxPerLane>(lane, j, sp, slen, rbeg, pts, picked, label, sel_sh, sel_sh_n, sel_fl, sel_fl_n, scratch);
 }
 
 // wave-uniform values as scalars (the compiler cannot prove uniformity of what is loaded through a per-wave index)
@@ -540,7 +598,7 @@ template <typename T> __device__ __forceinline__ T *uni_ptr(T *p)
     return (T *)(GT *)uni64((long long)p);
 }
 
-// LDS slice of one wave for rings of up to `cap` points: picked bytes + the ring's gap bit mask (cap bytes reserved)
+// LDS slice of one wave for rings of up to `cap` points: picked bytes (the second half held the ring's gap bit mask and is not used)
 __host__ __device__ constexpr int sel_slice_bytes(int cap) { return 2 * cap; }
 
 // one ring by one wave; cap = ring points the wave's LDS slice (sel_slice_bytes(cap) at smem_w) can hold
@@ -567,29 +625,22 @@ __device__ __forceinline__ void select_ring(BatchView &b, int r, int s, int lane
         return;
     }
     // labels go straight to HBM (zeroed here, ~144 single-byte stores per ring afterwards): the LDS slice only holds the
-    // picked and gap bytes
+    // picked bytes
     unsigned char *picked = smem_w;
     signed char *label = uni_ptr((signed char *)(b.label + off + rbeg));
-    const float *curv = uni_ptr(b.curv + off + rbeg);
+    const float4 *pts = uni_ptr((const float4 *)(b.cloud + off + rbeg));
     const int span = E - S;
-    // gap flags of the ring as a bit mask, one 64-bit word per 64 points (+ one word of padding read by the last elements' windows)
-    unsigned long long *gap = (unsigned long long *)(picked + cap);
-    for (int i0 = 0; i0 < len + 64; i0 += 64) {
-        const int i = i0 + lane;
-        unsigned char g = 0;
-        if (i < len) { picked[i] = 0; label[i] = 0; g = b.gap[off + rbeg + i]; }
-        const unsigned long long mk = __ballot(g != 0);
-        if (lane == 0) gap[i0 >> 6] = mk;
-    }
+#pragma unroll 1
+    for (int i = lane; i < len; i += 64) { picked[i] = 0; label[i] = 0; }
     __builtin_amdgcn_wave_barrier();
     for (int j = 0; j < kSectors; j++) {
         const int sp = 5 + span * j / 6;
         const int ep = 5 + span * (j + 1) / 6 - 1;
         const int slen = ep - sp + 1;
         // HDL-64-sized sectors (<= 320 / <= 384 points) take the 5- / 6-slot instantiations, longer rings the full one
-        if (slen <= 5 * 64) select_sector<5>(lane, j, sp, slen, rbeg, curv, picked, label, gap, sel_sh, sel_sh_n, sel_fl, sel_fl_n, scratch);
-        else if (slen <= 6 * 64) select_sector<6>(lane, j, sp, slen, rbeg, curv, picked, label, gap, sel_sh, sel_sh_n, sel_fl, sel_fl_n, scratch);
-        else select_sector_wide(lane, j, sp, slen, rbeg, curv, picked, label, gap, sel_sh, sel_sh_n, sel_fl, sel_fl_n, scratch);
+        if (slen <= 5 * 64) select_sector<5>(lane, j, sp, slen, rbeg, pts, picked, label, sel_sh, sel_sh_n, sel_fl, sel_fl_n, scratch);
+        else if (slen <= 6 * 64) select_sector<6>(lane, j, sp, slen, rbeg, pts, picked, label, sel_sh, sel_sh_n, sel_fl, sel_fl_n, scratch);
+        else select_sector_wide(lane, j, sp, slen, rbeg, pts, picked, label, sel_sh, sel_sh_n, sel_fl, sel_fl_n, scratch);
     }
 }
 

@@ -20,6 +20,8 @@ struct lmono_scan_batch {
     hipEvent_t staged_ev = nullptr, in_free_ev = nullptr;   // lmono_batch_stage_h: copy finished / the front end has read the staging buffer
     int64_t staged_points = -1;
     std::vector<int> feat_h;       // host copy of feat_n [n_scans][4], fetched on first use after a registration
+    float *curv = nullptr;         // lmono_batch_get_curvature's curvature of the one scan asked for (k_curvature on demand)
+    size_t curv_cap = 0;
     // odometry workspace
     int chains_cap = 0;
     double *state = nullptr, *incr = nullptr, *poses = nullptr, *xq = nullptr;
@@ -61,7 +63,7 @@ extern "C" lmono_scan_batch *lmono_batch_create(lmono_ctx *c, int n_cap, int64_t
     DevOwner &m = b->mem;
     bool ok = true;
     ok = ok && m.alloc(b->off_d, N + 1);
-    ok = ok && m.alloc(v.cloud, T) && m.alloc(v.curv, T) && m.alloc(v.label, T) && m.alloc(v.gap, T);
+    ok = ok && m.alloc(v.cloud, T) && m.alloc(v.label, T);
     ok = ok && m.alloc(v.ring_tmp, T);
     ok = ok && m.alloc(v.seg_hist, ((T >> 10) + N + 1) * 64) && m.alloc(v.scan_ends, N * 2) && m.alloc(v.scan_half, N) && m.alloc(v.scan_ori, N * 4);
     ok = ok && m.alloc(v.ring_begin, N * 65) && m.alloc(v.n_cloud, N) && m.alloc(v.status, N);
@@ -109,8 +111,7 @@ static int scanreg_launch(lmono_ctx *c, lmono_scan_batch *b, int scan0, int n_sc
     hipLaunchKernelGGL(k_ring_offsets, dim3(n_scans), dim3(64), 0, st, v);
     if (rt_tiles > 0) hipLaunchKernelGGL(k_ring_scatter, dim3(rt_tiles, n_scans), dim3(kRtT), 0, st, v);
     HIP_TRY(c, hipEventRecord(c->ev[1], st));
-    const int tiles = (int)((max_pts + kCurvTile - 1) / kCurvTile);
-    if (tiles > 0) hipLaunchKernelGGL(k_curvature, dim3(tiles, n_scans), dim3(256), 0, st, v);
+    // (nothing between these two: k_select computes the curvature itself; the slot keeps the layout of lmono_timing_read)
     HIP_TRY(c, hipEventRecord(c->ev[2], st));
     // the kernels below run one workgroup per ring of the sensor; the counters of the rings it cannot produce stay zero
     const int n_rings = rings_used(b->v.n_lines);
@@ -317,7 +318,15 @@ extern "C" int lmono_batch_get_curvature(lmono_ctx *c, lmono_scan_batch *b, int 
     int n = 0;
     HIP_TRY(c, hipMemcpy(&n, b->v.n_cloud + scan, sizeof(int), hipMemcpyDeviceToHost));
     if (n > cap) { c->err = "get_curvature: output capacity too small"; return LMONO_ECAPACITY; }
-    if (curv_h && n > 0) HIP_TRY(c, hipMemcpy(curv_h, b->v.curv + b->off_h[scan], sizeof(float) * n, hipMemcpyDeviceToHost));
+    if (curv_h && n > 0) {
+        // no registration keeps the curvature: k_curvature runs here for the one scan, into a buffer of the accessor's own (grow_replace: the
+        // stream is idle above and below)
+        if (!b->mem.grow_replace(b->curv, b->curv_cap, (size_t)n, /*floor=*/1 << 17)) { c->err = "get_curvature: hipMalloc failed"; return LMONO_ENOMEM; }
+        hipLaunchKernelGGL(k_curvature, dim3((n + kCurvTile - 1) / kCurvTile), dim3(256), 0, c->stream, b->v, scan, b->curv);
+        if (int rc = check_launch(c, "k_curvature")) return rc;
+        HIP_TRY(c, hipMemcpyAsync(curv_h, b->curv, sizeof(float) * n, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+    }
     if (label_h && n > 0) {
         std::vector<int8_t> tmp(n);
         HIP_TRY(c, hipMemcpy(tmp.data(), b->v.label + b->off_h[scan], n, hipMemcpyDeviceToHost));

@@ -572,7 +572,8 @@ int        lmono_voxel_map_insert_aligned(lmono_ctx *, int n, lmono_voxel_map *c
 /* ---- map builder: surface normals and curvature of a cloud -------------------------------------------------
  * The pcl::NormalEstimation with setRadiusSearch(0.05) on both clouds that opens MapBuilder::alignmentToMap, the coarse map-to-map
  * alignment the reference carries commented out (mono_lidar_mapping/src/map_builder/Map_Builder.cc:110-210); every later stage of that
- * function (SIFT keypoints, FPFH, the sample-consensus initial alignment) consumes these normals, and none of them is provided yet.
+ * function (SIFT keypoints, FPFH, the sample-consensus initial alignment) consumes these normals; of those the FPFH descriptors are
+ * provided (lmono_fpfh_*, below) and the sample-consensus initial alignment (lmono_sacia_*, below), the SIFT keypoints are not yet.
  * A definition of this project (lmono_amd/csrc/normals.hpp): the neighbours of a point are all valid points, itself and duplicates
  * included, within radius of it (d2 <= radius^2 in float32); their offsets from the point in 2^-16 m fixed point about the middle of
  * the cloud's bounding box give exact integer sums; the scatter matrix of those sums is diagonalised in fp64 (cyclic Jacobi, 8 sweeps);
@@ -604,6 +605,58 @@ int        lmono_normals_compute_map(lmono_ctx *, lmono_normals *, lmono_voxel_m
  * return the count (and copy when a pointer is not NULL). */
 int64_t    lmono_normals_read(lmono_ctx *, lmono_normals *, lmono_normal *out_h, uint32_t *count_h, int64_t cap);
 int64_t    lmono_normals_cloud(lmono_ctx *, lmono_normals *, lmono_point_rgb *out_h, int64_t cap);
+
+/* ---- map builder: FPFH descriptors at keypoints ----------------------------------------------------------------
+ * The pcl::FPFHEstimation with setSearchSurface and setRadiusSearch(0.05) of MapBuilder::alignmentToMap
+ * (mono_lidar_mapping/src/map_builder/Map_Builder.cc:110-210, commented out in the reference).  The surface is the cloud of a normals
+ * handle after a compute, read in device memory with its records; the keypoints are m <= max_keypoints finite positions on the host,
+ * not necessarily points of the cloud (the reference's SIFT keypoint detector is not provided: one point per voxel of a map at a
+ * coarse leaf serves).  A definition of this project (lmono_amd/csrc/fpfh.hpp): PCL's pair features in fp64 without transcendentals,
+ * three 11-bin histograms per surface point within radius of a keypoint (integer counts), and per keypoint their sum under the
+ * integer weight (uint64)(2^40 / (max(d2, 2^-20) * pairs)) in exact hi / lo words, each sub-histogram scaled to sum to 100 and
+ * written as 33 floats (FPFHSignature33's layout).  A surface point at the keypoint counts with the largest weight (PCL skips it).
+ * A descriptor is a pure function of the SET of surface points with normals and of the keypoint: the same bytes for every point
+ * order, grid tuning (cell, max_rings) and batch.  Parity with PCL is unpinned.  Limits: max_points <= 2^26, max_keypoints <= 4096,
+ * 0 < radius <= 4, (max_rings - 0.25) cell >= radius; the radius is independent of the normals'.
+ * Per keypoint: the descriptor, the number of contributing surface points, and a flag (0: none contributed, the descriptor is 33 zeros).
+ * stats [8] per stream: keypoints in, with a descriptor, without, surface points with an SPFH, sum of their pair counts, largest
+ * pair count, sum of the keypoints' contributing points, largest.  A normals handle without a result (or with an empty one) and a
+ * non-finite keypoint return LMONO_EINVAL, m > max_keypoints or a cloud above max_points LMONO_ECAPACITY, all before any launch;
+ * m == 0 is a successful empty result.  Every compute replaces the handle's last result. */
+typedef struct lmono_fpfh lmono_fpfh;
+lmono_fpfh *lmono_fpfh_create(lmono_ctx *, int64_t max_points, int64_t max_keypoints, float radius, float cell, int max_rings);
+void       lmono_fpfh_destroy(lmono_fpfh *);
+/* the default cell for radius at max_rings = 2: lmono_normals_default_cell's rule */
+float      lmono_fpfh_default_cell(float radius);
+/* keypoints_h: [m][3] float */
+int        lmono_fpfh_compute(lmono_ctx *, lmono_fpfh *, lmono_normals *, const float *keypoints_h, int64_t m, int64_t *stats);
+/* n distinct handles, each over one normals handle (which may repeat) and its own keypoints; one launch per phase for all streams.
+ * A stream's bytes do not depend on the batch it travels in. */
+int        lmono_fpfh_compute_batch(lmono_ctx *, int n, lmono_fpfh *const *fpfhs, lmono_normals *const *normals, const float *const *keypoints_h, const int64_t *ms, int64_t *stats);
+/* the last result in keypoint order: descriptors [m][33], contributing points [m], flags [m] (any pointer may be NULL), and the
+ * keypoints themselves.  Both return the count (and copy when a pointer is not NULL). */
+int64_t    lmono_fpfh_read(lmono_ctx *, lmono_fpfh *, float *desc_h, uint32_t *count_h, uint32_t *flag_h, int64_t cap);
+int64_t    lmono_fpfh_keypoints(lmono_ctx *, lmono_fpfh *, float *out_h, int64_t cap);
+
+/* ---- map builder: sample-consensus initial alignment on FPFH descriptors ------------------------------------
+ * Replaces the pcl::SampleConsensusInitialAlignment of MapBuilder::alignmentToMap (computeInitialAlignment: setMinSampleDistance(0.5),
+ * setMaxCorrespondenceDistance(1.0), setMaximumIterations(30); mono_lidar_mapping/src/map_builder/Map_Builder.cc:110-210, commented out in
+ * the reference), a definition of this project (lmono_amd/csrc/sacia.hpp): per source keypoint the k_corr target keypoints of nearest
+ * descriptor, exactly, ties to the lowest index; hypothesis h draws three source keypoints at least min_sample_dist apart and one candidate
+ * of each from the PnP RANSAC's counter-based generator, fits them with the closed form of lmono_icp_*, and is scored by the integer sum of
+ * the squared distances to the nearest target keypoint, truncated at max_corr^2; the least (error, h) wins.  Keypoints without a descriptor
+ * take no part; fewer than 3 with one on either side, a handle without a result and a keypoint 2048 m or more from the first one of its
+ * side return LMONO_EINVAL.  0 <= min_sample_dist <= 4096, 0 < max_corr <= 16, k_corr in 1 .. 32, n_hyp in 1 .. 65536; launch_hyps: the
+ * hypotheses of one launch (0: all), which changes no result.  stats [8]: ok (0: every hypothesis was void, the handle then shows no
+ * transform), the winning h (-1), its error word, its inliers, void hypotheses, usable source keypoints, usable target keypoints, n_hyp. */
+typedef struct lmono_sacia lmono_sacia;
+lmono_sacia *lmono_sacia_create(lmono_ctx *, float min_sample_dist, float max_corr, int k_corr, int n_hyp, uint32_t seed, int launch_hyps);
+void       lmono_sacia_destroy(lmono_sacia *);
+int        lmono_sacia_align(lmono_ctx *, lmono_sacia *, lmono_fpfh *src, lmono_fpfh *tgt, int64_t *stats);
+/* the last align: its transform, row-major 3 x 4, what lmono_icp_set_guess takes (LMONO_EINVAL without one), and per hypothesis the
+ * error word (all ones: void) and the inliers; errors returns the count (and copies when a pointer is not NULL). */
+int        lmono_sacia_transform(lmono_ctx *, lmono_sacia *, double out[12]);
+int64_t    lmono_sacia_errors(lmono_ctx *, lmono_sacia *, uint64_t *err_h, uint32_t *inl_h, int64_t cap);
 
 /* ---- image feature tracker ---------------------------------------------------------------------------------
  * Replaces FeatureTracker::trackImage of the mono path, use_rejectF = 0 or 1 (lmono_tracker_set_reject_f) (mono_lidar_mapping/src/image_process/

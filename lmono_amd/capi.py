@@ -1197,6 +1197,108 @@ class SurfaceNormals(_Handle):
         return out[:n]
 
 
+class FpfhDescriptors(_Handle):
+    """FPFH descriptors at keypoints on the device (lmono_fpfh_*): the surface is the cloud of a SurfaceNormals after a
+    compute, read with its records in device memory; the keypoints are [m][3] float32 positions, not necessarily points of the cloud
+    (VoxelMap.read() at a coarse leaf gives serviceable ones).  compute* return the call's stats [keypoints in, with a descriptor,
+    without, surface points with an SPFH, sum of their pair counts, largest pair count, sum of the keypoints' contributing points,
+    largest]; read() gives (descriptors [m][33] float32, contributing points [m] uint32, flags [m] uint32) in keypoint order, 33 zeros
+    and flag 0 where no surface point contributed.  cell and max_rings tune the search grid and change no result (defaults:
+    lmono_fpfh_default_cell(radius) and 2).  An LmonoError carries the C return value in .code."""
+
+    _destroy = "lmono_fpfh_destroy"
+
+    def __init__(self, ctx, max_points, max_keypoints, radius=0.05, cell=None, max_rings=2):
+        super().__init__(ctx)
+        self.max_points, self.max_keypoints = int(max_points), int(max_keypoints)
+        self.stats = np.zeros(8, np.int64)
+        if cell is None:
+            cell = ctx.L.lmono_fpfh_default_cell(C.c_float(radius))
+        self._create("lmono_fpfh_create", int(max_points), int(max_keypoints), C.c_float(radius), C.c_float(cell), int(max_rings))
+
+    @staticmethod
+    def _keypoints(k):
+        k = np.ascontiguousarray(k, np.float32)
+        if k.size % 3:
+            raise LmonoError("a keypoint is three floats")
+        return k.reshape(-1, 3)
+
+    def compute(self, normals, keypoints):
+        k = self._keypoints(keypoints)
+        stats = np.zeros(8, np.int64)
+        self.ctx.check(self.ctx.L.lmono_fpfh_compute(self.ctx.h, self.h, normals.h, k.ctypes.data if len(k) else None, len(k), stats.ctypes.data))
+        self.stats = stats
+        return stats
+
+    @staticmethod
+    def compute_batch(fpfhs, normals, keypoints):
+        """One launch per phase for all streams; normals may name one SurfaceNormals more than once; returns stats [n][8]."""
+        n = len(fpfhs)
+        if n == 0 or len(normals) != n or len(keypoints) != n:
+            raise LmonoError("one SurfaceNormals and one keypoint array per FpfhDescriptors")
+        ctx = fpfhs[0].ctx
+        ks = [FpfhDescriptors._keypoints(k) for k in keypoints]
+        fh = (C.c_void_p * n)(*[a.h for a in fpfhs]); nh = (C.c_void_p * n)(*[b.h for b in normals])
+        kh = (C.c_void_p * n)(*[k.ctypes.data if len(k) else None for k in ks])
+        ms = np.array([len(k) for k in ks], np.int64)
+        stats = np.zeros((n, 8), np.int64)
+        ctx.check(ctx.L.lmono_fpfh_compute_batch(ctx.h, n, fh, nh, kh, ms.ctypes.data, stats.ctypes.data))
+        for a, s in zip(fpfhs, stats):
+            a.stats = s.copy()
+        return stats
+
+    def read(self):
+        """(descriptors [m][33] float32, contributing points [m] uint32, flags [m] uint32) of the last compute, in keypoint order."""
+        m = int(self.ctx.check(self.ctx.L.lmono_fpfh_read(self.ctx.h, self.h, None, None, None, 0)))
+        desc = np.zeros((max(m, 1), 33), np.float32); cnt = np.zeros(max(m, 1), np.uint32); flag = np.zeros(max(m, 1), np.uint32)
+        self.ctx.check(self.ctx.L.lmono_fpfh_read(self.ctx.h, self.h, desc.ctypes.data, cnt.ctypes.data, flag.ctypes.data, m))
+        return desc[:m], cnt[:m], flag[:m]
+
+    def keypoints(self):
+        """The keypoints of the last compute, [m][3] float32."""
+        m = int(self.ctx.check(self.ctx.L.lmono_fpfh_keypoints(self.ctx.h, self.h, None, 0)))
+        out = np.zeros((max(m, 1), 3), np.float32)
+        self.ctx.check(self.ctx.L.lmono_fpfh_keypoints(self.ctx.h, self.h, out.ctypes.data, m))
+        return out[:m]
+
+
+class CoarseAligner(_Handle):
+    """Sample-consensus initial alignment on FPFH descriptors on the device (lmono_sacia_*): align(src, tgt) takes two
+    FpfhDescriptors after a compute and returns the call's stats [ok, winning hypothesis, its error word, its inliers, void hypotheses,
+    usable source keypoints, usable target keypoints, n_hyp]; transform() is the [3][4] float64 that moves the source onto the target, what
+    CloudAligner.set_guess takes; errors() gives every hypothesis's (error word uint64, all ones: void; inliers uint32).  launch_hyps
+    splits the hypotheses over launches and changes no result.  An LmonoError carries the C return value in .code."""
+
+    _destroy = "lmono_sacia_destroy"
+
+    def __init__(self, ctx, min_sample_dist=0.5, max_corr=1.0, k_corr=10, n_hyp=1024, seed=1, launch_hyps=None):
+        super().__init__(ctx)
+        self.stats = np.zeros(8, np.int64)
+        self._create("lmono_sacia_create", C.c_float(min_sample_dist), C.c_float(max_corr), int(k_corr), int(n_hyp), C.c_uint32(seed), int(launch_hyps or 0))
+
+    def align(self, src, tgt):
+        stats = np.zeros(8, np.int64)
+        self.ctx.check(self.ctx.L.lmono_sacia_align(self.ctx.h, self.h, src.h, tgt.h, stats.ctypes.data))
+        self.stats = stats
+        return stats
+
+    def transform(self):
+        out = np.zeros(12, np.float64)
+        self.ctx.check(self.ctx.L.lmono_sacia_transform(self.ctx.h, self.h, out.ctypes.data))
+        return out.reshape(3, 4)
+
+    def errors(self):
+        n = int(self.ctx.check(self.ctx.L.lmono_sacia_errors(self.ctx.h, self.h, None, None, 0)))
+        err = np.zeros(max(n, 1), np.uint64); inl = np.zeros(max(n, 1), np.uint32)
+        self.ctx.check(self.ctx.L.lmono_sacia_errors(self.ctx.h, self.h, err.ctypes.data, inl.ctypes.data, n))
+        return err[:n], inl[:n]
+
+    def refine(self, cloud_aligner, source_points):
+        """The refineAlignment the reference leaves commented out: the fine alignment started from the coarse transform; returns its stats."""
+        cloud_aligner.set_guess(self.transform())
+        return cloud_aligner.align(source_points)
+
+
 TRACK_RECORD = np.dtype([("id", np.int32), ("x_n", np.float32), ("y_n", np.float32), ("u", np.float32), ("v", np.float32),
                          ("vx", np.float32), ("vy", np.float32), ("track_cnt", np.int32)])
 TRACK_MAX_POINTS = 512

@@ -387,6 +387,8 @@ static int64_t read_last(lmono_ctx *c, const char *who, int64_t n, int64_t cap, 
 #include "sor_abi.hip"
 #include "icp_abi.hip"
 #include "normals_abi.hip"
+#include "fpfh_abi.hip"
+#include "sacia_abi.hip"
 #include "track_abi.hip"
 #include "keyframe_abi.hip"
 #include "pnp_abi.hip"
